@@ -30,6 +30,14 @@ RCCL and one through the kernel-issued exchange from the SAME deltas, times both
 and takes the kernel-issued form only if its replicas are identical, its result
 is RCCL's to rounding, and it is faster; `config.parallelism` says which and why.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: it sets up, runs the
+untimed prefill and the W warm-up generations, times K generations and prints the line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, ...).  `--full` adds everything else the benchmark measures or checks: the
+roofline leg (HIP events over a further 50 generations), the CPU baselines (one core, all cores) and, with one rank, the
+replica checksum; `--no-roofline` / `--no-cpu-baseline` drop a leg of a `--full` run.  A run with more than one rank
+checks its replicas either way.  `--dump-outputs DIR` writes what the timed path left after its last step as
+DIR/<name>.npy (dump_outputs below), before any `--full` leg runs on.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -67,9 +75,15 @@ def parse():
                     help="weak (default, the driver's contract): --streams per GPU; strong: --streams-global "
                          "streams in all, split evenly over the ranks (BASELINE.json configs[3]: 256 over 8)")
     ap.add_argument("--streams-global", type=int, default=STREAMS, help="--scaling strong: streams of the whole job")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beside the headline: the roofline leg, the CPU baselines and, with one rank, "
+                         "the replica checksum (off: set up, warm up, time --steps generations, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path left after its last step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of EACH cpu leg")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true", help="--full without the roofline leg")
     ap.add_argument("--prefill", type=int, default=300, help="untimed generations before the warm-up")
     ap.add_argument("--dist", action="store_true",
                     help="join an RCCL group even with one rank (exercises the exchange step)")
@@ -83,7 +97,56 @@ def parse():
                     help="--gpus N without a launcher: seconds of wall clock after which the parent ends every rank "
                          "(the exact children it started) and exits 124")
     ap.add_argument("--all-cores-leg", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+# ------------------------------------------------------------------- outputs --
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20261016
+# the training set after the last timed step: weights, momentum and weight deltas of both layers, every stream's
+# history ring, layers, output error and error scale (float32), its ring index and generation counter (float64)
+DUMP_F32 = ("ih_w", "ho_w", "ih_m", "ho_m", "ih_delta", "ho_delta", "hist", "hidden", "output", "o_error",
+            "min_error_factor", "ih_scale")
+DUMP_F64 = ("index", "generation")
+
+
+def limit_outputs(arrays, limit=DUMP_LIMIT_BYTES, seed=DUMP_SAMPLE_SEED):
+    """arrays over `limit` bytes in all: each one is replaced by a fixed, seeded sample of its elements (flattened, in
+    index order, about the same fraction of every array); the sample depends only on the name, the size and the seed,
+    so two runs with the same arguments sample the same elements."""
+    import zlib
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total <= limit:
+        return dict(arrays)
+    frac = 0.95 * limit / total
+    out = {}
+    for k, a in arrays.items():
+        flat = a.reshape(-1)
+        n = min(flat.size, max(1024, int(flat.size * frac)))
+        if n < flat.size:
+            rng = np.random.default_rng([seed, zlib.crc32(k.encode())])
+            flat = flat[np.unique(rng.integers(0, flat.size, n))]
+        out[k] = flat
+    return out
+
+
+def dump_outputs(path, gpu, stats):
+    """--dump-outputs: what a caller of the timed path holds after its last step -- the training set (DUMP_F32,
+    DUMP_F64) and the timed region's training statistics (mean BPTT depth, hidden zero fraction, entropy in bits) --
+    as <path>/<name>.npy."""
+    import numpy as np
+    snap = gpu.snapshot()
+    arrays = {k: np.ascontiguousarray(snap[k], np.float32) for k in DUMP_F32}
+    arrays.update({k: snap[k].astype(np.float64) for k in DUMP_F64})
+    arrays["training_stats"] = np.asarray(stats, np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in limit_outputs(arrays).items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 # ------------------------------------------------------------------ launcher --
@@ -631,12 +694,14 @@ def main():
     mean_depth = st.bptt_depth_sum / max(st.count, 1)
     zero_frac = st.hidden_zeros / max(st.count, 1)
     t_entropy = -st.entropy / max(st.count, 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, gpu, (mean_depth, zero_frac, t_entropy))
 
-    # roofline leg: HIP events around the GEMM launches, on the launch stream, over a further
+    # roofline leg (--full): HIP events around the GEMM launches, on the launch stream, over a further
     # short run of the same loop (kept out of the timed region: the event records cost time)
     roofline = None
     exchange_us = 0.0 if world == 1 and not (dist or xchg) else None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         I, H = gpu.I, gpu.H
         amd.rnn_amd_kernel_time_enable(1)
         amd.rnn_amd_kernel_time_ms(0, None, 1)
@@ -738,8 +803,13 @@ def main():
         w = rc.view(gpu.net.contents.ih_weights, gpu.I, gpu.H)
         w[5, 5] = np.nextafter(w[5, 5], np.float32(2.0))
         amd.rnn_amd_host_written(gpu.net, rc.RNN_AMD_WEIGHTS)
-    cks_dev, cks_host = replica_checksums(amd, gpu, group if world > 1 else None, with_momentum=not xchg)
-    replicas_identical = len(set(cks_dev)) == 1 and cks_dev == cks_host
+    # (one rank: a --full check; more ranks: always, it is what makes the number a sharded run's)
+    check_replicas = args.full or world > 1
+    if check_replicas:
+        cks_dev, cks_host = replica_checksums(amd, gpu, group if world > 1 else None, with_momentum=not xchg)
+        replicas_identical = len(set(cks_dev)) == 1 and cks_dev == cks_host
+    else:
+        replicas_identical = True
 
     out = {
         "metric": "BPTT timesteps*streams/sec at 1024-hidden/256-stream",
@@ -779,16 +849,17 @@ def main():
         out["config"]["parallelism"] += " -- chosen at start-up (--exchange auto): " + selection["why"]
     # a sharded run says of itself whether it was one: the group RCCL reports, the replicas after the timed region
     # (bit-identical by construction on both exchange paths), what the exchange step cost a rank per generation
-    out["replicas_identical"] = replicas_identical
-    out["replica_checksums"] = ["%016x" % c for c in cks_dev]
-    out["replica_checksums_over_a_copy"] = ["%016x" % c for c in cks_host]
-    out["replica_checksum_of"] = "ih_weights||ho_weights" + ("" if xchg else "||ih_momentum||ho_momentum")
+    if check_replicas:
+        out["replicas_identical"] = replicas_identical
+        out["replica_checksums"] = ["%016x" % c for c in cks_dev]
+        out["replica_checksums_over_a_copy"] = ["%016x" % c for c in cks_host]
+        out["replica_checksum_of"] = "ih_weights||ho_weights" + ("" if xchg else "||ih_momentum||ho_momentum")
     out["exchange_us"] = exchange_us
     if world > 1 and not share_gpu and out["config"]["rccl_ranks"] != world:
         raise SystemExit("bench.py: %d ranks but the RCCL group has %d" % (world, out["config"]["rccl_ranks"]))
     if roofline is not None:
         out["roofline"] = roofline
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, TESTS)  # the checker's loaders (compiled reference, oracle): this leg only
         import recur_ctypes as checker_rc
         import scenarios as checker_sc

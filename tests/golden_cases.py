@@ -6,6 +6,8 @@ and compare with the stored reference results).
 Each scenario is a dict of plain parameters; ``run_scenario`` drives any driver
 object with the ApiSet / OracleSet interface of scenarios.py.
 """
+import os
+
 import numpy as np
 
 import recur_ctypes as rc
@@ -83,3 +85,80 @@ def run_scenario(driver, c, text, trace=None):
         driver.char_step(text, i, c["method"], m)
         if trace is not None:
             trace(i)
+
+
+# ---- what the tests that used to call the compiled reference live compare against (tests/golden/ref_live.npz and
+# ref_header_offsets.txt, written by tests/golden/make_golden_live.py where the reference is built)
+
+LIVE_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_live.npz")
+HEADER_OFFSETS_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_header_offsets.txt")
+
+# tests/test_oracle_vs_ref.py: 25 generations from the same cold start, per activation and optimiser
+RUN_KW = dict(input_size=42, hidden_size=57, output_size=42, S=5, D=9, learn_rate=5e-3, seed=17)
+RUN_TEXT_LEN, RUN_GENERATIONS, RUN_MOMENTUM = 3000, 25, 0.9
+RUN_ACTS = {"relu": rc.RELU, "resqrt": rc.RESQRT, "reclip20": rc.RECLIP20}
+RUN_METHODS = {"weighted": rc.WEIGHTED, "nesterov": rc.NESTEROV}
+
+# tests/test_gpu_parity.py: the hundred generations at full size on erewhon.txt (training entropy per window)
+HUNDRED_KW = dict(input_size=42, hidden_size=1024, output_size=42, S=256, D=20, learn_rate=1e-6, seed=3)
+HUNDRED_WINDOW, HUNDRED_GENERATIONS, HUNDRED_MOMENTUM = 25, 100, 0.9
+
+# tests/test_gpu_parity.py: tools/pernet_rate.c's arguments (its printed mean error)
+PERNET_ARGS = (("-H", "99", "-t", "1", "-d", "30", "-s", "400"), ("-H", "99", "-t", "3", "-d", "30", "-s", "150"),
+               ("-H", "256", "-t", "2", "-d", "12", "-s", "60"))
+
+# tests/test_abi.py: every field of every public struct and every enum value of recur-nn.h
+STRUCT_FIELDS = {
+    "RecurNN": ["i_size", "h_size", "o_size", "input_size", "hidden_size", "output_size", "ih_size",
+                "ho_size", "flags", "log", "mem", "input_layer", "hidden_layer", "output_layer",
+                "ih_weights", "ho_weights", "real_inputs", "rng", "bptt", "bottom_layer", "metadata",
+                "generation", "presynaptic_noise", "activation"],
+    "RecurNNBPTT": ["depth", "index", "i_error", "h_error", "o_error", "ih_momentum", "ho_momentum",
+                    "history", "ih_delta", "ho_delta", "ih_delta_tmp", "ih_aux", "ho_aux", "mem",
+                    "learn_rate", "ih_scale", "ho_scale", "momentum", "momentum_weight",
+                    "min_error_factor"],
+    "RecurExtraLayer": ["mem", "weights", "momentums", "aux", "delta", "inputs", "outputs", "i_error",
+                        "o_error", "learn_rate_scale", "input_size", "output_size", "i_size", "o_size",
+                        "overlap"],
+    "struct RecurInitialisationParameters": [
+        "method", "submethod", "bias_uses_submethod", "inputs_use_submethod", "fan_in_sum",
+        "fan_in_step", "fan_in_min", "fan_in_ratio", "flat_variance", "flat_shape", "flat_perforation",
+        "run_input_probability", "run_input_magnitude", "run_gain", "run_len_mean", "run_len_stddev",
+        "run_n", "run_loop", "run_crossing_paths", "run_inputs_miss", "run_input_at_start"],
+    "RecurErrorRange": ["start", "len"],
+}
+ENUMS = ["RNN_NET_FLAG_OWN_BPTT", "RNN_NET_FLAG_OWN_WEIGHTS", "RNN_NET_FLAG_LOG_APPEND",
+         "RNN_NET_FLAG_LOG_HIDDEN_SUM", "RNN_NET_FLAG_LOG_WEIGHT_SUM",
+         "RNN_NET_FLAG_BPTT_ADAPTIVE_MIN_ERROR", "RNN_NET_FLAG_NO_MOMENTUMS", "RNN_NET_FLAG_NO_DELTAS",
+         "RNN_NET_FLAG_BOTTOM_LAYER", "RNN_NET_FLAG_AUX_ARRAYS", "RNN_COND_USE_SCALE", "RNN_COND_USE_ZERO",
+         "RNN_COND_USE_LAWN_MOWER", "RNN_COND_USE_TALL_POPPY", "RNN_COND_USE_RAND",
+         "RNN_NET_FLAG_STANDARD", "RNN_MOMENTUM_WEIGHTED", "RNN_MOMENTUM_NESTEROV",
+         "RNN_MOMENTUM_SIMPLIFIED_NESTEROV", "RNN_MOMENTUM_CLASSICAL", "RNN_ADAGRAD", "RNN_ADADELTA",
+         "RNN_RPROP", "RNN_LAST_LEARNING_METHOD", "RNN_INIT_ZERO", "RNN_INIT_FLAT", "RNN_INIT_FAN_IN",
+         "RNN_INIT_RUNS", "RNN_RELU", "RNN_RESQRT", "RNN_RECLIP20", "RNN_INIT_DIST_UNIFORM",
+         "RNN_INIT_DIST_GAUSSIAN", "RNN_INIT_DIST_LOG_NORMAL", "RNN_INIT_DIST_SEMICIRCLE",
+         "RNN_CONDITIONING_INTERVAL", "RNN_COND_USE_OFFSET"]
+
+
+def header_offsets(tmp_dir, include_dir):
+    """One C program that prints the size and offset of every field in STRUCT_FIELDS, every enum value in ENUMS and
+    the header's constants, compiled against the recur-nn.h in include_dir: its output."""
+    import subprocess
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "recur-nn.h"', 'int main(void){']
+    for st, fields in STRUCT_FIELDS.items():
+        lines.append('printf("sizeof %s %%zu\\n", sizeof(%s));' % (st, st))
+        for f in fields:
+            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));'
+                         % (st, f, st, f, st, f))
+    for e in ENUMS:
+        lines.append('printf("%s %%ld\\n", (long)%s);' % (e, e))
+    lines.append('printf("%g %g %g %g\\n", (double)MAX_TOP_ERROR_FACTOR, (double)BASE_MIN_ERROR_FACTOR, '
+                 '(double)WEIGHT_SCALE, (double)RNN_MOMENTUM_WEIGHT);')
+    lines.append("return 0;}")
+    src = os.path.join(str(tmp_dir), "offsets.c")
+    exe = os.path.join(str(tmp_dir), "offsets")
+    with open(src, "w") as f:
+        f.write("\n".join(lines))
+    subprocess.run(["gcc", "-std=gnu11", "-D_GNU_SOURCE", "-fcommon", "-w", "-I", include_dir, src, "-o", exe],
+                   check=True)
+    return subprocess.run([exe], capture_output=True, text=True, check=True).stdout

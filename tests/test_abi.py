@@ -324,63 +324,15 @@ REF = "/root/reference"
 needs_reference = pytest.mark.skipif(not os.path.exists(os.path.join(REF, "recur-nn.h")),
                                      reason="build container only: needs /root/reference")
 
-STRUCT_FIELDS = {
-    "RecurNN": ["i_size", "h_size", "o_size", "input_size", "hidden_size", "output_size", "ih_size",
-                "ho_size", "flags", "log", "mem", "input_layer", "hidden_layer", "output_layer",
-                "ih_weights", "ho_weights", "real_inputs", "rng", "bptt", "bottom_layer", "metadata",
-                "generation", "presynaptic_noise", "activation"],
-    "RecurNNBPTT": ["depth", "index", "i_error", "h_error", "o_error", "ih_momentum", "ho_momentum",
-                    "history", "ih_delta", "ho_delta", "ih_delta_tmp", "ih_aux", "ho_aux", "mem",
-                    "learn_rate", "ih_scale", "ho_scale", "momentum", "momentum_weight",
-                    "min_error_factor"],
-    "RecurExtraLayer": ["mem", "weights", "momentums", "aux", "delta", "inputs", "outputs", "i_error",
-                        "o_error", "learn_rate_scale", "input_size", "output_size", "i_size", "o_size",
-                        "overlap"],
-    "struct RecurInitialisationParameters": [
-        "method", "submethod", "bias_uses_submethod", "inputs_use_submethod", "fan_in_sum",
-        "fan_in_step", "fan_in_min", "fan_in_ratio", "flat_variance", "flat_shape", "flat_perforation",
-        "run_input_probability", "run_input_magnitude", "run_gain", "run_len_mean", "run_len_stddev",
-        "run_n", "run_loop", "run_crossing_paths", "run_inputs_miss", "run_input_at_start"],
-    "RecurErrorRange": ["start", "len"],
-}
-ENUMS = ["RNN_NET_FLAG_OWN_BPTT", "RNN_NET_FLAG_OWN_WEIGHTS", "RNN_NET_FLAG_LOG_APPEND",
-         "RNN_NET_FLAG_LOG_HIDDEN_SUM", "RNN_NET_FLAG_LOG_WEIGHT_SUM",
-         "RNN_NET_FLAG_BPTT_ADAPTIVE_MIN_ERROR", "RNN_NET_FLAG_NO_MOMENTUMS", "RNN_NET_FLAG_NO_DELTAS",
-         "RNN_NET_FLAG_BOTTOM_LAYER", "RNN_NET_FLAG_AUX_ARRAYS", "RNN_COND_USE_SCALE", "RNN_COND_USE_ZERO",
-         "RNN_COND_USE_LAWN_MOWER", "RNN_COND_USE_TALL_POPPY", "RNN_COND_USE_RAND",
-         "RNN_NET_FLAG_STANDARD", "RNN_MOMENTUM_WEIGHTED", "RNN_MOMENTUM_NESTEROV",
-         "RNN_MOMENTUM_SIMPLIFIED_NESTEROV", "RNN_MOMENTUM_CLASSICAL", "RNN_ADAGRAD", "RNN_ADADELTA",
-         "RNN_RPROP", "RNN_LAST_LEARNING_METHOD", "RNN_INIT_ZERO", "RNN_INIT_FLAT", "RNN_INIT_FAN_IN",
-         "RNN_INIT_RUNS", "RNN_RELU", "RNN_RESQRT", "RNN_RECLIP20", "RNN_INIT_DIST_UNIFORM",
-         "RNN_INIT_DIST_GAUSSIAN", "RNN_INIT_DIST_LOG_NORMAL", "RNN_INIT_DIST_SEMICIRCLE",
-         "RNN_CONDITIONING_INTERVAL", "RNN_COND_USE_OFFSET"]
 
-
-@needs_reference
 def test_offsetof_table_equals_the_reference_header(tmp_path):
-    """Every field of every public struct, every enum value: one C program compiled twice,
-    once against the reference's recur-nn.h and once against include/recur-nn.h."""
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "recur-nn.h"', 'int main(void){']
-    for st, fields in STRUCT_FIELDS.items():
-        lines.append('printf("sizeof %s %%zu\\n", sizeof(%s));' % (st, st))
-        for f in fields:
-            lines.append('printf("%s.%s %%zu %%zu\\n", offsetof(%s, %s), sizeof(((%s *)0)->%s));'
-                         % (st, f, st, f, st, f))
-    for e in ENUMS:
-        lines.append('printf("%s %%ld\\n", (long)%s);' % (e, e))
-    lines.append('printf("%g %g %g %g\\n", (double)MAX_TOP_ERROR_FACTOR, (double)BASE_MIN_ERROR_FACTOR, '
-                 '(double)WEIGHT_SCALE, (double)RNN_MOMENTUM_WEIGHT);')
-    lines.append("return 0;}")
-    src = tmp_path / "offsets.c"
-    src.write_text("\n".join(lines))
-    outs = []
-    for tag, inc in (("ref", ["-I", REF]), ("amd", ["-I", os.path.join(ROOT, "include")])):
-        exe = tmp_path / ("offsets_" + tag)
-        subprocess.run(["gcc", "-std=gnu11", "-D_GNU_SOURCE", "-fcommon", "-w"] + inc + [str(src), "-o", str(exe)],
-                       check=True)
-        outs.append(subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout)
-    assert outs[0] == outs[1]
-    assert outs[0].count("\n") > 120
+    """Every field of every public struct, every enum value: one C program (golden_cases.header_offsets) compiled
+    against include/recur-nn.h prints what it printed compiled against the reference's recur-nn.h
+    (tests/golden/ref_header_offsets.txt, tests/golden/make_golden_live.py)."""
+    import golden_cases as gc
+    got = gc.header_offsets(tmp_path, os.path.join(ROOT, "include"))
+    assert got == open(gc.HEADER_OFFSETS_GOLDEN).read()
+    assert got.count("\n") > 120
 
 
 @needs_reference

@@ -448,7 +448,7 @@ def test_bench_with_two_ranks_says_of_itself_whether_it_was_a_sharded_run():
     no RCCL group -- it refuses duplicate devices --, the kernel-issued exchange between the two processes): the start-up
     cross-check runs (one update through the exchange, replicas compared through a kernel's loads and over a copy), the
     JSON line carries every rank's checksum, replicas_identical, exchange_us and which exchange ran and why."""
-    r, out = _bench(["--gpus", "2", "--steps", "10", "--warmup", "2", "--prefill", "30", "--streams", "64",
+    r, out = _bench(["--gpus", "2", "--steps", "10", "--warmup", "2", "--prefill", "30", "--streams", "64", "--full",
                      "--no-cpu-baseline"], {"RECUR_BENCH_SHARE_GPU": "1"})
     assert r.returncode == 0 and out, r.stdout[-2000:] + r.stderr[-3000:]
     assert out["n_gpus"] == 2 and out["config"]["global_streams"] == 128

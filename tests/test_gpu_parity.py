@@ -661,36 +661,30 @@ def test_the_north_star_generation_is_reproducible_bit_for_bit(amd):
         assert np.array_equal(snaps[0][k], snaps[1][k]), k
 
 
-@pytest.mark.skipif(not rc.have_ref(), reason="oracle/_ref/librecur_ref.so was not built (needs /root/reference)")
 def test_a_hundred_generations_at_full_size_track_the_compiled_reference(amd):
     """The same long run against the REFERENCE ITSELF (oracle/_ref: recur-nn.c + recur-nn-init.c compiled with the
     reference's own -Ofast flags, driven through its per-net calls: rnn_bptt_advance, one-hot opinion, softmax error,
     rnn_bptt_calc_deltas per stream, one rnn_apply_learning per generation -- charmodel-predict.c:288-327), not the
     oracle's restatement of it: 100 generations at hidden 1024 / 256 streams / depth 20 on
-    erewhon.txt from the same cold start; the training entropy of every window of 25 generations within 1 %."""
-    kw = dict(input_size=42, hidden_size=1024, output_size=42, S=256, D=20, learn_rate=1e-6, seed=3)
+    erewhon.txt from the same cold start; the training entropy of every window of 25 generations within 1 %.  The
+    reference's entropies are recorded in tests/golden/ref_live.npz (tests/golden/make_golden_live.py)."""
+    kw = gc.HUNDRED_KW
     text = rc.encode_erewhon(amd)
-    ref = rc.load_ref(fast=True)
+    ent_r = list(np.load(gc.LIVE_GOLDEN)["hundred.entropy_per_window"])
     g = sc.AmdBatchedSet(amd, **kw)
-    r = sc.ApiSet(ref, softmax_best_guess=ref.ref_softmax_best_guess, **kw)
     g.load_text(text)
-    win, n_gen = 25, 100
-    ent_g, ent_r = [], []
+    win, n_gen = gc.HUNDRED_WINDOW, gc.HUNDRED_GENERATIONS
+    assert len(ent_r) == n_gen // win
+    ent_g = []
     for w in range(n_gen // win):
-        lg = 0.0
         for i in range(w * win, (w + 1) * win):
-            g.char_step(text, i, rc.WEIGHTED, 0.9)
-            for e, _ in r.char_step(text, i, rc.WEIGHTED, 0.9):
-                l = 1.0 - e  # the probability given to the symbol that came (charmodel-helpers.h:11-13: capped log2)
-                lg += -100.0 if l < 1e-30 else float(np.log2(np.float32(l)))
+            g.char_step(text, i, rc.WEIGHTED, gc.HUNDRED_MOMENTUM)
         st = g.stats(clear=True)
         ent_g.append(-st.entropy / st.count)
-        ent_r.append(-lg / (win * kw["S"]))
     print("training entropy per window  device:", np.round(ent_g, 4), " reference:", np.round(ent_r, 4))
     assert np.allclose(ent_g, ent_r, rtol=1e-2), (ent_g, ent_r)
     assert ent_g[-1] < ent_g[0] - 0.1, ent_g  # it learns
     g.close()
-    r.close()
 
 
 @pytest.mark.parametrize("label,kw", [
@@ -1112,31 +1106,26 @@ def test_c_driver_trains_on_erewhon():
 def test_the_same_c_program_on_the_reference_and_on_the_product(tmp_path):
     """tools/pernet_rate.c is the reference's per-net call sequence (rnn_bptt_advance, rnn_opinion,
     the caller's softmax error, rnn_bptt_calculate / rnn_bptt_calc_deltas + rnn_apply_learning) as
-    one plain C program against include/recur-nn.h.  Linked against the compiled reference
-    (oracle/_ref) and against librecur_amd.so it must print the same mean error: the drop-in
-    boundary exercised by the same binary interface on both sides."""
+    one plain C program against include/recur-nn.h.  Linked against librecur_amd.so it must print the
+    mean error it printed linked against the compiled reference (oracle/_ref; recorded in
+    tests/golden/ref_live.npz by tests/golden/make_golden_live.py): the drop-in boundary exercised by
+    the same binary interface on both sides."""
     import os
     import re
     import subprocess
-    ref = os.path.join(rc.ROOT, "oracle", "_ref")
-    if not os.path.exists(os.path.join(ref, "librecur_ref.so")):
-        pytest.skip("oracle/_ref not built (needs /root/reference at build time)")
+    want = list(np.load(gc.LIVE_GOLDEN)["pernet.mean_error"])
+    assert len(want) == len(gc.PERNET_ARGS)
     src = os.path.join(rc.ROOT, "tools", "pernet_rate.c")
     inc = os.path.join(rc.ROOT, "include")
     lib = os.path.join(rc.ROOT, "recur_amd", "lib")
-    exe_ref, exe_amd = str(tmp_path / "pn_ref"), str(tmp_path / "pn_amd")
-    subprocess.run(["gcc", "-O2", "-std=gnu11", "-D_GNU_SOURCE", "-I" + inc, src, "-o", exe_ref, "-L" + ref,
-                    "-lrecur_ref", "-Wl,-rpath," + ref, "-lm"], check=True)
+    exe_amd = str(tmp_path / "pn_amd")
     subprocess.run(["gcc", "-O2", "-std=gnu11", "-D_GNU_SOURCE", "-I" + inc, src, "-o", exe_amd, "-L" + lib,
                     "-lrecur_amd", "-Wl,-rpath," + lib, "-lm"], check=True)
-    for args in (["-H", "99", "-t", "1", "-d", "30", "-s", "400"], ["-H", "99", "-t", "3", "-d", "30", "-s", "150"],
-                 ["-H", "256", "-t", "2", "-d", "12", "-s", "60"]):
-        out = []
-        for exe in (exe_ref, exe_amd):
-            r = subprocess.run([exe] + args, capture_output=True, text=True, timeout=600)
-            assert r.returncode == 0, r.stderr[-2000:]
-            out.append(float(re.search(r"mean error ([\d.]+)", r.stdout).group(1)))
-        assert abs(out[0] - out[1]) <= 1e-4 * abs(out[0]), (args, out)
+    for args, ref_err in zip(gc.PERNET_ARGS, want):
+        r = subprocess.run([exe_amd] + list(args), capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        got = float(re.search(r"mean error ([\d.]+)", r.stdout).group(1))
+        assert abs(ref_err - got) <= 1e-4 * abs(ref_err), (args, ref_err, got)
 
 
 def test_text_tools_train_save_score_and_sample(tmp_path):

@@ -1,35 +1,38 @@
-"""Live cross-check of the oracle against the real reference library
-(oracle/_ref/librecur_ref.so).  Skipped where that file is absent; the committed
-golden vectors (test_oracle_golden.py) are the portable form of the same pin."""
+"""Cross-check of the oracle against the real reference library over a run: the reference's struct sizes and its
+state after a run, recorded from the compiled reference (tests/golden/ref_live.npz, tests/golden/make_golden_live.py).
+The golden vectors of test_oracle_golden.py pin the oracle's single operations; this pins a whole training run."""
 import numpy as np
 import pytest
 
+import golden_cases as gc
 import recur_ctypes as rc
 import scenarios as sc
 
-pytestmark = pytest.mark.skipif(not rc.have_ref(), reason="oracle/_ref not built here")
+Z = np.load(gc.LIVE_GOLDEN)
+
+
+def ref_snapshot(prefix):
+    return {k[len(prefix):]: Z[k] for k in Z.files if k.startswith(prefix)}
 
 
 def test_abi_struct_sizes_match_reference():
     import ctypes as C
-    ref = rc.load_ref()
-    assert ref.ref_sizeof_net() == C.sizeof(rc.RecurNN)
-    assert ref.ref_sizeof_bptt() == C.sizeof(rc.RecurNNBPTT)
+    assert int(Z["sizeof_net"]) == C.sizeof(rc.RecurNN)
+    assert int(Z["sizeof_bptt"]) == C.sizeof(rc.RecurNNBPTT)
 
 
 @pytest.mark.parametrize("act", [rc.RELU, rc.RESQRT, rc.RECLIP20])
 @pytest.mark.parametrize("method", [rc.WEIGHTED, rc.NESTEROV])
 def test_oracle_tracks_reference_over_a_run(act, method):
-    ref = rc.load_ref()
-    text = sc.synthetic_text(3000)
-    kw = dict(input_size=42, hidden_size=57, output_size=42, S=5, D=9, activation=act, learn_rate=5e-3,
-              seed=17)
-    a = sc.ApiSet(ref, softmax_best_guess=ref.ref_softmax_best_guess, **kw)
-    o = sc.OracleSet(**kw)
-    assert sc.compare(o.snapshot(), a.snapshot(), 0) == []  # initialisation is bit-exact
-    for i in range(25):
-        a.char_step(text, i, method, 0.9)
-        o.char_step(text, i, method, 0.9)
-    assert sc.compare(o.snapshot(), a.snapshot(), 2e-6) == []
-    a.close()
+    an = {v: k for k, v in gc.RUN_ACTS.items()}[act]
+    mn = {v: k for k, v in gc.RUN_METHODS.items()}[method]
+    text = sc.synthetic_text(gc.RUN_TEXT_LEN)
+    o = sc.OracleSet(activation=act, **gc.RUN_KW)
+    start, end = ref_snapshot("run.start."), ref_snapshot("run.%s.%s.end." % (an, mn))
+    snap = o.snapshot()
+    assert set(start) == set(end) == set(sc.FLOAT_KEYS + sc.EXACT_KEYS) & set(snap)  # every array compared
+    assert sc.compare(snap, start, 0) == []  # initialisation is bit-exact
+    for i in range(gc.RUN_GENERATIONS):
+        o.char_step(text, i, method, gc.RUN_MOMENTUM)
+    assert sc.compare(o.snapshot(), end, 2e-6) == []
     o.close()

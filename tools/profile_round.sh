@@ -9,7 +9,7 @@ out=${1:-gpurun_out/prof}
 root=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp && cd "$root" || exit 1
 rm -rf "$out" && mkdir -p "$out"
-CMD="python3 bench.py --no-cpu-baseline --steps 60 --warmup 10"
+CMD="python3 bench.py --full --no-cpu-baseline --steps 60 --warmup 10"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -o s -- $CMD > "$out/bench_under_rocprof.json" 2> "$out/trace.err"
 cp $(find "$out/trace" -name 's_kernel_stats.csv' | head -1) "$out/kernel_stats.csv"
 python3 tools/launch_boundaries.py $(find "$out/trace" -name 's_kernel_trace.csv' | head -1) k_fwd_fused 40 > "$out/launch_boundaries.txt"
