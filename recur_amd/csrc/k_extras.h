@@ -1,6 +1,6 @@
 // k_extras.h -- the chain "extras" (column 0 and the input columns of every step's error, recur-nn.c:338-376)
 // and the data-dependent control of bptt_and_accumulate_error (recur-nn.c:317-330, 383-413) as device
-// functions: shared by k_extras_control / k_extras_gather / k_bptt_control (kernels_bptt.hip) and by the tail of
+// functions: shared by k_extras_control / k_bptt_control (kernels_bptt.hip) and by the tail of
 // the one-launch chain (kernels_chain.hip), which runs them for its own streams without a launch of their own.
 #pragma once
 #include "k_common.h"
@@ -225,9 +225,9 @@ __device__ __forceinline__ void bptt_control_wave(const View &v, int r, int j, i
     as_global(v.b.depth_log)[r] = D - t;
     as_global(v.b.stat_depth)[r] = ci.depth_total + (double)(D - t);
   }
-  /* 0x20000000: rnn_bptt_calculate without batching leaves the UNSCALED sum in ih_delta and puts
+  /* RAMD_IH_SCALE_IN_RATE: rnn_bptt_calculate without batching leaves the UNSCALED sum in ih_delta and puts
    * ih_scale into the rate (recur-nn.c:966-975) */
-  const float cf = (flags & 0x20000000u) ? 1.0f : scale;
+  const float cf = (flags & RAMD_IH_SCALE_IN_RATE) ? 1.0f : scale;
   for (int k = lane; k < D; k += 64) as_global(v.b.coef)[(size_t)k * s.Scap + r] = (k < n_exec) ? cf : 0.0f;
 }
 

@@ -491,25 +491,19 @@ template <bool UNI> struct ProbDelta {
 
 // Split-K factor: enough workgroups to give every CU two or three, without
 // shredding K into single tiles.
-static int pick_ks(int tiles, int nkt, const char *env, size_t slab_floats, size_t out_floats) {
-  int forced = env_int(env, 0);
-  int ks;
-  if (forced > 0) {
-    ks = forced;
-  } else {
-    const int cus = 256;
-    double best = 1e30;
-    ks = 1;
-    for (int k = 1; k <= 16 && k <= nkt; k++) {
-      long wgs = (long)tiles * k;
-      /* CUs run up to ~3 of these workgroups side by side; count time in
-       * "K tiles on the busiest CU" plus a fill/drain charge per workgroup */
-      double per_cu = (double)((wgs + cus - 1) / cus);
-      double cost = per_cu * ((double)nkt / k) + 2.0 * (per_cu > 3 ? per_cu / 3 : 1) + 0.15 * k;
-      if (cost < best) {
-        best = cost;
-        ks = k;
-      }
+static int pick_ks(int tiles, int nkt, size_t slab_floats, size_t out_floats) {
+  const int cus = 256;
+  double best = 1e30;
+  int ks = 1;
+  for (int k = 1; k <= 16 && k <= nkt; k++) {
+    long wgs = (long)tiles * k;
+    /* CUs run up to ~3 of these workgroups side by side; count time in
+     * "K tiles on the busiest CU" plus a fill/drain charge per workgroup */
+    double per_cu = (double)((wgs + cus - 1) / cus);
+    double cost = per_cu * ((double)nkt / k) + 2.0 * (per_cu > 3 ? per_cu / 3 : 1) + 0.15 * k;
+    if (cost < best) {
+      best = cost;
+      ks = k;
     }
   }
   if (ks > nkt) ks = nkt;

@@ -163,7 +163,7 @@ __device__ unsigned g_xchg_gave_up;
 template <int METHOD>
 __global__ __launch_bounds__(256) void k_apply_xchg(XchgArgs xa, float momentum, float mw, const unsigned *abort_word) {
   /* a barrier in front of this launch gave up (a rank missing): the ranks' sums are not all there -- touch nothing;
-   * the host aborts at its next synchronisation (rnn_core.c: dsync), until then no weights are made from half a sum */
+   * the host aborts at its next synchronisation (engine.c: ramd_dsync), until then no weights are made from half a sum */
   if (abort_word && __hip_atomic_load(&g_xchg_gave_up, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return;
   const int g = blockIdx.x >= xa.first1 ? 1 : 0;
   const XchgSeg &sg = xa.seg[g];
@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void k_apply_xchg(XchgArgs xa, float momentum,
 // slot has reached it.  What the previous kernels of this stream wrote is visible to the peers' later kernels through
 // the kernel boundaries (release at the end of a launch, acquire at the start of the next, both at system scope).
 // Bounded: 20 s of polling by the device's own clock (RECUR_AMD_XCHG_BARRIER_TIMEOUT_S) raise *abort_word (see dsync in
-// rnn_core.c) and the device's copy of it.
+// engine.c) and the device's copy of it.
 __global__ void k_xchg_barrier(unsigned *flags, int rank, int world, unsigned seq, unsigned *abort_word,
                                unsigned long long timeout_ticks) {
   const int p = threadIdx.x;
@@ -444,7 +444,7 @@ extern "C" void ramd_launch_apply_xchg(ramd_stream_t st_, int method, int rank, 
 // A replica's checksum, formed ON THE DEVICE through the loads every kernel of the path uses (L2, the per-XCD
 // caches): sum over the 32-bit words of `n_arrays` arrays in a row of word_i * (2 i + 1) mod 2^64, i counted through
 // the row -- independent of the order of summation (atomics), sensitive to position.  Beside the same sum over a
-// device-to-host COPY of the arrays (rnn_core.c: rnn_amd_set_replica_checksum) it is what tells a launcher that what
+// device-to-host COPY of the arrays (exchange.c: rnn_amd_set_replica_checksum) it is what tells a launcher that what
 // peers stored into this rank's arrays is what this rank's kernels read.
 struct CksumArgs {
   const unsigned *a[4];

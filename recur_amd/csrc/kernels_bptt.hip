@@ -772,22 +772,6 @@ __global__ void k_ho_delta_finalize(View v, const float *slab, int ks, int accum
 
 #include "k_extras.h"
 
-
-template <int MAXQ>
-__global__ __launch_bounds__(256) void k_extras_gather(View v, int row0, int nrows, int nx, int nxp,
-                                                       int tn) {
-  const RamdShape &s = v.sh;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int m = blockIdx.x * 4 + wave;
-  if (m >= s.D * nrows) return;
-  const int t = m / nrows, r = row0 + (m - t * nrows);
-  ExtrasIn<MAXQ> in;
-  extras_load<MAXQ>(v, t, r, nx, tn, lane, in);
-  float es = extras_compute<MAXQ>(v, t, r, nx, nxp, tn, lane, in);
-  if (tn == 0) es += row_sumsq_load(v, t + 1, r, lane);
-  if (lane == 0) v.b.esum[(size_t)t * s.Scap + r] = es;
-}
-
 // Finalize of the extras GEMM: applies the row rule to column 0 and the input
 // columns, keeps the raw values in ex[t+1][s][c] (for the h_error / i_error
 // images) and adds their squares as the last partial sum.  One wave per (t, s).
@@ -1412,7 +1396,7 @@ __global__ __launch_bounds__(256) void k_bptt_control(View v, int row0, int nrow
   bptt_control_wave(v, r, j, lane, bptt_control_load(v, r, j, active), flags, v.b.esum + r, (size_t)v.sh.Scap);
 }
 
-// k_extras_gather and k_bptt_control in one launch, one workgroup per stream: the waves
+// The extras' gather and k_bptt_control in one launch, one workgroup per stream: the waves
 // share out the stream's steps, leave each step's error sum in LDS, and wave 0 then runs
 // the control logic on them (nothing else needs the sums of other streams).  The body is
 // extras_control_stream (k_extras.h), which the one-launch chain also runs in its tail.
@@ -1584,7 +1568,7 @@ __global__ __launch_bounds__(1024) void k_bptt_small(View v, int r, int accumula
     }
   }
   __syncthreads(); /* (also: every plane store of this workgroup has been performed) */
-  const float scale = (flags & 0x20000000u) ? 1.0f : red[16]; /* see bptt_control_wave */
+  const float scale = (flags & RAMD_IH_SCALE_IN_RATE) ? 1.0f : red[16]; /* see bptt_control_wave */
   {
     /* bptt->h_error / i_error as the reference leaves them: k_err_writeback's job, from the planes
      * this workgroup has just written (nothing of them was read before: no stale lines) */
@@ -1747,7 +1731,7 @@ extern "C" void ramd_launch_clear_deltas(ramd_stream_t st_, const RamdShape *sh,
 
 static int g_calc_wrote_images = 0;
 /* Multi-GPU: the weight-delta GEMM in two row halves, so that the sum over the ranks of the first half
- * can travel while the second half is still being multiplied (rnn_core.c sets the hook for the call it
+ * can travel while the second half is still being multiplied (set_api.c sets the hook for the call it
  * wants split; the launcher calls it after each half's deltas are complete in ih_delta || ho_delta,
  * with the half's range in floats from ih_delta). */
 static void (*g_delta_half_hook)(void *ctx, int half, size_t first_float, size_t n_floats) = nullptr;
@@ -1775,7 +1759,7 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
   size_t shm = (size_t)(sh->O + sh->H) * sizeof(float);
   bool images_done = !(flags & RAMD_IMAGES_PENDING);
   const int h_alen0 = b->mheads_alen, h_ncls0 = h_alen0 > 0 ? sh->output_size / h_alen0 : 0;
-  const bool top_sparse = !(flags & 0x40000000u) && ranges && range_stride && (flags & RAMD_RANGES_ARE_HEADS) &&
+  const bool top_sparse = !(flags & RAMD_TOP_DONE) && ranges && range_stride && (flags & RAMD_RANGES_ARE_HEADS) &&
                           h_alen0 >= 24 && h_alen0 <= 128 && h_ncls0 <= 64 && sh->output_size == h_ncls0 * h_alen0 &&
                           b->mheads_part && (size_t)sh->Scap * h_ncls0 * sh->H <= b->mheads_part_floats &&
                           row0 + nrows <= sh->Scap && env_int("RECUR_AMD_TOP_SPARSE", 1);
@@ -1784,7 +1768,7 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
     images_done = true;
     flags &= ~RAMD_IMAGES_PENDING;
   }
-  if (!(flags & 0x40000000u)) { /* ramd_launch_text_top has already done the top backprop */
+  if (!(flags & RAMD_TOP_DONE)) { /* ramd_launch_text_top has already done the top backprop */
     const int h_alen = h_alen0, h_ncls = h_ncls0;
     if (top_sparse) {
       /* the multi-head loss's ranges, only the heads a stream trained: partial products per (stream, head), then the
@@ -1863,7 +1847,7 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
                       nrows % (4 * DNW) == 0 && nrows <= 256 * (DD_FLAG_LOADS / 2) && row0 + nrows <= sh->Scap &&
                       sh->activation != 5 && dn_it >= DP && dn_it % DP == 0 &&
                       !(g_delta_half_hook && env_int("RECUR_AMD_DIST_OVERLAP", 0)) && env_int("RECUR_AMD_DELTA_DIRECT", 1);
-  const bool direct_fuse = direct && dks == 1 && defer && defer->fuse_want && !accumulate && !(flags & 0xa0000000u);
+  const bool direct_fuse = direct && dks == 1 && defer && defer->fuse_want && !accumulate && !(flags & (RAMD_NO_HO_DELTA | RAMD_IH_SCALE_IN_RATE));
   /* (HoWork's preconditions: up to 256 streams, o_size <= 48, five rows of ho_delta per workgroup at most) */
   /* (not where the chain launch has workgroups without chain work -- half of it or more, ramd_chain_steps: there the
    * request costs the chain nothing, here it costs 2.4 us: the 48 loads per wave queue behind the ring's at the CU's
@@ -1881,9 +1865,9 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
   /* (up to 256 streams: the request costs the chain launch 0.014 us per stream -- 3.6 us at 256 against the GEMM's
    * 6.2 us launch -- and nothing where the set leaves workgroups of that launch without chain work: 32 streams
    * 145.3 -> 141.0 us per generation, 64: 155.7 -> 151.2, 256: 244.8 -> 242.4) */
-  const bool ho_asked = !ho_in_delta && !(flags & 0x80000000u) && !ranges && !accumulate && nrows >= 16 && nrows <= 256 && sh->O <= 48 &&
+  const bool ho_asked = !ho_in_delta && !(flags & RAMD_NO_HO_DELTA) && !ranges && !accumulate && nrows >= 16 && nrows <= 256 && sh->O <= 48 &&
                         env_int("RECUR_AMD_HO_IN_CHAIN", 1);
-  auto ho_classic = [&]() { /* (the fused single-net path, flag 0x80000000, updates W_ho directly) */
+  auto ho_classic = [&]() { /* (the fused single-net path, RAMD_NO_HO_DELTA, updates W_ho directly) */
     if (ranges && range_stride && (flags & RAMD_RANGES_ARE_HEADS) && b->mheads_alen >= 24 && b->mheads_alen <= 128 &&
         sh->output_size % b->mheads_alen == 0 && sh->output_size / b->mheads_alen <= 64 && env_int("RECUR_AMD_HO_HEADS", 1)) {
       /* the multi-head loss: only the heads a stream trained carry error (k_ho_delta_heads) */
@@ -1897,7 +1881,7 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
     int tm = (sh->H + BM - 1) / BM, tn = (sh->O + BN - 1) / BN;
     int nkt = (nrows + BK - 1) / BK;
     int ho = sh->H * sh->O;
-    int ks = pick_ks(tm * tn, nkt, "RECUR_AMD_KS_HO", b->slab_floats, (size_t)ho);
+    int ks = pick_ks(tm * tn, nkt, b->slab_floats, (size_t)ho);
     /* per-stream 1.0 / 0.0 participation flags as floats (b->coef plane 0 is free here:
      * k_bptt_control rewrites it later in this call) */
     const float *live = b->ones + row0;
@@ -1945,7 +1929,7 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
     ho_req.active = active;
     ho_req.row0 = row0;
     ho_req.nrows = nrows;
-  } else if (!(flags & 0x80000000u) && !ho_in_delta) {
+  } else if (!(flags & RAMD_NO_HO_DELTA) && !ho_in_delta) {
     ho_classic();
   }
   // BPTT chain: D dependent steps, one launch each, then the extras of all steps
@@ -1979,9 +1963,9 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
   {
     /* the extras and the control logic ride in the one-launch chain's tail where they are the gather form
      * (XcWork, k_common.h); where the chain declines, the launch below */
-    const bool extras_gather = sh->H <= 2304 && !env_int("RECUR_AMD_EXTRAS_GEMM", 0) && !(b->dense_inputs && nx > 8);
+    const bool extras_gather = sh->H <= 2304 && !(b->dense_inputs && nx > 8);
     XcWork xc_req = {};
-    if (extras_gather && nx <= 128 && !env_int("RECUR_AMD_EXTRAS_SPLIT", 0) && env_int("RECUR_AMD_XC_IN_CHAIN", 1) &&
+    if (extras_gather && nx <= 128 && env_int("RECUR_AMD_XC_IN_CHAIN", 1) &&
         (size_t)(sh->D + 1) * sh->Scap * sh->I * sizeof(float) < ((size_t)1 << 31)) { /* (32-bit byte offsets into the planes) */
       xc_req.on = 1;
       xc_req.row0 = row0;
@@ -1990,7 +1974,7 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
       xc_req.active = active;
       xc_req.flags = flags;
     } else if (b->dense_inputs && nx > 8 && nx <= 16 * XD_NT && (sh->hidden_size == 512 || sh->hidden_size == 1024) &&
-               sh->D <= 63 && !env_int("RECUR_AMD_EXTRAS_GEMM", 0) && env_int("RECUR_AMD_XC_IN_CHAIN", 1) &&
+               sh->D <= 63 && env_int("RECUR_AMD_XC_IN_CHAIN", 1) &&
                env_int("RECUR_AMD_XC_DENSE_IN_CHAIN", 1) &&
                (size_t)(sh->D + 1) * sh->Scap * sh->I * sizeof(float) < ((size_t)1 << 31)) {
       /* dense inputs (gstclassify's features): the extras as a small GEMM in the one-launch chain's tail (extras_dense_tail) */
@@ -2015,37 +1999,25 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
     }
     int M = sh->D * nrows;
     int etm = (M + BM - 1) / BM, etn = (nx + BN - 1) / BN, nkt = (sh->H + BK - 1) / BK;
-    int ks = pick_ks(etm * etn, nkt, "RECUR_AMD_KS_EXTRAS", b->slab_floats, (size_t)M * nxp);
+    int ks = pick_ks(etm * etn, nkt, b->slab_floats, (size_t)M * nxp);
     /* the gather over the non-zero input rows (one-hot symbols: two rows per step and stream) or,
      * for dense inputs with more than a handful of columns, the GEMM over all of them */
     if (xc_req.done) {
       control_done = true; /* extras and control: done in the chain launch */
     } else if (extras_gather) {
       const int nq = (sh->H / 4 + 63) / 64;
-      if (env_int("RECUR_AMD_EXTRAS_SPLIT", 0)) {
-        if (nq <= 5)
-          RAMD_LAUNCH(k_extras_gather<5>, dim3((M + 3) / 4), dim3(256), 0, st, v, row0, nrows, nx,
-                             nxp, tn_parts);
-        else if (nq <= 8)
-          RAMD_LAUNCH(k_extras_gather<8>, dim3((M + 3) / 4), dim3(256), 0, st, v, row0, nrows, nx,
-                             nxp, tn_parts);
-        else /* h_size 2052: hidden 2048 */
-          RAMD_LAUNCH(k_extras_gather<9>, dim3((M + 3) / 4), dim3(256), 0, st, v, row0, nrows, nx,
-                             nxp, tn_parts);
-      } else {
-        /* extras and control in one launch, one workgroup per stream */
-        const size_t shm = (size_t)(2 * sh->D + 1) * sizeof(float);
-        if (nq <= 5)
-          RAMD_LAUNCH((k_extras_control<5, 1024>), dim3(nrows), dim3(1024), shm, st, v, row0, nrows,
-                             nx, nxp, tn_parts, active, flags);
-        else if (nq <= 8)
-          RAMD_LAUNCH((k_extras_control<8, 512>), dim3(nrows), dim3(512), shm, st, v, row0, nrows,
-                             nx, nxp, tn_parts, active, flags);
-        else /* h_size 2052: hidden 2048 */
-          RAMD_LAUNCH((k_extras_control<9, 512>), dim3(nrows), dim3(512), shm, st, v, row0, nrows,
-                             nx, nxp, tn_parts, active, flags);
-        control_done = true;
-      }
+      /* extras and control in one launch, one workgroup per stream */
+      const size_t shm = (size_t)(2 * sh->D + 1) * sizeof(float);
+      if (nq <= 5)
+        RAMD_LAUNCH((k_extras_control<5, 1024>), dim3(nrows), dim3(1024), shm, st, v, row0, nrows,
+                           nx, nxp, tn_parts, active, flags);
+      else if (nq <= 8)
+        RAMD_LAUNCH((k_extras_control<8, 512>), dim3(nrows), dim3(512), shm, st, v, row0, nrows,
+                           nx, nxp, tn_parts, active, flags);
+      else /* h_size 2052: hidden 2048 */
+        RAMD_LAUNCH((k_extras_control<9, 512>), dim3(nrows), dim3(512), shm, st, v, row0, nrows,
+                           nx, nxp, tn_parts, active, flags);
+      control_done = true;
     } else if (nx <= 16 * XD_NT && env_int("RECUR_AMD_EXTRAS_DENSE", 1)) {
       /* dense inputs, up to 47 of them: GEMM and finalize in one launch */
       ramd_launch_extras_dense(st, v, sh, row0, nrows, nx, nxp, tn_parts, 0, sh->D);
@@ -2077,11 +2049,11 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
     int rtiles = (nrows + BK - 1) / BK;
     int nkt = sh->D * rtiles;
     size_t n = (size_t)sh->I * sh->H;
-    int ks = pick_ks(tm * tn, nkt, "RECUR_AMD_KS_DELTA", b->slab_floats, n);
-    const bool big = env_int("RECUR_AMD_DELTA_TILE", sh->I >= 256 && nkt >= 16 ? 128 : 64) == 128;
+    int ks = pick_ks(tm * tn, nkt, b->slab_floats, n);
+    const bool big = sh->I >= 256 && nkt >= 16;
     if (big) {
       int tm2 = (sh->I + BM2 - 1) / BM2, tn2 = (ncol - 1 + BN2 - 1) / BN2;
-      ks = pick_ks(tm2 * tn2, nkt, "RECUR_AMD_KS_DELTA", b->slab_floats, n);
+      ks = pick_ks(tm2 * tn2, nkt, b->slab_floats, n);
     }
     int rows_core = sh->I, ks_rest = ks;
     float *rest_base = b->slab; /* planes of the rows from rows_core on: rest_base + z * rest_stride */
@@ -2143,7 +2115,7 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
         a.rgroups = drg;
         { /* the shares of a SIMD's two waves (dd_body): 5 / 8 to the first where the loop is long, rounded to whole rings */
           const int pct = env_int("RECUR_AMD_DELTA_FAST_PCT", 66), n_pair = 2 * (dn_it / dks);
-          if (pct > 0 && dn_it / dks >= env_int("RECUR_AMD_DELTA_FAST_MIN", 40)) {
+          if (pct > 0 && dn_it / dks >= 40) {
             int nf = (n_pair * pct / 100 + P / 2) / P * P;
             if (nf < P) nf = P;
             if (nf > n_pair - P) nf = n_pair - P;
@@ -2236,11 +2208,8 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
       o.col0 = 1;
       o.row0m = 0;
       int tiles = o.tm * o.tn;
-      int kd = env_int("RECUR_AMD_KS_DELTA", 0);
-      if (kd != 1 && kd != 2 && kd != 4 && kd != 8) {
-        kd = 8;
-        while (kd > 1 && tiles * kd > 256) kd >>= 1;
-      }
+      int kd = 8;
+      while (kd > 1 && tiles * kd > 256) kd >>= 1;
       while (kd > 1 && (kd > nkt || (size_t)kd * n > b->slab_floats)) kd >>= 1;
       o.ks = ks = kd;
       const int per = 8 / kd;
@@ -2348,7 +2317,7 @@ extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
          * each, or three per CU and three tiles each: 0.87 us per 64 x 64 x 32 tile step and CU
          * either way), while every further plane costs the optimiser's sum: 16 it is. */
         int tmr = (rest_rows + BM - 1) / BM, tnr = (ncol - 1 + BN - 1) / BN;
-        ks_rest = pick_ks(tmr * tnr, nkt, "RECUR_AMD_KS_DELTA_REST", (size_t)RAMD_MAX_REST_PLANES, 1);
+        ks_rest = pick_ks(tmr * tnr, nkt, (size_t)RAMD_MAX_REST_PLANES, 1);
         if (ks_rest > RAMD_MAX_REST_PLANES) ks_rest = RAMD_MAX_REST_PLANES;
         if (ks_rest > nkt) ks_rest = nkt;
         while (ks_rest > 1 && (size_t)ks * n + (size_t)ks_rest * rest_plane > b->slab_floats) ks_rest--;

@@ -28,7 +28,7 @@ BND_DECL(g_bnd_chain, ramd_bnd_chain_stamps)
 // output tiles, (S/32) x (hidden/32) workgroups = 256 at the 1024 / 256 size,
 // one per CU, no split-K slabs and no separate finalize pass.  Column 0 (bias
 // row) and the real-input rows only feed the sum of squares and are done for
-// all steps together afterwards (k_extras_gather, or the ProbExtras GEMM for very wide nets).
+// all steps together afterwards (k_extras_control, or the ProbExtras GEMM for very wide nets).
 //
 // Workgroup = 8 waves.  Waves 0-3 multiply: each takes a quarter of every 128-deep K
 // stage (in-workgroup split-K, summed through LDS at the end).  Waves 4-7 only move data:
@@ -1105,7 +1105,7 @@ const View *device_view(hipStream_t st, const View &v) {
  * kernels take XCD and seat from the workgroup number (g_xcd_static; every wave still checks its XCD against the
  * register) instead of drawing a ticket.  A probe that fails switches the kernel off for the process; the
  * launch-per-step chain takes its place from the first call on.  A give-up in
- * mid-run -- a co-tenant that arrives later -- is caught at the next synchronisation (rnn_core.c: dsync). */
+ * mid-run -- a co-tenant that arrives later -- is caught at the next synchronisation (engine.c: ramd_dsync). */
 static bool g_chain_validated = false, g_chain_broken = false, g_xcd_static = false, g_seat_table = false;
 static unsigned *g_seats = nullptr; /* SeatTable, device */
 
@@ -1220,7 +1220,7 @@ static void chain_validate(hipStream_t st) {
 /* Another queue of this process may have work on the device beside the chain (the noise generated ahead on a side
  * stream, an exchange overlapped on a communication stream): the dispatcher then deals the workgroups of BOTH
  * launches to the XCDs in turn, and workgroup i of the chain is not on XCD i % 8 (found by the configs[3] test, whose
- * every wave's check raised the abort word).  rnn_core.c says so when it creates such a stream; from then on the
+ * every wave's check raised the abort word).  The host code says so when it creates such a stream (ramd_note_side_stream); from then on the
  * chain draws tickets. */
 static bool g_side_streams = false;
 static unsigned g_ticket_launches = 0; /* launches that drew tickets: 32 per XCD each */

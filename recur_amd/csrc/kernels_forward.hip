@@ -133,7 +133,7 @@ __global__ void k_presynaptic_noise(View v, int row0, int nrows, float deviation
 }
 
 /* The same values without touching anything: out[j][1..H) and the generator state after them
- * (see noise_speculate in rnn_core.c: runs on a second stream while the rest of the previous
+ * (see noise_speculate in set_api.c: runs on a second stream while the rest of the previous
  * generation is still being computed) */
 /* src / tclass / skip: the forms for the multi-head step -- start from the states an earlier pass left (`src`: the ones
  * the pass before adopted, or the ones the speculation before this one wrote) and first make the draws the multi-head
@@ -1139,31 +1139,22 @@ extern "C" int ramd_launch_forward_fused(ramd_stream_t st_, const RamdShape *sh,
       (for_top ? ((mode != RAMD_IN_TEXT && !dense_ok) || !ramd_text_top_ok(sh))
                : ((mode != RAMD_IN_TEXT && mode != RAMD_IN_ONE_HOT && !dense_ok) || !env_int("RECUR_AMD_FWD_FUSED_ANY", 1))) ||
       env_int("RECUR_AMD_NO_FWD_FUSED", 0)) {
-    if (env_int("RECUR_AMD_TRACE_FWD", 0))
-      fprintf(stderr, "librecur_amd: forward not fused: uniform_idx %d, bottom %d, hidden %d, rows %d + %d of %d, mode %d, "
-                      "for_top %d, dense %p, inputs %d\n", b->uniform_idx, sh->bI, sh->hidden_size, row0, nrows, sh->Scap, mode,
-              for_top, (const void *)dense, sh->input_size);
     return 0;
   }
   const int tm = (nrows + CM - 1) / CM, tn = sh->hidden_size / CN;
   /* dense inputs: where the 32 x 32 tiles are one round of workgroups (gstclassify's 512 / 128: 64 tiles; one launch less,
    * the time of assemble + GEMM).  Beyond that the tiles' operand traffic decides -- 8 flop per byte from L2: 67.7 us at
    * 2048 / 512 (1024 tiles) against 58.7 + 6.3 us for k_assemble and the 128 x 128 tiles of k_gemm */
-  if (mode == RAMD_IN_DENSE && tm * tn > 256 && !env_int("RECUR_AMD_FWD_FUSED_DENSE_ANY", 0)) return 0;
+  if (mode == RAMD_IN_DENSE && tm * tn > 256) return 0;
   /* plane 0: sums; plane 1: [tn][nrows][4] padding partials */
-  if ((size_t)nrows * sh->H + (size_t)tn * nrows * 4 > b->slab_floats || tn * 4 > sh->H) {
-    if (env_int("RECUR_AMD_TRACE_FWD", 0))
-      fprintf(stderr, "librecur_amd: forward not fused: workspace of %zu floats, %zu wanted\n", b->slab_floats,
-              (size_t)nrows * sh->H + (size_t)tn * nrows * 4);
-    return 0;
-  }
+  if ((size_t)nrows * sh->H + (size_t)tn * nrows * 4 > b->slab_floats || tn * 4 > sh->H) return 0;
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
   const View *d_view = device_view(st, v);
   const int nstages = (sh->hidden_size + CK - 1) / CK;
   const int blocks = ((tn + 7) / 8) * 8 * tm;
   int ev = timing_begin(st, T_FWD);
-  const bool exact = sh->hidden_size % CK == 0 && !env_int("RECUR_AMD_FWD_NS0", 0);
+  const bool exact = sh->hidden_size % CK == 0;
 #define FWD_FUSED(NS)                                                                              \
   RAMD_LAUNCH((k_fwd_fused<NS>), dim3(blocks), dim3(512), 0, st, d_view, b->uniform_idx, row0, \
                      nrows, tm, tn, nstages, mode, text_i, global_first, n_set, dense, ld)
@@ -1219,7 +1210,7 @@ static void launch_output_layer(hipStream_t st, const RamdShape *sh, const RamdB
   View v = make_view(sh, b);
   if (sh->O == 4 && nrows >= 64) {
     RAMD_LAUNCH(k_out_layer_o4, dim3((nrows + 3) / 4), dim3(256), 0, st, v, row0, nrows);
-  } else if (sh->O <= 256 && !env_int("RECUR_AMD_OUT_GEMM", 0)) {
+  } else if (sh->O <= 256) {
     RAMD_LAUNCH(k_out_layer, dim3(nrows), dim3(1024),
                        (size_t)(sh->H + OUT_SEGS * 64) * sizeof(float), st, v, row0);
   } else if (nrows % WM == 0 && sh->O >= 1024 && ((sh->H + WK - 1) / WK == 9 || (sh->H + WK - 1) / WK == 17 || (sh->H + WK - 1) / WK == 33) &&
@@ -1248,7 +1239,7 @@ static void launch_output_layer(hipStream_t st, const RamdShape *sh, const RamdB
   } else { /* wide output layers (multi-head nets, O in the thousands): the MFMA GEMM */
     int tm = (nrows + BM - 1) / BM;
     int tn = (sh->O + BN - 1) / BN, nkt = (sh->H + BK - 1) / BK;
-    int ks = pick_ks(tm * tn, nkt, "RECUR_AMD_KS_OUT", b->slab_floats, (size_t)nrows * sh->O);
+    int ks = pick_ks(tm * tn, nkt, b->slab_floats, (size_t)nrows * sh->O);
     ProbOut p = {v, row0, nrows};
     launch_gemm<false, true, ProbOut>(st, p, b->slab, nrows, sh->O, nkt, ks, T_OTHER);
     int n4 = nrows * (sh->O / 4);
@@ -1268,7 +1259,7 @@ extern "C" int ramd_launch_forward_hidden(ramd_stream_t st_, const RamdShape *sh
   int tm = (nrows + BM - 1) / BM;
   {
     int tn = (sh->H + BN - 1) / BN, nkt = (sh->I + BK - 1) / BK;
-    int ks = pick_ks(tm * tn, nkt, "RECUR_AMD_KS_FWD", b->slab_floats, (size_t)nrows * sh->H);
+    int ks = pick_ks(tm * tn, nkt, b->slab_floats, (size_t)nrows * sh->H);
     const int wide_ns = (sh->I + WK - 1) / WK;
     /* (from 2048 rows: h_size = hidden_size + 4 makes 33 column tiles of 64, and with a few hundred
      * rows that 33rd tile is a second round of workgroups: 97 us against the generic kernel's 60

@@ -1,10 +1,12 @@
 /* ramd_internal.h -- private interface between the gnu11 C host code
- * (rnn_core.c, rnn_init.c, rnn_io.c) and the HIP kernels (kernels_*.hip).
+ * (engine.c, net_api.c, set_api.c, exchange.c, rnn_init.c, rnn_io.c) and the
+ * HIP kernels and their launchers (kernels_*.hip).
  *
- * The HIP side is a thin shim: every ramd_launch_* function enqueues one
- * kernel (or a fixed short sequence) on the given stream and returns.  All
- * policy -- what lives where, when to copy, the order of launches -- is in the
- * C code.
+ * The C side owns residency, coherence and call order: what lives where, when
+ * to copy, which ramd_launch_* follows which.  The launchers own the choice of
+ * kernel form for a shape: a ramd_launch_* function enqueues on the given
+ * stream whichever of its kernels (one, or a short sequence) suits the sizes,
+ * the flags and the RECUR_AMD_* switches, and returns.
  */
 #ifndef RAMD_INTERNAL_H
 #define RAMD_INTERNAL_H 1
@@ -79,7 +81,7 @@ typedef struct RamdBuffers {
   /* ring position shared by every training stream of the current call, or -1
    * when they differ (set by the host before each launch) */
   int uniform_idx;
-  /* presynaptic noise generated ahead of its forward pass (see noise_speculate in rnn_core.c):
+  /* presynaptic noise generated ahead of its forward pass (see noise_speculate in set_api.c):
    * [n][H] values and the generator states after them; noise_spec_use: the next forward adds
    * these and adopts the states instead of running the generators */
   float *noise_spec;
@@ -113,7 +115,7 @@ typedef struct RamdPendingDelta {
   int ho_ks;
   float *ho_delta_out;
   /* in: a workspace of the caller's own for the planes (own_slab_floats of it) instead of the shared split-K
-   * workspace -- for sums that are to outlive the call (the engine's kept deltas, rnn_core.c) */
+   * workspace -- for sums that are to outlive the call (the engine's kept deltas, set_api.c) */
   float *own_slab;
   size_t own_slab_floats;
   /* in: the update that follows, should the weight-delta GEMM be able to carry it out itself (k_delta_direct's
@@ -174,6 +176,12 @@ int ramd_launch_forward_hidden(ramd_stream_t st, const RamdShape *sh, const Ramd
  * whose hidden value is zero: the launcher rebuilds the images first, unless its top-layer form
  * takes the stale entries from the error planes itself (k_top_heads_combine) */
 #define RAMD_IMAGES_PENDING 0x08000000u
+/* flag of ramd_launch_calc_deltas: the fused single-net path (rnn_bptt_calculate): no ho_delta is formed, the top
+ * layer's weights are updated directly by the ramd_launch_fused_updates that follows */
+#define RAMD_NO_HO_DELTA 0x80000000u
+/* flag of ramd_launch_calc_deltas: that path unbatched: ih_delta gets the UNSCALED sum, the stream's ih_scale goes
+ * into the rate of the update, not into the sum (recur-nn.c:966-975) */
+#define RAMD_IH_SCALE_IN_RATE 0x20000000u
 /* a stream's range list as the multi-head loss leaves it: up to 64 + 1 (start, len) pairs, then one bit per head the
  * stream trained (an unsigned long long at this int offset; the stride keeps it 8-byte aligned) */
 #define RAMD_HEADBITS_AT 130

@@ -58,12 +58,12 @@ typedef struct RamdEngine {
   /* The delta sums of the last set call, kept as the un-summed planes the GEMM left (in a workspace of their own)
    * for the rnn_apply_learning that normally follows to sum on its way -- the separate calls then cost what the
    * one-call text step costs, a k_delta_finalize launch less.  Whoever else wants the delta arrays gets them summed
-   * first (deltas_materialize). */
+   * first (ramd_deltas_materialize). */
   u8 *active_host; /* what b.active holds (the last active mask sent), or NULL */
   int active_host_n;
   /* the top layer's backprop of these rows has been done with the loss (rnn_amd_set_opinion_sigmoid_mse /
    * _grouped_softmax): the next rnn_amd_set_calc_deltas over them skips it -- unless anything touched the weights, the
-   * hidden rows or the output error in between (top_done_clear); masked: only for the active flags in active_host */
+   * hidden rows or the output error in between (ramd_top_done_clear); masked: only for the active flags in active_host */
   int top_done, top_done_row0, top_done_n, top_done_masked;
   u8 *top_done_mask; /* masked: the streams whose backprop was done (the loss's `trained` flags) */
   RamdPendingDelta kept;
@@ -76,7 +76,7 @@ typedef struct RamdEngine {
   float *lr_pushed;
   int *idx_pushed;
   /* rnn_bptt_clear_deltas was called and nothing has needed the zeros yet: an accumulating
-   * calc_deltas that follows simply does not accumulate (deltas_materialize otherwise) */
+   * calc_deltas that follows simply does not accumulate (ramd_deltas_materialize otherwise) */
   int deltas_zero_pending;
   /* noise generated ahead (noise_speculate): valid while nothing else has moved the device's
    * generators since (rng_version) */
@@ -137,14 +137,86 @@ static inline RamdPriv *ramd_priv(const RecurNN *net) {
   return p;
 }
 
-/* rnn_core.c */
+/* the rows' top backprop is no longer the one that was done with the loss (RamdEngine.top_done) */
+static inline void ramd_top_done_clear(RamdEngine *e) { e->top_done = 0; }
+
+/* The host files that call the HIP runtime themselves (engine.c, net_api.c, set_api.c, exchange.c) define
+ * RAMD_HIP_HOST before they include this header. */
+#ifdef RAMD_HIP_HOST
+#define __HIP_PLATFORM_AMD__ 1
+#include <hip/hip_runtime_api.h>
+
+#define HIP_OK(x)                                                                  \
+  do {                                                                             \
+    hipError_t e_ = (x);                                                           \
+    if (e_ != hipSuccess) {                                                        \
+      fprintf(stderr, "librecur_amd: HIP error \"%s\" at %s:%d\n", hipGetErrorString(e_), \
+              __FILE__, __LINE__);                                                 \
+      abort();                                                                     \
+    }                                                                              \
+  } while (0)
+
+extern hipStream_t ramd_stream;        /* engine.c: the library's stream (rnn_amd_use_device) */
+extern hipStream_t ramd_side_stream;   /* engine.c: noise_speculate's stream (set_api.c), or NULL */
+extern hipEvent_t ramd_half_summed[2]; /* exchange.c: a half's sum over the ranks has arrived (ramd_delta_half_ready) */
+#endif
+
+/* engine.c: the device, the mailbox, the engines and the coherence between host and device */
+void ramd_require_device(const char *what);
 void *ramd_zalloc(size_t bytes);
+void *ramd_dev_alloc(size_t bytes);
+void ramd_dev_free(void *p);
+void ramd_h2d(void *d, const void *h, size_t bytes);
+void ramd_d2h(void *h, const void *d, size_t bytes);
+void ramd_dsync(void);
+void ramd_mail_in(void *dev, const void *host, size_t bytes);
+void ramd_mail_in_flush(void);
+void ramd_mail_out(void *host, const void *dev, size_t bytes);
+void ramd_mail_out_flush(void);
+void ramd_upload_rows_q(void *dev, const void *host, size_t host_pitch, size_t width, size_t rows, int flush);
+void ramd_upload_rows(void *dev, const void *host, size_t host_pitch, size_t width, size_t rows);
+void ramd_upload(void *dev, const void *host, size_t bytes);
+void ramd_upload_q(void *dev, const void *host, size_t bytes);
+RamdEngine *ramd_engine_new(RecurNN *owner);
+void ramd_engine_delete(RamdEngine *e);
+void ramd_engine_attach(RamdEngine *e, RecurNN *net);
 RamdEngine *ramd_engine_of(RecurNN *net);
+void ramd_engine_ensure_device(RamdEngine *e);
+int ramd_state_row(const RamdEngine *e, const RamdPriv *p);
+void ramd_rng_written_from_host(RamdEngine *e);
+void ramd_stream_copy(RamdEngine *e, RecurNN *net, int to_device);
+void ramd_stream_need_host(RamdEngine *e, RecurNN *net);
+void ramd_stream_need_dev(RamdEngine *e, RecurNN *net);
+void ramd_err_flush(RamdEngine *e);
+void ramd_err_after_calc(RamdEngine *e, int row0, int nrows);
+void ramd_deltas_materialize(RamdEngine *e);
+void ramd_engine_need_host(RamdEngine *e, int what);
+void ramd_engine_need_dev(RamdEngine *e, int what);
+void ramd_engine_dev_wrote(RamdEngine *e, int what);
 void ramd_need_host(RecurNN *net, int what);
 void ramd_host_wrote(RecurNN *net, int what);
-void ramd_require_device(const char *what);
 void ramd_rng_to_host(RecurNN *net);
 void ramd_rng_from_host(RecurNN *net);
+
+/* net_api.c: what the batched calls share with the per-net calls */
+void ramd_host_advance(RecurNN *net);
+void ramd_push_learn_rates(RamdEngine *e, int row0, int nrows);
+void ramd_push_indices(RamdEngine *e, int row0, int nrows);
+void ramd_pull_scalars(RamdEngine *e, int row0, int nrows);
+void ramd_set_uniform_idx(RamdEngine *e, int row0, int nrows);
+const int *ramd_push_ranges(RamdEngine *e, RecurErrorRange *ranges);
+void ramd_log_bptt(RamdEngine *e, RecurNN *net, float mef_before);
+void ramd_check_method_arrays(RamdEngine *e, int method);
+int ramd_update_rule(const RecurNNBPTT *bptt, int learning_style, float momentum, float *mw, float *rate, float *ho_rate);
+void ramd_apply_learning(RecurNN *net, int learning_method, float momentum, const RamdPendingDelta *pend);
+void ramd_fused_net_update(RamdEngine *e, RecurNN *net, int row, unsigned batch_size);
+
+/* set_api.c */
+void ramd_set_need_training(const RnnAmdSet *set, const char *what);
+
+/* exchange.c: the all-reduce overlapped with the weight-delta GEMM, for set_step (set_api.c) */
+void ramd_delta_half_ready(void *ctx, int half, size_t first_float, size_t n_floats);
+extern int ramd_halves_seen; /* bit h: half h's sum is on its way */
 
 /* dist.c */
 int ramd_dist_active(void);

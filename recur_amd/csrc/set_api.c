@@ -1,0 +1,1128 @@
+/* set_api.c -- the batched API: an RnnAmdSet drives all the streams of a training set (or a set of forward-only
+ * clones) through one launch sequence per call (include/recur_amd.h; gnu11 C).  Forward passes, the losses, the delta
+ * call, the presynaptic noise generated ahead, the multi-head and text calls, and the generations as ONE call
+ * (set_step).  The exchange between ranks that a step may end with is exchange.c's.
+ */
+#define RAMD_HIP_HOST 1
+#include "rnn_host.h"
+
+RnnAmdSet *rnn_amd_set_open(RecurNN **nets, int n_nets) {
+  if (!nets || n_nets < 1) {
+    return NULL;
+  }
+  RamdEngine *e = ramd_engine_of(nets[0]);
+  /* either training streams in rnn_new_training_set order, or forward-only clones
+   * (rnn_clone without bptt, e.g. gstrnnca.c's constructors) in creation order */
+  int fwd_only = ramd_priv(nets[0])->stream < 0;
+  int row0 = fwd_only ? ramd_priv(nets[0])->fwd : ramd_priv(nets[0])->stream;
+  for (int j = 0; j < n_nets; j++) {
+    RamdPriv *p = ramd_priv(nets[j]);
+    int id = fwd_only ? p->fwd : p->stream;
+    if (ramd_engine_of(nets[j]) != e || id != row0 + j || (p->stream < 0) != fwd_only) {
+      fprintf(stderr, "librecur_amd: rnn_amd_set_open: nets must be one training set in "
+                      "rnn_new_training_set order (or forward-only clones in creation order)\n");
+      return NULL;
+    }
+  }
+  ramd_engine_ensure_device(e);
+  RnnAmdSet *set = ramd_zalloc(sizeof(RnnAmdSet));
+  set->eng = e;
+  /* the set keeps its own copy of the pointer array: the caller's may be a temporary */
+  set->nets = ramd_zalloc(n_nets * sizeof(RecurNN *));
+  memcpy(set->nets, nets, n_nets * sizeof(RecurNN *));
+  set->n = n_nets;
+  set->row0 = row0;
+  set->fwd_only = fwd_only;
+  set->global_first = 0;
+  set->global_count = n_nets;
+  set->counts_shard = 0;
+  /* A set of ALL the engine's training streams opened inside a group is this rank's shard of the distributed
+   * training set: rank r holds global streams [r n, (r + 1) n).  A set of some of them -- the host layers' one-net
+   * passes, a validation or side net that one rank alone touches -- stays local: its host draws must not become
+   * collectives that the other ranks never enter. */
+  if (ramd_dist_active() && !fwd_only && n_nets == e->n_streams) {
+    set->global_first = rnn_amd_dist_rank() * n_nets;
+    set->global_count = rnn_amd_dist_world() * n_nets;
+    set->counts_shard = 1;
+    e->sharded_sets++;
+    e->sharded = 1;
+  }
+  return set;
+}
+
+/* the engine stays a shard while ANY open set shards it (two sets may be open on one engine and close in any order:
+ * ADVICE.md round 4) or it was sharded explicitly (rnn_amd_set_shard, the shard constructor: the nets remain a shard
+ * whatever set drives them) */
+static void set_unshard(RnnAmdSet *set) {
+  RamdEngine *e = set->eng;
+  if (set->counts_shard && e->sharded_sets > 0) {
+    e->sharded_sets--;
+  }
+  set->counts_shard = 0;
+  e->sharded = e->sharded_sticky || e->sharded_sets > 0;
+}
+
+void rnn_amd_set_close(RnnAmdSet *set) {
+  if (!set) {
+    return;
+  }
+  ramd_need_host(set->nets[0], RNN_AMD_EVERYTHING);
+  set_unshard(set);
+  free(set->nets);
+  free(set);
+}
+
+/* the same without fetching anything: the streams' state stays current on the device only */
+void rnn_amd_set_drop(RnnAmdSet *set) {
+  if (!set) {
+    return;
+  }
+  set_unshard(set);
+  free(set->nets);
+  free(set);
+}
+
+int rnn_amd_set_size(const RnnAmdSet *set) { return set->n; }
+
+void rnn_amd_set_shard(RnnAmdSet *set, int global_first, int global_count) {
+  if (global_first < 0 || global_first + set->n > global_count) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_shard(%d, %d) for a set of %d streams\n", global_first,
+            global_count, set->n);
+    abort();
+  }
+  set->global_first = global_first;
+  set->global_count = global_count;
+  if (global_count != set->n) {
+    set->eng->sharded_sticky = 1;
+  } else if (global_first == 0) {
+    set->eng->sharded_sticky = 0; /* the whole set again: host draws come from the nets' own generators as before */
+  }
+  set->eng->sharded = set->eng->sharded_sticky || set->eng->sharded_sets > 0;
+}
+
+void rnn_amd_set_dist_all_reduce_deltas(RnnAmdSet *set) {
+  RamdEngine *e = set->eng;
+  if (!ramd_dist_active()) {
+    return;
+  }
+  ramd_engine_need_dev(e, RNN_AMD_DELTAS);
+  /* ih_delta||ho_delta are one allocation (library-owned or the caller's external buffer) */
+  const int tev = ramd_timing_begin(ramd_stream, RAMD_T_XCHG);
+  rnn_amd_dist_all_reduce(e->b.ih_delta, e->ih_size + e->ho_size);
+  ramd_timing_end(ramd_stream, tev);
+  ramd_engine_dev_wrote(e, RNN_AMD_DELTAS);
+}
+
+/* first state row of the set (forward-only rows sit after the Scap training rows) */
+static int set_state_row0(const RnnAmdSet *set) {
+  return set->fwd_only ? set->eng->sh.Scap + set->row0 : set->row0;
+}
+
+void ramd_set_need_training(const RnnAmdSet *set, const char *what) {
+  if (set->fwd_only) {
+    fprintf(stderr, "librecur_amd: %s needs a training set (nets with bptt)\n", what);
+    abort();
+  }
+}
+
+static void set_streams_to_dev(RnnAmdSet *set) {
+  RamdEngine *e = set->eng;
+  int any = 0;
+  for (int j = 0; j < set->n; j++) {
+    RamdPriv *p = ramd_priv(set->nets[j]);
+    if (!p->dev_valid) {
+      ramd_stream_copy(e, set->nets[j], 1);
+      p->dev_valid = 1;
+      any = 1;
+    }
+  }
+  if (any) {
+    ramd_dsync();
+    ramd_top_done_clear(e);
+  }
+  if (!set->fwd_only) {
+    ramd_push_indices(e, set->row0, set->n);
+    ramd_mail_in_flush();
+  }
+}
+
+static void set_streams_dev_wrote(RnnAmdSet *set) {
+  for (int j = 0; j < set->n; j++) {
+    RamdPriv *p = ramd_priv(set->nets[j]);
+    p->dev_valid = 1;
+    p->host_valid = 0;
+  }
+}
+
+void rnn_amd_set_advance(RnnAmdSet *set) {
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_advance");
+  (void)e;
+  for (int j = 0; j < set->n; j++) {
+    ramd_host_advance(set->nets[j]);
+  }
+  /* the device's copy of the indices follows with the next call's uploads (ramd_push_indices): no
+   * launch of its own for rnn_bptt_advance's three integer operations per stream */
+}
+
+/* The presynaptic noise of the NEXT forward pass of this set, generated now on a second stream.
+ * A stream's generator is a sequential recurrence -- 3 x (h_size - 1) dependent steps per pass,
+ * one lane per stream, 0.2 ms for 1028 values whatever the number of streams -- so the only
+ * way to take it off the generation's critical path is to run it beside something else: it is
+ * launched as soon as the last draw before the next pass has been made (the multi-head loss's
+ * leak decisions, or the pass itself in the text step) and runs beside the whole backward
+ * pass.  It reads the generators and leaves them alone; the forward pass adds the values and
+ * adopts the generator states that go with them (k_noise_apply) provided nothing has moved the
+ * generators in between (rng_version: uploads of a generator, other passes, other losses),
+ * otherwise it generates as before and the speculated values are dropped. */
+/* loss_classes > 0: the early form for the multi-head step, called between the forward pass and the loss.  When that
+ * pass adopted the speculated states they still sit in b.rng_spec, which the loss does not touch: the generator is
+ * started from there, `loss_classes` heads' worth of leak decisions on (one draw per head other than the stream's
+ * own, whatever the outcome), beside the output layer and the loss instead of after them -- at 1024 / 256 / 73 x 50
+ * the generator (0.31 ms beside the matrix kernels) had become the generation's critical path. */
+static void noise_speculate_from(RnnAmdSet *set, int loss_classes) {
+  RamdEngine *e = set->eng;
+  const float noise = set->nets[0]->presynaptic_noise;
+  static int enabled = -1, two_ahead = -1;
+  if (enabled < 0) {
+    const char *env = getenv("RECUR_AMD_NOISE_AHEAD");
+    enabled = !(env && atoi(env) == 0);
+    two_ahead = !(env && atoi(env) == 1); /* (1: one pass ahead only) */
+  }
+  if (noise == 0.0f || e->sh.bI || set->fwd_only || !enabled) {
+    return;
+  }
+  if (!ramd_side_stream) {
+    HIP_OK(hipStreamCreateWithFlags(&ramd_side_stream, hipStreamNonBlocking));
+    ramd_note_side_stream();
+  }
+  if (!e->spec_go) {
+    HIP_OK(hipEventCreateWithFlags((hipEvent_t *)&e->spec_go, hipEventDisableTiming));
+    HIP_OK(hipEventCreateWithFlags((hipEvent_t *)&e->sp[0].done, hipEventDisableTiming));
+    HIP_OK(hipEventCreateWithFlags((hipEvent_t *)&e->sp[1].done, hipEventDisableTiming));
+  }
+  for (int k = 0; k < 2; k++) {
+    if (!e->sp[k].noise) {
+      e->sp[k].noise = ramd_dev_alloc((size_t)e->sh.Scap * e->sh.H * sizeof(float));
+      e->sp[k].states = ramd_dev_alloc((size_t)e->sh.Scap * sizeof(rand_ctx));
+    }
+  }
+  const int r0 = set->row0;
+  int launched = 0;
+  /* the next pass (buffer sp_head), unless an earlier call has started it already */
+  int k = e->sp_head;
+  if (!e->sp[k].pending) {
+    const int early = loss_classes > 0 && e->sp_adopted >= 0;
+    if (loss_classes > 0 && !early) {
+      return; /* (between the pass and the loss only the adopted states are safe to start from) */
+    }
+    HIP_OK(hipEventRecord((hipEvent_t)e->spec_go, ramd_stream)); /* the draws made so far, the buffers' last readers */
+    HIP_OK(hipStreamWaitEvent(ramd_side_stream, (hipEvent_t)e->spec_go, 0));
+    ramd_launch_noise_speculate(ramd_side_stream, &e->sh, &e->b, r0, set->n, noise, e->sp[k].noise, e->sp[k].states,
+                                early ? e->sp[e->sp_adopted].states : NULL, early ? e->d_mclass + r0 : NULL,
+                                early ? loss_classes : 0, 0);
+    HIP_OK(hipEventRecord((hipEvent_t)e->sp[k].done, ramd_side_stream));
+    e->sp[k].pending = 1;
+    e->sp[k].version = e->rng_version + (early ? 1 : 0); /* (the loss that follows counts as one move) */
+    e->sp[k].row0 = r0;
+    e->sp[k].n = set->n;
+    e->sp[k].dev = noise;
+    e->sp[k].assumed_classes = 0;
+    launched = 1;
+  }
+  /* ... and, in the multi-head step, the pass after it: from the states the first one leaves, past the draws of a
+   * loss whose classes nobody has yet -- one per head but the stream's own, so on the assumption that every stream's own
+   * class is one of the heads (multi_loss checks it when it comes and drops what was built on it otherwise).  The
+   * generator then runs a whole generation ahead and is off the critical path even where it is as long as the
+   * generation (32 streams per GPU). */
+  const int k2 = k ^ 1;
+  if (two_ahead && loss_classes > 0 && e->sp[k].pending && !e->sp[k2].pending && e->sp[k].row0 == r0 &&
+      e->sp[k].n == set->n && e->sp[k].dev == noise) {
+    if (!launched) {
+      HIP_OK(hipEventRecord((hipEvent_t)e->spec_go, ramd_stream)); /* buffer k2's last reader: the pass just made */
+      HIP_OK(hipStreamWaitEvent(ramd_side_stream, (hipEvent_t)e->spec_go, 0));
+    }
+    ramd_launch_noise_speculate(ramd_side_stream, &e->sh, &e->b, r0, set->n, noise, e->sp[k2].noise, e->sp[k2].states,
+                                e->sp[k].states, NULL, 0, loss_classes - 1);
+    HIP_OK(hipEventRecord((hipEvent_t)e->sp[k2].done, ramd_side_stream));
+    e->sp[k2].pending = 1;
+    e->sp[k2].version = e->sp[k].version + 2; /* one more pass and one more loss on */
+    e->sp[k2].row0 = r0;
+    e->sp[k2].n = set->n;
+    e->sp[k2].dev = noise;
+    e->sp[k2].assumed_classes = loss_classes;
+  }
+}
+static void noise_speculate(RnnAmdSet *set) { noise_speculate_from(set, 0); }
+
+/* hidden_only: stop after the hidden layer's GEMM and leave its K slabs for
+ * ramd_launch_text_top; returns their number (0 otherwise) */
+static int set_forward(RnnAmdSet *set, int mode, const float *d_dense, int ld, int text_i,
+                       float *outputs, int advance, int hidden_only) {
+  RamdEngine *e = set->eng;
+  ramd_top_done_clear(e);
+  ramd_engine_need_dev(e, RNN_AMD_WEIGHTS);
+  set_streams_to_dev(set);
+  if (advance) {
+    ramd_set_need_training(set, "advancing");
+    for (int j = 0; j < set->n; j++) {
+      ramd_host_advance(set->nets[j]); /* the device steps its copy inside the assemble kernel */
+      e->idx_pushed[set->row0 + j] = set->nets[j]->bptt->index;
+    }
+  }
+  const int r0 = set_state_row0(set);
+  if (set->fwd_only) {
+    e->b.uniform_idx = -1;
+  } else {
+    ramd_set_uniform_idx(e, set->row0, set->n);
+  }
+  if (mode == RAMD_IN_DENSE) {
+    e->b.dense_inputs = 1;
+  } else if (mode == RAMD_IN_ONE_HOT || mode == RAMD_IN_TEXT) {
+    e->b.dense_inputs = 0;
+  }
+  float noise = set->nets[0]->presynaptic_noise;
+  if (noise != 0.0f) {
+    /* values generated ahead for exactly this pass, and nothing has touched the generators since? */
+    const int k = e->sp_head;
+    e->b.noise_spec_use = e->sp[k].pending && e->sp[k].version == e->rng_version && e->sp[k].row0 == r0 &&
+                          e->sp[k].n == set->n && e->sp[k].dev == noise && !e->sh.bI;
+    e->sp_adopted = -1;
+    if (e->b.noise_spec_use) {
+      HIP_OK(hipStreamWaitEvent(ramd_stream, (hipEvent_t)e->sp[k].done, 0));
+      e->b.noise_spec = e->sp[k].noise;
+      e->b.rng_spec = e->sp[k].states;
+      e->sp[k].pending = 0;
+      e->sp_head = k ^ 1; /* (the other buffer: the pass after this one, if it has been started) */
+      e->sp_adopted = k;
+    } else {
+      e->sp[0].pending = e->sp[1].pending = 0; /* nothing that was started fits: the second one hangs on the first */
+    }
+    e->rng_version++; /* this pass moves the generators, either way */
+  } else {
+    e->sp_adopted = -1;
+  }
+  for (int j = 1; j < set->n; j++) {
+    if (set->nets[j]->presynaptic_noise != noise) {
+      fprintf(stderr, "librecur_amd: the nets of a set must share presynaptic_noise\n");
+      abort();
+    }
+  }
+  if (e->sh.bI) {
+    /* the caller's inputs feed the bottom layer, whose rectified outputs become the real
+     * inputs of the current slot: the ring has to step before it runs */
+    if (advance) {
+      ramd_launch_advance(ramd_stream, &e->sh, &e->b, set->row0, set->n);
+    }
+    ramd_launch_bottom_forward(ramd_stream, &e->sh, &e->b, r0, set->n, mode, d_dense, ld, text_i,
+                               set->global_first, set->global_count, noise);
+    ramd_launch_assemble(ramd_stream, &e->sh, &e->b, r0, set->n, RAMD_IN_KEEP, NULL, 0, 0,
+                         set->global_first, set->global_count, 0);
+  } else {
+    if (hidden_only && (advance || mode == RAMD_IN_DENSE) && noise == 0.0f && !set->fwd_only) {
+      /* the text step: building the input rows and the hidden layer's GEMM in one launch
+       * (the ring index the kernel stores is the host's, which has just stepped); dense inputs on their way to
+       * ramd_launch_dense_top likewise */
+      int fused = ramd_launch_forward_fused(ramd_stream, &e->sh, &e->b, r0, set->n, mode, text_i,
+                                            set->global_first, set->global_count, 1, d_dense, ld);
+      if (fused) {
+        set_streams_dev_wrote(set);
+        return fused;
+      }
+    } else if (!hidden_only && (advance || mode == RAMD_IN_DENSE) && !set->fwd_only && (noise == 0.0f || e->b.noise_spec_use)) {
+      /* the same launch for the one-hot and text passes that go on to a generic output layer (the multi-head step),
+       * and for dense inputs (gstclassify's features, rnnca's neighbourhoods; their callers advance on their own, and
+       * the index the kernel stores is the one that is there); presynaptic noise only as the values generated
+       * ahead, which the finishing kernel adds */
+      int fused = ramd_launch_forward_fused(ramd_stream, &e->sh, &e->b, r0, set->n, mode, text_i,
+                                            set->global_first, set->global_count, 0, d_dense, ld);
+      if (fused) {
+        ramd_launch_forward_finish(ramd_stream, &e->sh, &e->b, r0, set->n, fused, 1);
+        if (set->early_spec_classes > 0 && e->sp_adopted >= 0) {
+          /* the multi-head step: the next pass's noise from here on, beside the output layer and the loss */
+          noise_speculate_from(set, set->early_spec_classes);
+          set->early_spec_classes = -1; /* done */
+        }
+        ramd_launch_forward_finish(ramd_stream, &e->sh, &e->b, r0, set->n, fused, 2);
+        e->b.noise_spec_use = 0;
+        set_streams_dev_wrote(set);
+        if (outputs) {
+          ramd_d2h(outputs, e->b.out + (size_t)r0 * e->sh.O, (size_t)set->n * e->sh.O * sizeof(float));
+          ramd_dsync();
+        }
+        return 0;
+      }
+    }
+    ramd_launch_assemble(ramd_stream, &e->sh, &e->b, r0, set->n, mode, d_dense, ld, text_i,
+                         set->global_first, set->global_count, advance);
+  }
+  int fwd_ks = 0;
+  if (hidden_only) {
+    fwd_ks = ramd_launch_forward_hidden(ramd_stream, &e->sh, &e->b, r0, set->n, noise, 1);
+  } else {
+    ramd_launch_forward(ramd_stream, &e->sh, &e->b, r0, set->n, noise);
+  }
+  e->b.noise_spec_use = 0;
+  set_streams_dev_wrote(set);
+  if (outputs) {
+    ramd_d2h(outputs, e->b.out + (size_t)r0 * e->sh.O, (size_t)set->n * e->sh.O * sizeof(float));
+    ramd_dsync();
+  }
+  return fwd_ks;
+}
+
+void rnn_amd_set_opinion(RnnAmdSet *set, const float *inputs, int ld_inputs, float *outputs) {
+  RamdEngine *e = set->eng;
+  if (inputs) {
+    int w = e->sh.bI ? e->sh.b_in : e->sh.input_size;
+    /* (queued: leaves with the ring indices in set_forward's flush) */
+    ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), w * sizeof(float), set->n, set->fwd_only);
+    set_forward(set, RAMD_IN_DENSE, e->d_dense, w, 0, outputs, 0, 0);
+    if (e->sh.bI) {
+      /* the layer's one input buffer, shared by every clone, as the per-net loop would leave it:
+       * the last stream's inputs (recur-nn.c:88-94) */
+      RecurExtraLayer *bl = set->nets[0]->bottom_layer;
+      bl->inputs[0] = 1.0f;
+      memcpy(bl->inputs + 1, inputs + (size_t)(set->n - 1) * ld_inputs, sizeof(float) * bl->input_size);
+    }
+  } else {
+    set_forward(set, RAMD_IN_KEEP, NULL, 0, 0, outputs, 0, 0);
+  }
+}
+
+void rnn_amd_set_one_hot_opinion(RnnAmdSet *set, const int *hot, float *outputs) {
+  RamdEngine *e = set->eng;
+  ramd_upload(e->b.hot + set_state_row0(set), hot, set->n * sizeof(int));
+  set_forward(set, RAMD_IN_ONE_HOT, NULL, 0, 0, outputs, 0, 0);
+}
+
+void rnn_amd_set_put_o_error(RnnAmdSet *set, const float *o_error, int ld) {
+  RamdEngine *e = set->eng;
+  ramd_top_done_clear(e);
+  ramd_set_need_training(set, "rnn_amd_set_put_o_error");
+  set_streams_to_dev(set);
+  ramd_upload_rows(e->b.o_error + (size_t)set->row0 * e->sh.O, o_error, ld * sizeof(float), e->sh.O * sizeof(float),
+              set->n);
+  set_streams_dev_wrote(set);
+}
+
+void rnn_amd_set_softmax_error(RnnAmdSet *set, const int *target) {
+  RamdEngine *e = set->eng;
+  ramd_top_done_clear(e);
+  ramd_set_need_training(set, "rnn_amd_set_softmax_error");
+  set_streams_to_dev(set);
+  if (target) {
+    ramd_upload(e->b.target + set->row0, target, set->n * sizeof(int));
+  }
+  ramd_launch_softmax_error(ramd_stream, &e->sh, &e->b, set->row0, set->n);
+  set_streams_dev_wrote(set);
+}
+
+/* the set calls' active mask on the device (b.active, written by nothing else): uploaded unless these very flags are
+ * there already -- the class-group loss sends the flags it returns along with its own uploads, because its caller passes
+ * them straight on to the delta call (one launch less per generation).  queued: leaves with the caller's next flush */
+static void active_mask_to_dev(RamdEngine *e, const u8 *active, int n, int queued) {
+  if (e->active_host && e->active_host_n == n && memcmp(e->active_host, active, (size_t)n) == 0) {
+    return;
+  }
+  if (!e->active_host) {
+    e->active_host = ramd_zalloc((size_t)e->sh.Scap + 4);
+  }
+  memcpy(e->active_host, active, (size_t)n);
+  e->active_host_n = n;
+  if (queued) {
+    ramd_upload_q(e->b.active, active, (size_t)n);
+  } else {
+    ramd_upload(e->b.active, active, (size_t)n); /* (through the mailbox when the set is a whole number of words) */
+  }
+}
+
+/* may this set call leave its delta sums as planes (RamdEngine.kept)?  Not with a bottom layer (its deltas follow in
+ * a launch of their own that accumulates), an exchange between ranks or a caller's delta buffer (both want the sums
+ * as such, at once); the workspace is the engine's own, made on first use: eight planes and the rest rows' planes */
+static int kept_deltas_ok(RamdEngine *e) {
+  static int on = -1;
+  if (on < 0) {
+    const char *v = getenv("RECUR_AMD_KEEP_DELTAS");
+    on = !(v && *v == '0');
+  }
+  if (!on || e->sh.bI || e->xchg_world || e->delta_external || rnn_amd_dist_world() > 1) {
+    return 0;
+  }
+  if (!e->d_kept_slab) {
+    size_t fl = 8 * e->ih_size + (size_t)64 * 128 * e->sh.H;
+    if (fl * sizeof(float) > ((size_t)2 << 30)) {
+      return 0;
+    }
+    e->d_kept_slab = ramd_dev_alloc(fl * sizeof(float));
+    e->kept_floats = fl;
+  }
+  return 1;
+}
+
+/* dev_ranges: one range list per stream already on the device (range_stride ints apart),
+ * instead of the shared host list `ranges` */
+static void set_calc_deltas(RnnAmdSet *set, int accumulate, RecurErrorRange *ranges,
+                            const u8 *active, unsigned extra_flags, const int *dev_ranges,
+                            int range_stride, RamdPendingDelta *defer) {
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_calc_deltas");
+  if (e->deltas_zero_pending) { /* the sum into zeros is the sum */
+    accumulate = 0;
+    e->deltas_zero_pending = 0;
+  }
+  ramd_engine_need_dev(e, RNN_AMD_WEIGHTS | (accumulate ? RNN_AMD_DELTAS : 0));
+  e->kept_live = 0; /* (summed just now if this call accumulates, otherwise overwritten) */
+  if (!defer && !accumulate && kept_deltas_ok(e)) {
+    /* leave the sums as planes for the rnn_apply_learning that normally follows (see RamdEngine.kept) */
+    memset(&e->kept, 0, sizeof(e->kept));
+    e->kept.own_slab = e->d_kept_slab;
+    e->kept.own_slab_floats = e->kept_floats;
+    defer = &e->kept;
+  }
+  set_streams_to_dev(set);
+  ramd_push_learn_rates(e, set->row0, set->n);
+  const int *d_ranges = dev_ranges ? dev_ranges : ramd_push_ranges(e, ranges);
+  const unsigned char *d_active = NULL;
+  if (active) {
+    active_mask_to_dev(e, active, set->n, 0);
+    d_active = e->b.active;
+  }
+  if (e->err_pending && d_ranges && e->err_row0 == set->row0 && e->err_nrows == set->n) {
+    /* the ranged top backprops keep stale entries of these rows' error images, which have not been rebuilt yet: the
+     * launcher sees to it (its per-head form reads them from the planes: no k_err_writeback launch) */
+    extra_flags |= RAMD_IMAGES_PENDING;
+    e->err_pending = 0;
+  } else if (e->err_pending && (d_ranges || e->err_row0 != set->row0 || e->err_nrows != set->n)) {
+    ramd_err_flush(e);
+  }
+  if (e->top_done && e->top_done_row0 == set->row0 && e->top_done_n == set->n && !d_ranges &&
+      (e->top_done_masked ? (active && e->top_done_mask && memcmp(e->top_done_mask, active, (size_t)set->n) == 0)
+                          : !active)) {
+    extra_flags |= RAMD_TOP_DONE; /* with the loss (rnn_amd_set_opinion_sigmoid_mse / _grouped_softmax) */
+  }
+  ramd_top_done_clear(e);
+  ramd_set_uniform_idx(e, set->row0, set->n);
+  ramd_launch_calc_deltas(ramd_stream, &e->sh, &e->b, set->row0, set->n, accumulate, d_ranges,
+                          dev_ranges ? range_stride : 0, d_active,
+                          set->nets[0]->flags | extra_flags, defer);
+  if (e->sh.bI) {
+    if (set->global_count != set->n || e->delta_external) {
+      fprintf(stderr, "librecur_amd: a bottom layer cannot be trained on a sharded set: its "
+                      "error accumulator runs through the streams in order "
+                      "(recur-nn.c:377-382)\n");
+      abort();
+    }
+    ramd_launch_bottom_deltas(ramd_stream, &e->sh, &e->b, set->row0, set->n, accumulate, d_active);
+  }
+  e->err_pending = 1;
+  e->err_row0 = set->row0;
+  e->err_nrows = set->n;
+  if (defer == &e->kept) {
+    e->kept_live = e->kept.slab || e->kept.ho_slab;
+  }
+  ramd_engine_dev_wrote(e, RNN_AMD_DELTAS);
+  set_streams_dev_wrote(set);
+  for (int j = 0; j < set->n; j++) {
+    if (!active || active[j]) {
+      set->nets[j]->generation++; /* recur-nn.c:765 */
+    }
+  }
+  if (set->nets[0]->log) {
+    ramd_log_bptt(e, set->nets[0], set->nets[0]->bptt->min_error_factor);
+    ramd_pull_scalars(e, set->row0, 1);
+    rnn_log_int(set->nets[0], "generation", set->nets[0]->generation);
+  }
+}
+
+void rnn_amd_set_calc_deltas(RnnAmdSet *set, int accumulate, RecurErrorRange *ranges,
+                             const u8 *active) {
+  set_calc_deltas(set, accumulate, ranges, active, 0, NULL, 0, NULL);
+}
+
+/* gstclassify's loss for the whole set (gstclassify.c:2070-2119), see recur_amd.h */
+void rnn_amd_set_grouped_softmax_error(RnnAmdSet *set, int n_groups, const int *group_offset,
+                                       const int *group_size, const int *targets,
+                                       const float *error_weight, u8 *trained) {
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_grouped_softmax_error");
+  ramd_top_done_clear(e);
+  const RamdShape *s = &e->sh;
+  int largest = 1;
+  for (int i = 0; i < n_groups; i++) {
+    if (group_offset[i] < 0 || group_size[i] < 1 || group_offset[i] + group_size[i] > s->output_size) {
+      fprintf(stderr, "librecur_amd: class group %d (%d + %d) outside the %d outputs\n", i,
+              group_offset[i], group_size[i], s->output_size);
+      abort();
+    }
+    largest = RAMD_MAX(largest, group_size[i]);
+  }
+  set_streams_to_dev(set);
+  /* one staging block: offsets, sizes, targets, then the weights */
+  size_t ints = (size_t)2 * n_groups + (size_t)set->n * n_groups;
+  size_t bytes = ints * sizeof(int) + (error_weight ? (size_t)s->output_size * sizeof(float) : 0);
+  if (bytes > e->d_group_bytes) {
+    ramd_dsync();
+    ramd_dev_free(e->d_group);
+    e->d_group = ramd_dev_alloc(bytes);
+    e->d_group_bytes = bytes;
+  }
+  int *d = (int *)e->d_group;
+  ramd_upload_q(d, group_offset, n_groups * sizeof(int));
+  ramd_upload_q(d + n_groups, group_size, n_groups * sizeof(int));
+  ramd_upload_q(d + 2 * n_groups, targets, (size_t)set->n * n_groups * sizeof(int));
+  float *dw = NULL;
+  if (error_weight) {
+    dw = (float *)(d + ints);
+    ramd_upload_q(dw, error_weight, (size_t)s->output_size * sizeof(float));
+  }
+  if (trained) { /* a stream is trained if any of its groups has a usable target */
+    for (int j = 0; j < set->n; j++) {
+      trained[j] = 0;
+      for (int i = 0; i < n_groups; i++) {
+        int t = targets[(size_t)j * n_groups + i];
+        trained[j] |= (t >= 0 && t < group_size[i]);
+      }
+    }
+    /* the caller hands these flags to rnn_amd_set_calc_deltas next (gstclassify.c:2120-2127): they travel with this
+     * call's uploads, and that call finds them in place (active_mask_to_dev) */
+    if (set->n % 4 == 0 && !set->fwd_only) {
+      active_mask_to_dev(e, trained, set->n, 1);
+    }
+  }
+  ramd_mail_in_flush();
+  ramd_launch_grouped_softmax_error(ramd_stream, s, &e->b, set->row0, set->n, n_groups, largest, d,
+                                    d + n_groups, d + 2 * n_groups, dw);
+  set_streams_dev_wrote(set);
+}
+
+/* The multi-head text model for the whole set, per generation: what
+ * charmodel-multi-predict.c:244-256 does per net (rnn_bptt_advance, multi_softmax_error
+ * with its one_hot_opinion, rnn_bptt_calc_deltas with the error ranges), stream j
+ * accumulating on top of stream j - 1.  The loss half leaves o_error and one range list
+ * per stream on the device; the deltas half consumes them.  In between the caller may
+ * apply the previous batch's deltas, as text_train does (244-252). */
+static const int MULTI_RANGE_STRIDE = RAMD_MULTI_RANGE_STRIDE; /* 2 x (64 + 1) ints and the head bits */
+
+static int multi_heads(RamdEngine *e, int alphabet_len) {
+  const RamdShape *s = &e->sh;
+  int n_classes = alphabet_len > 0 ? s->output_size / alphabet_len : 0;
+  if (alphabet_len < 1 || n_classes < 1 || n_classes > 64) {
+    fprintf(stderr, "librecur_amd: %d outputs as heads of %d: 1 to 64 heads are supported\n",
+            s->output_size, alphabet_len);
+    abort();
+  }
+  if (!e->d_mranges) {
+    e->d_mranges = ramd_dev_alloc((size_t)s->Scap * MULTI_RANGE_STRIDE * sizeof(int));
+    e->d_mclass = ramd_dev_alloc((size_t)s->Scap * sizeof(int));
+  }
+  /* the sparse top backprop's partial products, one row of h_size per (stream, head): 53 MB at 256 streams of 50
+   * heads and 1024 hidden units; sets too large for that keep the one-GEMM form (k_top_backprop_heads) */
+  size_t part = (size_t)s->Scap * n_classes * s->H;
+  if (alphabet_len >= 24 && alphabet_len <= 128 && part > e->b.mheads_part_floats && part * sizeof(float) <= ((size_t)2 << 30)) {
+    ramd_dev_free(e->b.mheads_part);
+    e->b.mheads_part = ramd_dev_alloc(part * sizeof(float));
+    e->b.mheads_part_floats = part;
+  }
+  return n_classes;
+}
+
+/* the loss after the opinion: b.target holds each stream's next symbol */
+static void mclass_note(RamdEngine *e, const int *target_class, int n, int n_classes) {
+  int ok = 1;
+  for (int j = 0; j < n; j++) {
+    ok &= target_class[j] >= 0 && target_class[j] < n_classes;
+  }
+  e->mclass_in_range = ok;
+}
+
+static void multi_loss(RnnAmdSet *set, const int *target_class, int alphabet_len, int n_classes,
+                       float leakage, int speculated) {
+  RamdEngine *e = set->eng;
+  e->mheads_alen = alphabet_len;
+  e->b.mheads_alen = alphabet_len;
+  e->rng_version++; /* the leak decisions are draws from the streams' generators */
+  if (target_class) {
+    ramd_upload(e->d_mclass + set->row0, target_class, set->n * sizeof(int));
+    mclass_note(e, target_class, set->n, n_classes);
+  }
+  /* noise that was generated past THIS loss before its classes were known */
+  for (int k = 0; k < 2; k++) {
+    if (e->sp[k].pending && e->sp[k].assumed_classes && e->sp[k].version == e->rng_version &&
+        (e->sp[k].assumed_classes != n_classes || !e->mclass_in_range)) {
+      e->sp[0].pending = e->sp[1].pending = 0; /* (the other one hangs on it, or is the pass in between: redone) */
+    }
+  }
+  /* u64 threshold = leakage * UINT64_MAX (charmodel-multi-predict.c:27): float arithmetic */
+  float tf = leakage * (float)UINT64_MAX;
+  unsigned long long threshold = tf >= 18446744073709551615.0f ? UINT64_MAX : (unsigned long long)tf;
+  ramd_launch_multi_softmax_error(ramd_stream, &e->sh, &e->b, set->row0, set->n, alphabet_len, n_classes,
+                                  threshold, e->d_mclass + set->row0,
+                                  e->d_mranges + (size_t)set->row0 * MULTI_RANGE_STRIDE,
+                                  MULTI_RANGE_STRIDE);
+  set_streams_dev_wrote(set);
+  if (!speculated) {
+    noise_speculate(set); /* the next draws are the next forward pass's noise */
+  }
+}
+
+static void multi_calc_deltas(RnnAmdSet *set, int accumulate, RamdPendingDelta *defer) {
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_multi_calc_deltas");
+  if (!e->d_mranges) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_multi_calc_deltas before any multi-head loss\n");
+    abort();
+  }
+  /* (heads of at least 24 columns: a stream's ranges then lie at least 16 columns apart, see k_top_backprop_heads) */
+  set_calc_deltas(set, accumulate, NULL, NULL, e->mheads_alen >= 24 ? RAMD_RANGES_ARE_HEADS : 0,
+                  e->d_mranges + (size_t)set->row0 * MULTI_RANGE_STRIDE, MULTI_RANGE_STRIDE, defer);
+}
+void rnn_amd_set_multi_calc_deltas(RnnAmdSet *set, int accumulate) { multi_calc_deltas(set, accumulate, NULL); }
+
+static void multi_step_deltas(RnnAmdSet *set, const int *hot, const int *next, const int *target_class, int alphabet_len,
+                              float leakage, int accumulate, RamdPendingDelta *defer) {
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_multi_step_deltas");
+  int n_classes = multi_heads(e, alphabet_len);
+  /* the three small uploads leave with one launch */
+  ramd_upload_q(e->b.hot + set->row0, hot, set->n * sizeof(int));
+  if (target_class) {
+    ramd_upload_q(e->d_mclass + set->row0, target_class, set->n * sizeof(int));
+    mclass_note(e, target_class, set->n, n_classes);
+  }
+  ramd_upload(e->b.target + set->row0, next, set->n * sizeof(int));
+  set->early_spec_classes = set->fwd_only ? 0 : n_classes; /* (set_forward's fused branch takes it up) */
+  set_forward(set, RAMD_IN_ONE_HOT, NULL, 0, 0, NULL, 1, 0);
+  int early = set->early_spec_classes < 0;
+  set->early_spec_classes = 0;
+  if (!early && e->sp_adopted >= 0 && !set->fwd_only) {
+    noise_speculate_from(set, n_classes);
+    early = 1;
+  }
+  multi_loss(set, NULL, alphabet_len, n_classes, leakage, early);
+  multi_calc_deltas(set, accumulate, defer);
+}
+void rnn_amd_set_multi_step_deltas(RnnAmdSet *set, const int *hot, const int *next,
+                                   const int *target_class, int alphabet_len, float leakage,
+                                   int accumulate) {
+  multi_step_deltas(set, hot, next, target_class, alphabet_len, leakage, accumulate, NULL);
+}
+
+static void check_text_pos(RamdEngine *e, int i, int last_ok, const char *what) {
+  if (!e->b.text) {
+    fprintf(stderr, "librecur_amd: %s without rnn_amd_set_load_text\n", what);
+    abort();
+  }
+  /* the reference's loops run i over [start, len - 1) (charmodel-predict.c:288,
+   * charmodel-multi-predict.c:244); the kernels wrap the per-stream offset once, so i
+   * itself has to be in range */
+  if (i < 0 || i >= e->b.text_len - 1 + last_ok) {
+    fprintf(stderr, "librecur_amd: %s: text position %d outside [0, %d)\n", what, i,
+            e->b.text_len - 1 + last_ok);
+    abort();
+  }
+}
+
+/* the same from the text on the device: stream j reads text[o] and is scored against
+ * text[o + 1], o as in rnn_amd_set_char_step */
+void rnn_amd_set_multi_text_loss(RnnAmdSet *set, int i, const int *target_class, int alphabet_len,
+                                 float leakage) {
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_multi_text_loss");
+  check_text_pos(e, i, 0, "rnn_amd_set_multi_text_loss");
+  int n_classes = multi_heads(e, alphabet_len);
+  set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 0); /* advance + one-hot opinion + b.target */
+  multi_loss(set, target_class, alphabet_len, n_classes, leakage, 0);
+}
+
+/* rnn_bptt_advance (optional) + one_hot_opinion of the stream's text symbol, nothing else:
+ * rnn_char_multitext_spin's step (charmodel-multi-predict.c:293-297); i may be len - 1 */
+void rnn_amd_set_text_opinion(RnnAmdSet *set, int i, int advance) {
+  RamdEngine *e = set->eng;
+  check_text_pos(e, i, 1, "rnn_amd_set_text_opinion");
+  set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, advance, 0);
+}
+
+/* rnnca's loss on the device (gstrnnca.c:701-714) after rnn_amd_set_opinion: sigmoid of the
+ * first n outputs in place, o_error = slope * (target - answer); targets: host [n_nets][ld] */
+void rnn_amd_set_sigmoid_mse_error(RnnAmdSet *set, const float *targets, int ld, int n) {
+  RamdEngine *e = set->eng;
+  ramd_top_done_clear(e);
+  ramd_set_need_training(set, "rnn_amd_set_sigmoid_mse_error");
+  if (n < 1 || n > e->sh.output_size || ld < n) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_sigmoid_mse_error over %d of %d outputs (ld %d)\n", n,
+            e->sh.output_size, ld);
+    abort();
+  }
+  set_streams_to_dev(set);
+  size_t bytes = (size_t)set->n * n * sizeof(float);
+  if (bytes > e->d_group_bytes) {
+    ramd_dsync();
+    ramd_dev_free(e->d_group);
+    e->d_group = ramd_dev_alloc(bytes);
+    e->d_group_bytes = bytes;
+  }
+  ramd_upload_rows(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n);
+  ramd_launch_sigmoid_mse_error(ramd_stream, &e->sh, &e->b, set->row0, set->n, n, (const float *)e->d_group,
+                                n);
+  set_streams_dev_wrote(set);
+}
+
+/* dense inputs -> hidden layer's sums only (they stay in the workspace for ramd_launch_dense_top); 0 where that launch
+ * cannot follow */
+static int dense_top_ok(RnnAmdSet *set, const float *inputs) {
+  RamdEngine *e = set->eng;
+  return inputs && !set->fwd_only && !e->sh.bI && ramd_dense_top_ok(&e->sh) &&
+         set->nets[0]->presynaptic_noise == 0.0f && set->nets[0]->bptt;
+}
+
+void rnn_amd_set_opinion_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld,
+                                     int n) {
+  RamdEngine *e = set->eng;
+  if (!dense_top_ok(set, inputs) || n < 1 || n > e->sh.output_size || ld < n) {
+    rnn_amd_set_opinion(set, inputs, ld_inputs, NULL);
+    rnn_amd_set_sigmoid_mse_error(set, targets, ld, n);
+    return;
+  }
+  ramd_set_need_training(set, "rnn_amd_set_opinion_sigmoid_mse");
+  size_t bytes = (size_t)set->n * n * sizeof(float);
+  if (bytes > e->d_group_bytes) {
+    ramd_dsync();
+    ramd_dev_free(e->d_group);
+    e->d_group = ramd_dev_alloc(bytes);
+    e->d_group_bytes = bytes;
+  }
+  /* inputs and targets leave together with the ring indices (set_forward's flush) */
+  ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), e->sh.input_size * sizeof(float), set->n, 0);
+  ramd_upload_rows_q(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n, 0);
+  int fwd_ks = set_forward(set, RAMD_IN_DENSE, e->d_dense, e->sh.input_size, 0, NULL, 0, 1);
+  if (!ramd_launch_dense_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, fwd_ks, (const float *)e->d_group, n, n, 0,
+                             NULL, NULL, NULL, NULL)) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_sigmoid_mse: the top launch declined a shape it had accepted\n");
+    abort();
+  }
+  set_streams_dev_wrote(set);
+  e->top_done = 1;
+  e->top_done_row0 = set->row0;
+  e->top_done_n = set->n;
+  e->top_done_masked = 0;
+}
+
+void rnn_amd_set_opinion_grouped_softmax(RnnAmdSet *set, const float *inputs, int ld_inputs, int n_groups,
+                                         const int *group_offset, const int *group_size, const int *targets,
+                                         const float *error_weight, u8 *trained) {
+  RamdEngine *e = set->eng;
+  const RamdShape *s = &e->sh;
+  if (!dense_top_ok(set, inputs) || !trained || set->n % 4 != 0) {
+    rnn_amd_set_opinion(set, inputs, ld_inputs, NULL);
+    rnn_amd_set_grouped_softmax_error(set, n_groups, group_offset, group_size, targets, error_weight, trained);
+    return;
+  }
+  ramd_set_need_training(set, "rnn_amd_set_opinion_grouped_softmax");
+  for (int i = 0; i < n_groups; i++) {
+    if (group_offset[i] < 0 || group_size[i] < 1 || group_offset[i] + group_size[i] > s->output_size) {
+      fprintf(stderr, "librecur_amd: class group %d (%d + %d) outside the %d outputs\n", i, group_offset[i],
+              group_size[i], s->output_size);
+      abort();
+    }
+  }
+  size_t ints = (size_t)2 * n_groups + (size_t)set->n * n_groups;
+  size_t bytes = ints * sizeof(int) + (error_weight ? (size_t)s->output_size * sizeof(float) : 0);
+  if (bytes > e->d_group_bytes) {
+    ramd_dsync();
+    ramd_dev_free(e->d_group);
+    e->d_group = ramd_dev_alloc(bytes);
+    e->d_group_bytes = bytes;
+  }
+  int *d = (int *)e->d_group;
+  ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), s->input_size * sizeof(float), set->n, 0);
+  ramd_upload_q(d, group_offset, n_groups * sizeof(int));
+  ramd_upload_q(d + n_groups, group_size, n_groups * sizeof(int));
+  ramd_upload_q(d + 2 * n_groups, targets, (size_t)set->n * n_groups * sizeof(int));
+  float *dw = NULL;
+  if (error_weight) {
+    dw = (float *)(d + ints);
+    ramd_upload_q(dw, error_weight, (size_t)s->output_size * sizeof(float));
+  }
+  for (int j = 0; j < set->n; j++) { /* a stream is trained if any of its groups has a usable target */
+    trained[j] = 0;
+    for (int i = 0; i < n_groups; i++) {
+      int t = targets[(size_t)j * n_groups + i];
+      trained[j] |= (t >= 0 && t < group_size[i]);
+    }
+  }
+  active_mask_to_dev(e, trained, set->n, 1); /* (for the delta call that follows: travels with the rest) */
+  int fwd_ks = set_forward(set, RAMD_IN_DENSE, e->d_dense, s->input_size, 0, NULL, 0, 1);
+  if (!ramd_launch_dense_top(ramd_stream, s, &e->b, set->row0, set->n, fwd_ks, NULL, 0, 0, n_groups, d, d + n_groups,
+                             d + 2 * n_groups, dw)) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_grouped_softmax: the top launch declined a shape it had accepted\n");
+    abort();
+  }
+  set_streams_dev_wrote(set);
+  e->top_done = 1;
+  e->top_done_row0 = set->row0;
+  e->top_done_n = set->n;
+  e->top_done_masked = 1;
+  if (!e->top_done_mask) {
+    e->top_done_mask = ramd_zalloc((size_t)e->sh.Scap + 4);
+  }
+  memcpy(e->top_done_mask, trained, (size_t)set->n); /* (a copy of its own: active_host follows whatever mask is sent next) */
+}
+
+/* fill_frame's fast_sigmoid_array(answer, answer, n) (gstrnnca.c:813-814) for every net of the
+ * set (training or forward-only), then optionally the n_nets x o_size answers to the host */
+void rnn_amd_set_sigmoid_outputs(RnnAmdSet *set, int n, float *outputs) {
+  RamdEngine *e = set->eng;
+  if (n < 1 || n > e->sh.output_size) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_sigmoid_outputs over %d of %d outputs\n", n,
+            e->sh.output_size);
+    abort();
+  }
+  set_streams_to_dev(set);
+  const int r0 = set_state_row0(set);
+  ramd_launch_sigmoid_outputs(ramd_stream, &e->sh, &e->b, r0, set->n, n);
+  set_streams_dev_wrote(set);
+  if (outputs) {
+    ramd_d2h(outputs, e->b.out + (size_t)r0 * e->sh.O, (size_t)set->n * e->sh.O * sizeof(float));
+    ramd_dsync();
+  }
+}
+
+void rnn_amd_set_load_text(RnnAmdSet *set, const u8 *text, int len) {
+  RamdEngine *e = set->eng;
+  if (!text || len < 2) { /* a step reads text[o] and text[o + 1] */
+    fprintf(stderr, "librecur_amd: rnn_amd_set_load_text needs at least 2 symbols (got %d)\n", len);
+    abort();
+  }
+  ramd_dsync();
+  ramd_dev_free(e->b.text);
+  e->b.text = ramd_dev_alloc((size_t)len + 1); /* zeroed: the "next symbol" of the last one */
+  ramd_h2d(e->b.text, text, len);
+  e->b.text_len = len;
+  ramd_dsync();
+}
+
+static void char_step_deltas(RnnAmdSet *set, int i, RamdPendingDelta *defer) {
+  RamdEngine *e = set->eng;
+  check_text_pos(e, i, 0, "rnn_amd_set_char_step");
+  if (ramd_text_top_ok(&e->sh)) {
+    /* advance + hidden layer, then output layer, loss and top backprop in one launch */
+    int fwd_ks = set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 1);
+    noise_speculate(set); /* no draws between this pass's noise and the next one's */
+    ramd_launch_text_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, fwd_ks);
+    set_calc_deltas(set, 0, NULL, NULL, RAMD_TOP_DONE, NULL, 0, defer);
+  } else {
+    set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 0); /* advance + one-hot opinion */
+    noise_speculate(set);
+    ramd_launch_softmax_error(ramd_stream, &e->sh, &e->b, set->row0, set->n);
+    set_calc_deltas(set, 0, NULL, NULL, 0, NULL, 0, defer);
+  }
+}
+
+void rnn_amd_set_char_step_deltas(RnnAmdSet *set, int i) { char_step_deltas(set, i, NULL); }
+
+/* With ONE rank the sum over the ranks is the rank's own sum and the sharded update is the whole update: the exchange
+ * step -- the all-reduce, or the barriers and the peer-pointer update kernel -- is skipped and the generation is the
+ * plain one (one-rank cost of either exchange path: 0; round 4: +4.8 us through RCCL, +11 us kernel-issued).
+ * RECUR_AMD_DIST_ONE_RANK_EXCHANGE=1 keeps the exchange step in (tests and `bench.py --dist` exercise it on one GPU). */
+static int one_rank_exchange_forced(void) {
+  static int on = -1;
+  if (on < 0) {
+    const char *v = getenv("RECUR_AMD_DIST_ONE_RANK_EXCHANGE");
+    on = v && *v == '1';
+  }
+  return on;
+}
+
+/* what a one-call generation does before its update: the text step (symbol i of the resident text), or a dense-input
+ * generation with rnnca's loss (rnn_amd_set_dense_step_sigmoid_mse) */
+typedef struct {
+  int i;                /* text position, or -1: dense, or -2: the multi-head step */
+  const float *inputs;  /* dense: host [n][ld_inputs] */
+  int ld_inputs;
+  const float *targets; /* host [n][ld], the first n_targets outputs */
+  int ld, n_targets;
+  /* the multi-head step (rnn_amd_set_multi_step_deltas's arguments) */
+  const int *hot, *next, *target_class;
+  int alphabet_len;
+  float leakage;
+} StepSpec;
+
+static void step_deltas(RnnAmdSet *set, const StepSpec *sp, RamdPendingDelta *defer) {
+  if (sp->i >= 0) {
+    char_step_deltas(set, sp->i, defer);
+  } else if (sp->i == -2) {
+    multi_step_deltas(set, sp->hot, sp->next, sp->target_class, sp->alphabet_len, sp->leakage, 0, defer);
+  } else {
+    rnn_amd_set_opinion_sigmoid_mse(set, sp->inputs, sp->ld_inputs, sp->targets, sp->ld, sp->n_targets);
+    set_calc_deltas(set, 0, NULL, NULL, 0, NULL, 0, defer);
+  }
+}
+
+static void set_step(RnnAmdSet *set, const StepSpec *sp, int learning_style, float momentum) {
+  if (set->eng->xchg_world > 1 || (set->eng->xchg_world == 1 && one_rank_exchange_forced())) {
+    /* deltas -> (barrier) -> sharded update with the sum over the ranks in it -> (barrier) */
+    step_deltas(set, sp, NULL);
+    rnn_amd_set_apply_exchange(set, learning_style, momentum);
+    return;
+  }
+  /* the deltas go straight from the GEMM's K slabs into the update (and into ih_delta) when
+   * nothing can look at them in between: library-owned storage, no log on the prototype */
+  RamdPendingDelta pend = {0};
+  const int dist = ramd_dist_active() && (rnn_amd_dist_world() > 1 || one_rank_exchange_forced());
+  int fuse = !set->eng->delta_external && !set->nets[0]->log && !dist;
+  if (dist) {
+    ramd_halves_seen = 0;
+    ramd_set_delta_half_hook(ramd_delta_half_ready, set->eng);
+  }
+  float mw, rate, ho_rate;
+  const int method = ramd_update_rule(set->nets[0]->bptt, learning_style, momentum, &mw, &rate, &ho_rate);
+  if (fuse && !set->eng->sh.bI && (method == RNN_MOMENTUM_WEIGHTED || method == RNN_ADAGRAD)) {
+    /* the momentum rule (recur-nn.c:482-487, 653-676) or ADAGRAD (518-524, the multi-head trainer's rule): the
+     * weight-delta GEMM may carry the update out in its own epilogue (kernels_bptt.hip: k_delta_direct), with the rates
+     * and weights ramd_apply_learning would use (ADAGRAD's arithmetic reads neither the momentum nor its weight) */
+    _Static_assert(RNN_MOMENTUM_WEIGHTED == 0 && RNN_ADAGRAD == 4, "RamdPendingDelta.fuse_method takes these two as they are");
+    ramd_engine_need_dev(set->eng, RNN_AMD_WEIGHTS | RNN_AMD_MOMENTUMS);
+    pend.fuse_want = 1;
+    pend.fuse_method = method;
+    pend.fuse_rate = rate;
+    pend.fuse_ho_rate = ho_rate;
+    pend.fuse_momentum = momentum;
+    pend.fuse_mw = mw;
+  }
+  step_deltas(set, sp, fuse ? &pend : NULL);
+  if (pend.fuse_done) { /* weights and momentum are updated, the delta arrays hold the sums */
+    ramd_engine_dev_wrote(set->eng, RNN_AMD_WEIGHTS | RNN_AMD_MOMENTUMS | RNN_AMD_DELTAS);
+    return;
+  }
+  if (dist) {
+    /* the one exchange step of the path: this rank's deltas become the sum over all ranks'
+     * streams (recur-nn.c:724-739 distributed), then the identical update everywhere */
+    ramd_set_delta_half_hook(NULL, NULL);
+    if (ramd_halves_seen == 3) { /* both halves are on their way: the update waits for them */
+      HIP_OK(hipStreamWaitEvent(ramd_stream, ramd_half_summed[0], 0));
+      HIP_OK(hipStreamWaitEvent(ramd_stream, ramd_half_summed[1], 0));
+    } else { /* a shape the two-halves form does not take: one all-reduce behind the deltas */
+      const int tev = ramd_timing_begin(ramd_stream, RAMD_T_XCHG);
+      rnn_amd_dist_all_reduce(set->eng->b.ih_delta, set->eng->ih_size + set->eng->ho_size);
+      ramd_timing_end(ramd_stream, tev);
+    }
+  }
+  ramd_apply_learning(set->nets[0], learning_style, momentum, (pend.slab || pend.ho_slab) ? &pend : NULL);
+}
+
+/* the multi-head generation as ONE call: rnn_amd_set_multi_step_deltas (accumulate 0) + rnn_apply_learning -- knowing the
+ * update that follows, the weight-delta GEMM carries it out in its own epilogue where the rule is ADAGRAD (the trainer's)
+ * or the momentum rule: no optimiser launch (17 us of configs[3]'s 340) */
+void rnn_amd_set_multi_step(RnnAmdSet *set, const int *hot, const int *next, const int *target_class, int alphabet_len,
+                            float leakage, int learning_style, float momentum) {
+  StepSpec sp = {-2, NULL, 0, NULL, 0, 0, hot, next, target_class, alphabet_len, leakage};
+  set_step(set, &sp, learning_style, momentum);
+}
+
+void rnn_amd_set_char_step(RnnAmdSet *set, int i, int learning_style, float momentum) {
+  StepSpec sp = {i, NULL, 0, NULL, 0, 0, NULL, NULL, NULL, 0, 0.0f};
+  set_step(set, &sp, learning_style, momentum);
+}
+
+/* rnnca's maybe_learn for every trainer (gstrnnca.c:693-740) as one call: see recur_amd.h */
+void rnn_amd_set_dense_step_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld,
+                                        int n, int learning_style, float momentum) {
+  if (!inputs) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_dense_step_sigmoid_mse needs the inputs\n");
+    abort();
+  }
+  rnn_bptt_clear_deltas(set->nets[0]); /* (lazy: the delta call below simply does not accumulate) */
+  StepSpec sp = {-1, inputs, ld_inputs, targets, ld, n, NULL, NULL, NULL, 0, 0.0f};
+  set_step(set, &sp, learning_style, momentum);
+}
+
+/* The single-net text step of rnn_char_epoch (charmodel-predict.c:312-321) without a host round trip per
+ * symbol: rnn_bptt_advance, one_hot_opinion of text[i], net_error_bptt's loss against text[i + 1] (on the
+ * device, into the set's statistics) and rnn_bptt_calculate(net, batch_size) -- the top layer updated at once
+ * with bptt->momentum, the recurrent layer every batch_size generations (recur-nn.c:919-1019).  For a set of
+ * ONE net; the caller sets bptt->momentum as the reference's loop does. */
+void rnn_amd_set_char_step_fused(RnnAmdSet *set, int i, unsigned batch_size) {
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_char_step_fused");
+  if (set->n != 1) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_char_step_fused is the single-net path (set of %d)\n", set->n);
+    abort();
+  }
+  check_text_pos(e, i, 0, "rnn_amd_set_char_step_fused");
+  RecurNN *net = set->nets[0];
+  const RamdShape *s = &e->sh;
+  const int j = set->row0;
+  const int batched = batch_size > 1;
+  unsigned top_done = 0;
+  if (ramd_text_top_ok(s)) { /* advance + hidden layer, then output layer, loss and top backprop in one launch */
+    int fwd_ks = set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 1);
+    ramd_launch_text_top(ramd_stream, s, &e->b, j, 1, fwd_ks);
+    top_done = RAMD_TOP_DONE;
+  } else {
+    set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 0); /* advance + one-hot opinion */
+    ramd_launch_softmax_error(ramd_stream, s, &e->b, j, 1);
+  }
+  int accumulate = batched;
+  ramd_deltas_materialize(e); /* a pending rnn_bptt_clear_deltas: this path never writes ho_delta (see calc_deltas_one) */
+  ramd_engine_need_dev(e, RNN_AMD_WEIGHTS | RNN_AMD_MOMENTUMS | RNN_AMD_DELTAS);
+  ramd_push_learn_rates(e, j, 1);
+  if (e->err_pending && (e->err_row0 != j || e->err_nrows != 1)) {
+    ramd_err_flush(e);
+  }
+  ramd_set_uniform_idx(e, j, 1);
+  ramd_launch_calc_deltas(ramd_stream, s, &e->b, j, 1, accumulate, NULL, 0, NULL,
+                          net->flags | RAMD_NO_HO_DELTA | (batched ? 0 : RAMD_IH_SCALE_IN_RATE) | top_done, NULL);
+  ramd_err_after_calc(e, j, 1);
+  net->generation++;
+  set_streams_dev_wrote(set);
+  ramd_fused_net_update(e, net, j, batch_size);
+}
+
+void rnn_amd_set_read_stats(RnnAmdSet *set, RnnAmdStats *stats, int clear) {
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_read_stats");
+  int n = set->n, r0 = set->row0;
+  double *d = malloc(4 * n * sizeof(double));
+  long long *l = malloc(2 * n * sizeof(long long));
+  ramd_d2h(d, e->b.stat_err + r0, n * sizeof(double));
+  ramd_d2h(d + n, e->b.stat_ent + r0, n * sizeof(double));
+  ramd_d2h(d + 2 * n, e->b.stat_zero + r0, n * sizeof(double));
+  ramd_d2h(d + 3 * n, e->b.stat_depth + r0, n * sizeof(double));
+  ramd_d2h(l, e->b.stat_correct + r0, n * sizeof(long long));
+  ramd_d2h(l + n, e->b.stat_count + r0, n * sizeof(long long));
+  ramd_dsync();
+  memset(stats, 0, sizeof(*stats));
+  for (int j = 0; j < n; j++) {
+    stats->error += d[j];
+    stats->entropy += d[n + j];
+    stats->hidden_zeros += d[2 * n + j];
+    stats->bptt_depth_sum += d[3 * n + j];
+    stats->correct += l[j];
+    stats->count += l[n + j];
+  }
+  free(d);
+  free(l);
+  if (clear) {
+    HIP_OK(hipMemsetAsync(e->b.stat_err + r0, 0, n * sizeof(double), ramd_stream));
+    HIP_OK(hipMemsetAsync(e->b.stat_ent + r0, 0, n * sizeof(double), ramd_stream));
+    HIP_OK(hipMemsetAsync(e->b.stat_zero + r0, 0, n * sizeof(double), ramd_stream));
+    HIP_OK(hipMemsetAsync(e->b.stat_depth + r0, 0, n * sizeof(double), ramd_stream));
+    HIP_OK(hipMemsetAsync(e->b.stat_correct + r0, 0, n * sizeof(long long), ramd_stream));
+    HIP_OK(hipMemsetAsync(e->b.stat_count + r0, 0, n * sizeof(long long), ramd_stream));
+  }
+}
+
+void rnn_amd_set_external_delta(RnnAmdSet *set, void *device_buffer) {
+  RamdEngine *e = set->eng;
+  float *dst = device_buffer ? (float *)device_buffer : e->delta_own;
+  ramd_deltas_materialize(e);
+  if (dst != e->b.ih_delta) {
+    HIP_OK(hipMemcpyAsync(dst, e->b.ih_delta, (e->ih_size + e->ho_size) * sizeof(float),
+                          hipMemcpyDeviceToDevice, ramd_stream));
+    ramd_dsync();
+    e->b.ih_delta = dst;
+    e->b.ho_delta = dst + e->ih_size;
+  }
+  e->delta_external = device_buffer != NULL;
+}
