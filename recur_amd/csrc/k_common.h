@@ -97,20 +97,66 @@ __device__ __forceinline__ float soft_clip_dev(float sum, float halfmax) {
   return 2.0f * x / (1 + x * x * fudge);
 }
 
-// A wave-wide sum that every lane gets, without the LDS crossbar (round 6): a butterfly over the sixteen lanes of a row in
-// four DPP steps, then the four rows' values through scalar registers (v_readlane) -- a dozen instructions of a few cycles
-// each where six __shfl_xor steps are six dependent ds_bpermute round trips.  (Every lane of the wave must be active.)
-__device__ __forceinline__ float wave_sum_all(float x) {
-#define RAMD_DPP_ADD_(x, ctrl) x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), ctrl, 0xf, 0xf, true))
-  RAMD_DPP_ADD_(x, 0xB1);  /* quad_perm [1, 0, 3, 2] */
-  RAMD_DPP_ADD_(x, 0x4E);  /* quad_perm [2, 3, 0, 1] */
-  RAMD_DPP_ADD_(x, 0x141); /* row_half_mirror */
-  RAMD_DPP_ADD_(x, 0x140); /* row_mirror */
-#undef RAMD_DPP_ADD_
+// The DPP row butterfly, stated once: `x` of the lane that `ctrl` names within this lane's row of sixteen (no LDS crossbar).
+#define RAMD_DPP(x, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), ctrl, 0xf, 0xf, true))
+struct OpAdd {
+  __device__ __forceinline__ float operator()(float a, float b) const { return a + b; }
+};
+struct OpMax {
+  __device__ __forceinline__ float operator()(float a, float b) const { return fmaxf(a, b); }
+};
+struct OpMin {
+  __device__ __forceinline__ float operator()(float a, float b) const { return fminf(a, b); }
+};
+/* every lane gets `op` over the 2^STEPS lanes of its group within a row: 4 = the sixteen of a row, 3 = the eight of a half row */
+template <int STEPS = 4, class OP> __device__ __forceinline__ float dpp_row_all(float x, OP op) {
+  static_assert(STEPS == 3 || STEPS == 4, "a half row or a row");
+  x = op(x, RAMD_DPP(x, 0xB1));  /* quad_perm [1, 0, 3, 2] */
+  x = op(x, RAMD_DPP(x, 0x4E));  /* quad_perm [2, 3, 0, 1] */
+  x = op(x, RAMD_DPP(x, 0x141)); /* row_half_mirror: the other quad of the eight */
+  if (STEPS == 4) x = op(x, RAMD_DPP(x, 0x140)); /* row_mirror */
+  return x;
+}
+// A wave-wide max / min / sum that every lane gets, without the LDS crossbar (round 6): the row butterfly, then the four
+// rows' values through scalar registers (v_readlane), (r0 op r1) op (r2 op r3) -- a dozen instructions of a few cycles each
+// where six __shfl_xor steps are six dependent ds_bpermute round trips (the one-wave softmax was 1.6 us of the top launch).
+// (Every lane of the wave must be active.)
+template <class OP> __device__ __forceinline__ float wave_all(float x, OP op) {
+  x = dpp_row_all(x, op);
   const int xi = __builtin_bit_cast(int, x);
   const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 16));
   const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 48));
-  return (r0 + r1) + (r2 + r3);
+  return op(op(r0, r1), op(r2, r3));
+}
+__device__ __forceinline__ float wave_sum_all(float x) { return wave_all(x, OpAdd{}); }
+
+// The activation (rnn_activation: 2 RNN_RESQRT, 5 RNN_RECLIP20, anything else RNN_RELU), stated once for every kernel that
+// reads it from the shape (k_chain_persist has it as a template argument).  Forward, recur-nn.c:123-148:
+__device__ __forceinline__ float act_forward(const RamdShape &s, float x) {
+#pragma clang fp contract(off)
+  if (s.activation == 2) return (x > 0.0f) ? sqrtf(x + 1.0f) - 1.0f : 0.0f;
+  if (s.activation == 5) x = x < 20.0f ? x : 20.0f;
+  return (x > 0.0f) ? x : 0.0f;
+}
+/* Backward (recur-nn.c:359-376), from the node's forward value xi.  The gate: does any error pass the node? */
+__device__ __forceinline__ bool act_live(const RamdShape &s, float xi) {
+  return xi != 0.0f && (s.activation != 5 || xi < 20.0f);
+}
+/* the derivative's scale on an error that passed the gate (`on`).  RESQRT alone has one: a site that has to fetch xi from
+ * another lane for it asks act_has_back_scale first and applies resqrt_back_scale itself. */
+__device__ __forceinline__ bool act_has_back_scale(const RamdShape &s) { return s.activation == 2; }
+__device__ __forceinline__ float resqrt_back_scale(float xi, float e) {
+#pragma clang fp contract(off)
+  return e / (2 * (xi + 1.0f));
+}
+__device__ __forceinline__ float act_back_scale(const RamdShape &s, float xi, float e, bool on = true) {
+  if (on && act_has_back_scale(s)) e = resqrt_back_scale(xi, e);
+  return e;
+}
+/* both: the error that leaves the node */
+__device__ __forceinline__ float act_backward(const RamdShape &s, float xi, float e) {
+  const bool on = act_live(s, xi);
+  return act_back_scale(s, xi, on ? e : 0.0f, on);
 }
 
 // deterministic block-wide sum (fixed tree), blockDim.x == 256

@@ -82,9 +82,8 @@ __device__ __forceinline__ float extras_compute(const View &v, int t, int r, int
     int c = c0 + lane;
     int n = (c == 0) ? 0 : s.hidden_size + c;
     float xi = (c0 == 0) ? in.xi : ((c < nx) ? x[n] : 0.0f);
-    bool on = xi != 0.0f && (s.activation != 5 || xi < 20.0f);
     if (c < nx) dst[c] = 0.0f;
-    unsigned long long live = __ballot(on);
+    unsigned long long live = __ballot(act_live(s, xi));
     /* two live columns per round, so that both weight rows are in flight together (a
      * one-hot text stream has exactly two: the bias row and the symbol's row) */
     while (live) {
@@ -118,9 +117,9 @@ __device__ __forceinline__ float extras_compute(const View &v, int t, int r, int
         acca += __shfl_xor(acca, off, 64);
         accb += __shfl_xor(accb, off, 64);
       }
-      if (s.activation == 2) {
-        acca /= 2 * (xa + 1.0f);
-        accb /= 2 * (xb + 1.0f);
+      if (act_has_back_scale(s)) {
+        acca = resqrt_back_scale(xa, acca);
+        accb = resqrt_back_scale(xb, accb);
       }
       if (lane == 0) {
         dst[ca] = acca;
@@ -417,7 +416,7 @@ __device__ __forceinline__ void extras_control_tail(const View &v, int r, int j,
 #pragma unroll
     for (int b = 0; b < BB; b++) {
 #pragma unroll
-      for (int h = 0; h < 2; h++) live[b][h] = __ballot(xi[b][h] != 0.0f && (s.activation != 5 || xi[b][h] < 20.0f));
+      for (int h = 0; h < 2; h++) live[b][h] = __ballot(act_live(s, xi[b][h]));
       const unsigned long long rest = live[b][0] & ~1ull;
       l1[b] = rest ? __ffsll((long long)rest) - 1 : live[b][1] ? 64 + __ffsll((long long)live[b][1]) - 1 : -1;
       const char *wr = reinterpret_cast<const char *>(v.b.ih_w + (size_t)(l1[b] >= 0 ? s.hidden_size + l1[b] : 0) * s.H);
@@ -454,9 +453,9 @@ __device__ __forceinline__ void extras_control_tail(const View &v, int r, int j,
       if (lane == 0) hs_sh[t] = hs[b];
       const bool has0 = (live[b][0] & 1ull) != 0;
       float e0 = has0 ? a0[b] : 0.0f, e1 = l1[b] >= 0 ? a1[b] : 0.0f;
-      if (s.activation == 2) {
-        e0 /= 2 * (value_of(xi[b], 0) + 1.0f);
-        e1 /= 2 * (value_of(xi[b], l1[b] >= 0 ? l1[b] : 0) + 1.0f);
+      if (act_has_back_scale(s)) { /* (asked first: the values are fetched from other lanes) */
+        e0 = resqrt_back_scale(value_of(xi[b], 0), e0);
+        e1 = resqrt_back_scale(value_of(xi[b], l1[b] >= 0 ? l1[b] : 0), e1);
       }
       auto *dst = as_global(v.b.ex + ((size_t)(t + 1) * s.Scap + r) * nxp);
       if (lane < nx) dst[lane] = (lane == 0 && has0) ? e0 : (lane == l1[b]) ? e1 : 0.0f;
@@ -498,9 +497,9 @@ __device__ __forceinline__ void extras_control_tail(const View &v, int r, int j,
           acca += __shfl_xor(acca, off, 64);
           accb += __shfl_xor(accb, off, 64);
         }
-        if (s.activation == 2) {
-          acca /= 2 * (xa + 1.0f);
-          accb /= 2 * (xb + 1.0f);
+        if (act_has_back_scale(s)) {
+          acca = resqrt_back_scale(xa, acca);
+          accb = resqrt_back_scale(xb, accb);
         }
         if (lane == 0) {
           dst[la] = acca;
@@ -680,10 +679,7 @@ __device__ __forceinline__ void extras_dense_tail(const View &v, int r, int j, i
           float e = 0.0f;
 #pragma unroll
           for (int w = 0; w < NW; w++) e += red[(w * 32 + erow) * LD + c];
-          const float xi = xv[q];
-          const bool on = xi != 0.0f && (s.activation != 5 || xi < 20.0f);
-          e = on ? e : 0.0f;
-          if (on && s.activation == 2) e /= 2 * (xi + 1.0f);
+          e = act_backward(s, xv[q], e);
           if (live) dst[c] = e;
           sq += e * e;
         }

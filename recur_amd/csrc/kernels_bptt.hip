@@ -788,10 +788,7 @@ __global__ __launch_bounds__(64) void k_extras_finalize(View v, int row0, int nr
     float e = 0.0f;
     for (int z = 0; z < ks; z++) e += v.b.slab[((size_t)z * M + m) * nxp + c];
     int n = c == 0 ? 0 : s.hidden_size + c;
-    float xi = x[n];
-    bool on = xi != 0.0f && (s.activation != 5 || xi < 20.0f);
-    e = on ? e : 0.0f;
-    if (on && s.activation == 2) e /= 2 * (xi + 1.0f);
+    e = act_backward(s, x[n], e);
     dst[c] = e;
     sq += e * e;
   }
@@ -957,10 +954,7 @@ __global__ __launch_bounds__(64 * XD_WAVES) void k_extras_dense(View v, int row0
       float e = 0.0f;
 #pragma unroll
       for (int w = 0; w < XD_WAVES; w++) e += red[w][row][c];
-      const float xi = xv[q];
-      const bool on = xi != 0.0f && (s.activation != 5 || xi < 20.0f);
-      e = on ? e : 0.0f;
-      if (on && s.activation == 2) e /= 2 * (xi + 1.0f);
+      e = act_backward(s, xv[q], e);
       if (live) dst[c] = e;
       sq += e * e;
     }
@@ -1479,14 +1473,11 @@ __global__ __launch_bounds__(1024) void k_bptt_small(View v, int r, int accumula
   const float min_error_sum = (mef_rate < min_error_gain) ? mef_rate : min_error_gain;
   const size_t plane = (size_t)s.Scap * I;
 #define LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-  /* sum over the eight lanes of a row without LDS: two quad permutes and a half-row mirror */
-#define DPP_ADD(x, ctrl) x += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), ctrl, 0xf, 0xf, true))
   const bool two_rows = (wave * 8 + 128) < I; /* this wave's second rows exist */
   __syncthreads();
   if (tid < I) { /* step 0's input row */
     const float xi = xall[tid];
-    bool on = xi != 0.0f && (s.activation != 5 || xi < 20.0f);
-    xon[tid] = on ? xi : 0.0f;
+    xon[tid] = act_live(s, xi) ? xi : 0.0f;
   }
   LDS_BARRIER();
   for (int t = 0; t < D; t++) {
@@ -1513,10 +1504,8 @@ __global__ __launch_bounds__(1024) void k_bptt_small(View v, int r, int accumula
           e1 += w[q][k + 1] * hv[k + 1];
         }
         e += e1;
-        DPP_ADD(e, 0xB1);  /* quad_perm [1,0,3,2] */
-        DPP_ADD(e, 0x4E);  /* quad_perm [2,3,0,1] */
-        DPP_ADD(e, 0x141); /* row_half_mirror: the other quad of the eight */
-        if (s.activation == 2) e /= 2 * (xi + 1.0f);
+        e = dpp_row_all<3>(e, OpAdd{}); /* the eight lanes of a row, without LDS */
+        e = act_back_scale(s, xi, e);   /* (scaled before it is gated: xon holds the gated xi, zero for a skipped row) */
         e = (xi != 0.0f) ? e : 0.0f;
         if ((tid & 7) == 0) {
           en[y0 + 128 * q] = e;
@@ -1525,7 +1514,7 @@ __global__ __launch_bounds__(1024) void k_bptt_small(View v, int r, int accumula
       }
     }
     /* the wave's share of the sum of squares: its row leaders sit in lanes 0, 8, .., 56 */
-    DPP_ADD(sq, 0x128); /* row_ror 8: lanes 0 and 8 of every row of sixteen */
+    sq += RAMD_DPP(sq, 0x128); /* row_ror 8: lanes 0 and 8 of every row of sixteen */
     {
       const int sqi = __builtin_bit_cast(int, sq);
       float ws = __builtin_bit_cast(float, __builtin_amdgcn_readlane(sqi, 0)) +
@@ -1547,8 +1536,7 @@ __global__ __launch_bounds__(1024) void k_bptt_small(View v, int r, int accumula
     if (tid < 128) h[tid] = (tid == 0 || tid > hs) ? 0.0f : en[tid];
     if (tid < I && t + 1 < D) {
       const float xi = xall[(t + 1) * I + tid];
-      bool on = xi != 0.0f && (s.activation != 5 || xi < 20.0f);
-      xon[tid] = on ? xi : 0.0f;
+      xon[tid] = act_live(s, xi) ? xi : 0.0f;
     }
     if (tid == 0) {
       es_sh[t] = es;
@@ -1557,7 +1545,6 @@ __global__ __launch_bounds__(1024) void k_bptt_small(View v, int r, int accumula
     LDS_BARRIER();
     if (es <= min_error_sum || es > max_error_sum) break; /* the same for every thread */
   }
-#undef DPP_ADD
 #undef LDS_BARRIER
   if (wave == 0) {
     /* the steps that did not run left zeros, which end the scan of bptt_control_wave too */

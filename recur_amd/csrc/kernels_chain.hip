@@ -253,11 +253,7 @@ __global__ __launch_bounds__(512) void k_chain_main(const View *__restrict__ vp,
     for (int i = 0; i < 4; i++) {
       int n = n0 + c4 + i;
       if (n <= s.hidden_size) {
-        float ev = e[i];
-        float xi = xin[i];
-        bool on = xi != 0.0f && (s.activation != 5 || xi < 20.0f);
-        ev = on ? ev : 0.0f;
-        if (on && s.activation == 2) ev /= 2 * (xi + 1.0f);
+        const float ev = act_backward(s, xin[i], e[i]);
         dst[n] = ev;
         sq += ev * ev;
       }
@@ -423,11 +419,7 @@ __global__ __launch_bounds__(512) void k_chain_wide(const View *__restrict__ vp,
     float sq = 0.0f;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
-      float ev = e[i];
-      const float xi = xin[rr][i];
-      const bool on = xi != 0.0f && (s.activation != 5 || xi < 20.0f);
-      ev = on ? ev : 0.0f;
-      if (on && s.activation == 2) ev /= 2 * (xi + 1.0f);
+      const float ev = act_backward(s, xin[rr][i], e[i]);
       dst0[(size_t)row * s.I + i] = ev;
       sq += ev * ev;
     }

@@ -270,18 +270,7 @@ __global__ __launch_bounds__(256) void k_fwd_finalize(View v, int row0, int nrow
   }
   float h[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    float x = h[i];
-    if (s.activation == 2) { /* RNN_RESQRT */
-      x = (x > 0.0f) ? sqrtf(x + 1.0f) - 1.0f : 0.0f;
-    } else if (s.activation == 5) { /* RNN_RECLIP20 */
-      x = x < 20.0f ? x : 20.0f;
-      x = (x > 0.0f) ? x : 0.0f;
-    } else {
-      x = (x > 0.0f) ? x : 0.0f;
-    }
-    h[i] = x;
-  }
+  for (int i = 0; i < 4; i++) h[i] = act_forward(s, h[i]);
   if (c == 0) h[0] = 1.0f; /* the bias node, recur-nn.c:148 */
   *reinterpret_cast<float4 *>(v.b.hidden + (size_t)(row0 + j) * s.H + c) =
       make_float4(h[0], h[1], h[2], h[3]);
@@ -329,18 +318,7 @@ __global__ __launch_bounds__(256) void k_fwd_finalize_fused(View v, int row0, in
   }
   float h[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
-  for (int i = 0; i < 4; i++) {
-    float x = h[i];
-    if (s.activation == 2) { /* RNN_RESQRT */
-      x = (x > 0.0f) ? sqrtf(x + 1.0f) - 1.0f : 0.0f;
-    } else if (s.activation == 5) { /* RNN_RECLIP20 */
-      x = x < 20.0f ? x : 20.0f;
-      x = (x > 0.0f) ? x : 0.0f;
-    } else {
-      x = (x > 0.0f) ? x : 0.0f;
-    }
-    h[i] = x;
-  }
+  for (int i = 0; i < 4; i++) h[i] = act_forward(s, h[i]);
   if (c == 0) h[0] = 1.0f; /* the bias node, recur-nn.c:148 */
   *reinterpret_cast<float4 *>(v.b.hidden + (size_t)(row0 + j) * s.H + c) = make_float4(h[0], h[1], h[2], h[3]);
 }
@@ -992,14 +970,7 @@ __global__ __launch_bounds__(1024) void k_fwd_small(View v, int r) {
   if (tid < H) {
     float x = part[tid];
     for (int k = 1; k < G; k++) x += part[k * HC + tid];
-    if (s.activation == 2) {
-      x = (x > 0.0f) ? sqrtf(x + 1.0f) - 1.0f : 0.0f;
-    } else if (s.activation == 5) {
-      x = x < 20.0f ? x : 20.0f;
-      x = (x > 0.0f) ? x : 0.0f;
-    } else {
-      x = (x > 0.0f) ? x : 0.0f;
-    }
+    x = act_forward(s, x);
     if (tid == 0) x = 1.0f; /* the bias node, recur-nn.c:148 */
     hid[tid] = x;
     hsh[tid] = x;

@@ -33,51 +33,28 @@ __global__ __launch_bounds__(64) void k_softmax_error(View v, int row0, int nrow
   float *err = v.b.o_error + (size_t)r * s.O;
   int len = s.output_size;
   // max and min are order independent: one pass over the lanes
-  float lo = src[0], hi = src[0];
-  for (int i = threadIdx.x; i < len; i += 64) {
-    hi = fmaxf(hi, src[i]);
-    lo = fminf(lo, src[i]);
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    lo = fminf(lo, __shfl_xor(lo, off, 64));
-  }
-  float adj = 0.0f;
-  if (hi > 50.0f) adj = 50.0f - hi;
-  else if (lo < -60.0f) adj = fminf(-60.0f - lo, 50.0f - hi);
-  // the exponentials in parallel, their sum in the reference's order (lane 0)
+  const float adj = softmax_shift_of(src, len, threadIdx.x);
+  // the exponentials in parallel, their sum in the reference's order
   for (int i = threadIdx.x; i < len; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
   __syncthreads();
   // every lane adds the exponentials in the reference's order (the same value in all of
   // them); the divisions and the arg max (first of equal maxima, badmaths.h:126-139) are
   // spread over the lanes
-  float sum = 0.0f;
-  for (int i = 0; i < len; i++) sum += ex[i];
-  float best_e = -1.0f;
-  int best_i = 0x7fffffff;
+  const float sum = ordered_sum(ex, len);
+  BestGuess best;
   const int target = v.b.target[r];
   for (int i = threadIdx.x; i < len; i += 64) {
     float e = ex[i] / sum;
-    err[i] = (i == target) ? -e + 1.0f : -e; /* error[next] += 1.0f, charmodel-predict.c:25 */
-    if (e > best_e) {
-      best_e = e;
-      best_i = i;
-    }
+    err[i] = softmax_error(e, i == target);
+    best.offer(e, i);
   }
-  for (int off = 32; off > 0; off >>= 1) {
-    float oe = __shfl_xor(best_e, off, 64);
-    int oi = __shfl_xor(best_i, off, 64);
-    if (oe > best_e || (oe == best_e && oi < best_i)) {
-      best_e = oe;
-      best_i = oi;
-    }
-  }
+  wave_best_guess(best);
   if (threadIdx.x != 0) return;
-  float e = -(ex[target] / sum) + 1.0f;
+  float e = softmax_error(ex[target] / sum, true);
   float l = 1.0f - e;
   v.b.stat_err[r] += e;
-  v.b.stat_ent[r] += (l < 1e-30f) ? -100.0f : log2f(l); /* charmodel-helpers.h:11-13 */
-  v.b.stat_correct[r] += (best_i == target);
+  v.b.stat_ent[r] += capped_log2f_dev(l);
+  v.b.stat_correct[r] += (best.i == target);
   v.b.stat_count[r] += 1;
   v.b.stat_zero[r] += zeros / (double)s.hidden_size;
 }
@@ -117,7 +94,6 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
   float *sout = part + OUT_SEGS * 64 * 4 + OUT_SEGS * s.O; /* [O] outputs (behind the waves' column sums [OUT_SEGS][O]) */
   float *sex = sout + s.O;             /* [O] exponentials                   */
   float *serr = sex + s.O;             /* [O] output error                   */
-  float *hid = v.b.hidden + (size_t)r * s.H;
   const int seg = threadIdx.x >> 6, lane = threadIdx.x & 63;
   TT_STAMP(0);
   BND_MARK(g_bnd_top, 0);
@@ -142,63 +118,7 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
     pad_oe = v.b.o_error[(size_t)r * s.O + pi];
     if constexpr (KIND == 1) mse_target = lane < tl.n ? tl.targets[(size_t)blockIdx.x * tl.ld + lane] : 0.0f;
   }
-  if (fwd_ks != 0) {
-    // the forward GEMM's K slabs are still in the workspace: sum them, apply the
-    // activation and write the hidden row here (what k_fwd_finalize does, recur-nn.c:123-148).
-    // fwd_ks < 0: k_fwd_fused left one plane of sums and, for the h_size padding columns,
-    // -fwd_ks per-tile partial sums in plane 1.
-    const float *p = v.b.slab + (size_t)blockIdx.x * s.H;
-    const int npart = fwd_ks < 0 ? -fwd_ks : 0;
-    if (fwd_ks < 0) fwd_ks = 1;
-    for (int i = threadIdx.x; i < s.H; i += 1024) {
-      /* all the slabs' loads in flight at once (a loop with a run-time trip count issues
-       * them one L2 latency after another) */
-      const size_t plane = (size_t)nrows * s.H;
-      float xs[8];
-#pragma unroll
-      for (int z = 0; z < 8; z++) xs[z] = (z < fwd_ks) ? p[z * plane + i] : 0.0f;
-      float x = xs[0];
-#pragma unroll
-      for (int z = 1; z < 8; z++)
-        if (z < fwd_ks) x += xs[z];
-      for (int z = 8; z < fwd_ks; z++) x += p[z * plane + i];
-      if (npart && i >= s.H - 4) continue; /* the tail columns: below */
-      if (s.activation == 2) {
-        x = (x > 0.0f) ? sqrtf(x + 1.0f) - 1.0f : 0.0f;
-      } else if (s.activation == 5) {
-        x = x < 20.0f ? x : 20.0f;
-        x = (x > 0.0f) ? x : 0.0f;
-      } else {
-        x = (x > 0.0f) ? x : 0.0f;
-      }
-      if (i == 0) x = 1.0f; /* the bias node, recur-nn.c:148 */
-      hid[i] = x;
-      shid[i] = x;
-    }
-    if (npart && threadIdx.x < 256) {
-      /* k_fwd_fused's four tail columns (hidden value hidden_size and the padding of h_size):
-       * wave p adds column p's per-tile partial sums */
-      const int p4 = threadIdx.x >> 6, ln = threadIdx.x & 63;
-      const float *pd = v.b.slab + (size_t)nrows * s.H + (size_t)blockIdx.x * 4 + p4;
-      float x = 0.0f;
-      for (int t = ln; t < npart; t += 64) x += pd[(size_t)t * nrows * 4];
-      for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-      if (s.activation == 2) {
-        x = (x > 0.0f) ? sqrtf(x + 1.0f) - 1.0f : 0.0f;
-      } else if (s.activation == 5) {
-        x = x < 20.0f ? x : 20.0f;
-        x = (x > 0.0f) ? x : 0.0f;
-      } else {
-        x = (x > 0.0f) ? x : 0.0f;
-      }
-      if (ln == 0) {
-        hid[s.H - 4 + p4] = x;
-        shid[s.H - 4 + p4] = x;
-      }
-    }
-  } else {
-    for (int i = threadIdx.x; i < s.H; i += 1024) shid[i] = hid[i];
-  }
+  top_hidden_row(v, r, nrows, fwd_ks, shid, WaveSumShfl{});
   __syncthreads();
   TT_STAMP(1);
   // ---- output layer (recur-nn.c:150-151)
@@ -318,13 +238,7 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
     if (seg == 0) text_softmax_wave(s, lane, shid, sout, sex, serr, v.b.o_error + (size_t)r * s.O, target, pad_oe, tstat);
     else if (seg == 1) text_count_zeros_wave(s, lane, shid, tstat);
     __syncthreads();
-    if (threadIdx.x == 64) { /* (its loads return before the wave's backprop loads, which are issued behind them) */
-      v.b.stat_err[r] += tstat[0];
-      v.b.stat_ent[r] += tstat[1];
-      v.b.stat_correct[r] += (tstat[2] != 0.0f);
-      v.b.stat_count[r] += 1;
-      v.b.stat_zero[r] += (int)tstat[3] / (double)s.hidden_size;
-    }
+    if (threadIdx.x == 64) top_add_stats(v, r, tstat); /* (its loads return before the wave's backprop loads, which are issued behind them) */
   } else if constexpr (KIND == 1) { // k_sigmoid_mse_error: sigmoid in place on the first n outputs, slope * (target - answer)
     if (seg == 0 && lane < s.O) { /* (o_size <= 64: launcher) */
       float oe = pad_oe; /* the rest of the error row stays what it was */
@@ -343,54 +257,10 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
     if (seg == 0) {
       float *err = v.b.o_error + (size_t)r * s.O;
       if (lane < s.O) serr[lane] = pad_oe; /* (o_size <= 64: launcher) columns outside every group stay what they were */
-      int trained = 0, wins = 0;
-      float wrong = 0.0f;
-      for (int i = 0; i < tl.ngroups; i++) {
-        const int o = tl.goff[i], n = tl.gsize[i], tg = tl.gt[(size_t)blockIdx.x * tl.ngroups + i];
-        if (tg < 0 || tg >= n) {
-          for (int q = lane; q < n; q += 64) serr[o + q] = 0.0f;
-          continue;
-        }
-        const float *gs = sout + o;
-        float lo = gs[0], hi = gs[0];
-        for (int q = lane; q < n; q += 64) {
-          hi = fmaxf(hi, gs[q]);
-          lo = fminf(lo, gs[q]);
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-          hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-          lo = fminf(lo, __shfl_xor(lo, off, 64));
-        }
-        float adj = 0.0f;
-        if (hi > 50.0f) adj = 50.0f - hi;
-        else if (lo < -60.0f) adj = fminf(-60.0f - lo, 50.0f - hi);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* (one wave: the last group's reads of sex are over) */
-        for (int q = lane; q < n; q += 64) sex[q] = fast_expf_dev(gs[q] + adj);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* one wave: its LDS writes are ordered */
-        float sum = 0.0f;
-        for (int q = 0; q < n; q++) sum += sex[q];
-        float best_e = -1.0f;
-        int best_i = 0x7fffffff;
-        for (int q = lane; q < n; q += 64) {
-          float e = sex[q] / sum;
-          serr[o + q] = (q == tg) ? -e + 1.0f : -e;
-          if (e > best_e) {
-            best_e = e;
-            best_i = q;
-          }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-          float oe = __shfl_xor(best_e, off, 64);
-          int oi = __shfl_xor(best_i, off, 64);
-          if (oe > best_e || (oe == best_e && oi < best_i)) {
-            best_e = oe;
-            best_i = oi;
-          }
-        }
-        wins += (best_i == tg);
-        wrong += -(sex[tg] / sum) + 1.0f;
-        trained++;
-      }
+      int wins;
+      float wrong;
+      const int trained = grouped_softmax_wave(lane, tl.ngroups, tl.goff, tl.gsize, tl.gt + (size_t)blockIdx.x * tl.ngroups,
+                                               sout, sex, serr, FenceOneWave{}, wins, wrong);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (lane < s.O) {
         float oe = serr[lane];
@@ -447,23 +317,11 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
   if (lane == 0) tred[seg] = sum;
   __syncthreads();
   TT_STAMP(4);
-  /* the same tree as block_sum_256 within each group of four waves, then the four groups */
-  float g0 = (tred[0] + tred[1]) + (tred[2] + tred[3]), g1 = (tred[4] + tred[5]) + (tred[6] + tred[7]);
-  float g2 = (tred[8] + tred[9]) + (tred[10] + tred[11]), g3 = (tred[12] + tred[13]) + (tred[14] + tred[15]);
-  sum = (g0 + g1) + (g2 + g3);
-  float halfmax = s.H * MAX_TOP_ERROR_FACTOR_F;
-  float scaled = sum, scale = 1.0f;
-  if (sum > halfmax) {
-    scale = soft_clip_dev(sum, halfmax);
-    scaled = scale * sum;
-  }
+  float scale;
+  const bool clipped = top_soft_clip(v, r, tred, scale);
   float *dst = v.b.ehi + (size_t)r * s.I; /* step 0 plane */
   for (int q = 0, y = threadIdx.x; y < s.H; y += 1024, q++)
-    dst[y] = (y == 0 || y > s.hidden_size) ? 0.0f : (sum > halfmax) ? ev[q] * scale : ev[q];
-  if (threadIdx.x == 0) {
-    v.b.top_raw[r] = sum;
-    v.b.top_scaled[r] = scaled;
-  }
+    dst[y] = (y == 0 || y > s.hidden_size) ? 0.0f : clipped ? ev[q] * scale : ev[q];
   TT_STAMP(5);
   BND_MARK(g_bnd_top, 1);
 }
@@ -487,15 +345,8 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
 // 25.7 against 11.0 with one).
 // Text loss only (KIND 0), o_size <= 64, a wave's rows in one batch (h_size <= 1088): else k_text_top.
 constexpr int T2_NB = 17;
-#define T2_DPP(x, ctrl) __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, x), ctrl, 0xf, 0xf, true))
 #define T2_SWZ(x, xorm) __builtin_bit_cast(float, __builtin_amdgcn_ds_swizzle(__builtin_bit_cast(int, x), ((xorm) << 10) | 0x1f))
-__device__ __forceinline__ float dpp_row_sum16(float x) {
-  x += T2_DPP(x, 0xB1);  /* quad_perm [1, 0, 3, 2] */
-  x += T2_DPP(x, 0x4E);  /* quad_perm [2, 3, 0, 1] */
-  x += T2_DPP(x, 0x141); /* row_half_mirror */
-  x += T2_DPP(x, 0x140); /* row_mirror */
-  return x;
-}
+__device__ __forceinline__ float dpp_row_sum16(float x) { return dpp_row_all(x, OpAdd{}); }
 /* p[k]: this lane's partial sum of row k (k = 0 .. 15) of its sixteen-lane group; returns the group's sum of row c4 (the
  * lane's number in the group): a butterfly that halves the rows a lane still carries at every exchange */
 __device__ __forceinline__ float transpose_sum16(const float (&p)[16], int c4) {
@@ -514,23 +365,10 @@ __device__ __forceinline__ float transpose_sum16(const float (&p)[16], int c4) {
 #pragma unroll
   for (int k = 0; k < 2; k++) {
     const float keep = b1 ? w[k + 2] : w[k], send = b1 ? w[k] : w[k + 2];
-    x[k] = keep + T2_DPP(send, 0x4E);
+    x[k] = keep + RAMD_DPP(send, 0x4E);
   }
   const float keep = b0 ? x[1] : x[0], send = b0 ? x[0] : x[1];
-  return keep + T2_DPP(send, 0xB1);
-}
-/* a wave-wide max / min / sum that every lane gets, without the LDS crossbar: a butterfly over the sixteen lanes of a row in
- * four DPP steps, then the four rows' values through scalar registers (v_readlane) -- ~12 instructions of a few cycles each
- * where six __shfl_xor steps are six dependent ds_bpermute round trips (the one-wave softmax was 1.6 us of the launch) */
-template <class OP> __device__ __forceinline__ float wave_all(float x, OP op) {
-  x = op(x, T2_DPP(x, 0xB1));
-  x = op(x, T2_DPP(x, 0x4E));
-  x = op(x, T2_DPP(x, 0x141));
-  x = op(x, T2_DPP(x, 0x140));
-  const int xi = __builtin_bit_cast(int, x);
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 0)), r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 32)), r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(xi, 48));
-  return op(op(r0, r1), op(r2, r3));
+  return keep + RAMD_DPP(send, 0xB1);
 }
 /* text_softmax_wave (k_top.h) for o_size <= 64 without LDS round trips: lane i holds output i.  The same arithmetic value
  * by value (adjustment, fast_expf_dev, the division, +1 on the target, best guess with the lowest index on a tie); the sum
@@ -542,31 +380,22 @@ __device__ __forceinline__ void text_softmax_regs(const RamdShape &s, int lane, 
   const int len = s.output_size;
   const bool in = lane < len;
   const float o = sout[in ? lane : 0];
-  const float hi = wave_all(o, [](float a, float b) { return fmaxf(a, b); }); /* (a lane past the outputs holds output 0) */
-  const float lo = wave_all(o, [](float a, float b) { return fminf(a, b); });
-  float adj = 0.0f;
-  if (hi > 50.0f) adj = 50.0f - hi;
-  else if (lo < -60.0f) adj = fminf(-60.0f - lo, 50.0f - hi);
+  const float hi = wave_all(o, OpMax{}), lo = wave_all(o, OpMin{}); /* (a lane past the outputs holds output 0) */
+  const float adj = softmax_shift(lo, hi);
   const float ex = in ? fast_expf_dev(o + adj) : 0.0f;
-  const float sum = wave_all(ex, [](float a, float b) { return a + b; });
+  const float sum = wave_all(ex, OpAdd{}); /* (a tree, not the index order of ordered_sum) */
   const float e = ex / sum;
   /* the best guess: the largest e, the lowest index on a tie (badmaths.h:113-141) -- the first lane that holds the maximum */
-  const float emax = wave_all(in ? e : -1.0f, [](float a, float b) { return fmaxf(a, b); });
+  const float emax = wave_all(in ? e : -1.0f, OpMax{});
   const unsigned long long at = __ballot(in && e == emax);
   const int best_i = at ? __ffsll((long long)at) - 1 : 0x7fffffff;
   if (lane < s.O) {
-    const float oe = in ? ((lane == target) ? -e + 1.0f : -e) : pad_oe; /* the pad of o_error stays what it was (zero) */
+    const float oe = in ? softmax_error(e, lane == target) : pad_oe; /* the pad of o_error stays what it was (zero) */
     if (in) err[lane] = oe;
     serr[lane] = oe;
   }
   const float et = __shfl(e, target, 64);
-  if (lane == 0) {
-    const float e1 = -et + 1.0f;
-    const float l = 1.0f - e1;
-    tstat[0] = e1;
-    tstat[1] = (l < 1e-30f) ? -100.0f : log2f(l);
-    tstat[2] = (best_i == target) ? 1.0f : 0.0f;
-  }
+  if (lane == 0) text_stat_store(softmax_error(et, true), best_i == target, tstat);
 }
 __global__ __launch_bounds__(1024) void k_text_top2(View v, int row0, int nrows, int fwd_ks) {
   extern __shared__ float tsh[];
@@ -603,57 +432,8 @@ __global__ __launch_bounds__(1024) void k_text_top2(View v, int row0, int nrows,
     target = v.b.target[r];
     pad_oe = v.b.o_error[(size_t)r * s.O + (lane < s.O ? lane : 0)];
   }
-  // ---- 2. the hidden row (k_text_top's first phase)
-  float *hid = v.b.hidden + (size_t)r * s.H;
-  if (fwd_ks != 0) {
-    const float *p = v.b.slab + (size_t)j * s.H;
-    const int npart = fwd_ks < 0 ? -fwd_ks : 0;
-    if (fwd_ks < 0) fwd_ks = 1;
-    const size_t plane = (size_t)nrows * s.H;
-    for (int i = threadIdx.x; i < s.H; i += 1024) {
-      float xs[8];
-#pragma unroll
-      for (int z = 0; z < 8; z++) xs[z] = (z < fwd_ks) ? p[z * plane + i] : 0.0f;
-      float x = xs[0];
-#pragma unroll
-      for (int z = 1; z < 8; z++)
-        if (z < fwd_ks) x += xs[z];
-      for (int z = 8; z < fwd_ks; z++) x += p[z * plane + i];
-      if (npart && i >= s.H - 4) continue; /* the tail columns: below */
-      if (s.activation == 2) {
-        x = (x > 0.0f) ? sqrtf(x + 1.0f) - 1.0f : 0.0f;
-      } else if (s.activation == 5) {
-        x = x < 20.0f ? x : 20.0f;
-        x = (x > 0.0f) ? x : 0.0f;
-      } else {
-        x = (x > 0.0f) ? x : 0.0f;
-      }
-      if (i == 0) x = 1.0f; /* the bias node, recur-nn.c:148 */
-      hid[i] = x;
-      shid[i] = x;
-    }
-    if (npart && seg < 4) { /* k_fwd_fused's four tail columns: wave p4 adds column p4's per-tile partial sums */
-      const int p4 = seg;
-      const float *pd = v.b.slab + (size_t)nrows * s.H + (size_t)j * 4 + p4;
-      float x = 0.0f;
-      for (int t = lane; t < npart; t += 64) x += pd[(size_t)t * nrows * 4];
-      x = wave_sum_all(x);
-      if (s.activation == 2) {
-        x = (x > 0.0f) ? sqrtf(x + 1.0f) - 1.0f : 0.0f;
-      } else if (s.activation == 5) {
-        x = x < 20.0f ? x : 20.0f;
-        x = (x > 0.0f) ? x : 0.0f;
-      } else {
-        x = (x > 0.0f) ? x : 0.0f;
-      }
-      if (lane == 0) {
-        hid[s.H - 4 + p4] = x;
-        shid[s.H - 4 + p4] = x;
-      }
-    }
-  } else {
-    for (int i = threadIdx.x; i < s.H; i += 1024) shid[i] = hid[i];
-  }
+  // ---- 2. the hidden row
+  top_hidden_row(v, r, nrows, fwd_ks, shid, WaveSumDpp{});
   __syncthreads();
   TT_STAMP(1);
   // ---- 3. output layer (recur-nn.c:150-151): the lane's rows, then the four row groups of the wave, then the waves
@@ -698,13 +478,7 @@ __global__ __launch_bounds__(1024) void k_text_top2(View v, int row0, int nrows,
   }
   __syncthreads();
   TT_STAMP(3);
-  if (threadIdx.x == 128) {
-    v.b.stat_err[r] += tstat[0];
-    v.b.stat_ent[r] += tstat[1];
-    v.b.stat_correct[r] += (tstat[2] != 0.0f);
-    v.b.stat_count[r] += 1;
-    v.b.stat_zero[r] += (int)tstat[3] / (double)s.hidden_size;
-  }
+  if (threadIdx.x == 128) top_add_stats(v, r, tstat);
   // ---- 5. top-layer backprop + soft clip (recur-nn.c:199-228, 719-721) from the rows in registers
   const float4 se = colq ? *reinterpret_cast<const float4 *>(serr + 4 * c4) : zero4();
   float pr[16];
@@ -722,27 +496,15 @@ __global__ __launch_bounds__(1024) void k_text_top2(View v, int row0, int nrows,
   float *dst = v.b.ehi + (size_t)r * s.I; /* step 0 plane */
   if (rowa) dst[ya] = (ya == 0 || ya > s.hidden_size) ? 0.0f : ea;
   if (rowb) dst[yb] = (yb == 0 || yb > s.hidden_size) ? 0.0f : eb;
-  float sum = wave_all(fabsf(ea) + fabsf(eb), [](float a, float b) { return a + b; });
+  const float sum = wave_all(fabsf(ea) + fabsf(eb), OpAdd{});
   if (lane == 0) tred[seg] = sum;
   TT_STAMP(6);
   __syncthreads();
   TT_STAMP(4);
-  {
-    const float g0 = (tred[0] + tred[1]) + (tred[2] + tred[3]), g1 = (tred[4] + tred[5]) + (tred[6] + tred[7]);
-    const float g2 = (tred[8] + tred[9]) + (tred[10] + tred[11]), g3 = (tred[12] + tred[13]) + (tred[14] + tred[15]);
-    sum = (g0 + g1) + (g2 + g3);
-  }
-  const float halfmax = s.H * MAX_TOP_ERROR_FACTOR_F;
-  float scaled = sum;
-  if (sum > halfmax) { /* rare (a hot net): the row once more, scaled */
-    const float scale = soft_clip_dev(sum, halfmax);
-    scaled = scale * sum;
+  float scale;
+  if (top_soft_clip(v, r, tred, scale)) { /* rare (a hot net): the row once more, scaled */
     if (rowa) dst[ya] = (ya == 0 || ya > s.hidden_size) ? 0.0f : ea * scale;
     if (rowb) dst[yb] = (yb == 0 || yb > s.hidden_size) ? 0.0f : eb * scale;
-  }
-  if (threadIdx.x == 0) {
-    v.b.top_raw[r] = sum;
-    v.b.top_scaled[r] = scaled;
   }
   TT_STAMP(5);
   BND_MARK(g_bnd_top, 1);
@@ -825,67 +587,34 @@ __global__ __launch_bounds__(64 * MS_WAVES) void k_multi_softmax_error(View v, i
       const bool in0 = lane < alen, in1 = lane + 64 < alen;
       const float g0 = gs[in0 ? lane : 0], g1 = gs[in1 ? lane + 64 : 0];
       float hi = fmaxf(g0, g1), lo = fminf(g0, g1); /* (a lane without a value holds gs[0]) */
-      for (int off = 32; off > 0; off >>= 1) {
-        hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-        lo = fminf(lo, __shfl_xor(lo, off, 64));
-      }
-      float adj = 0.0f;
-      if (hi > 50.0f) adj = 50.0f - hi;
-      else if (lo < -60.0f) adj = fminf(-60.0f - lo, 50.0f - hi);
+      wave_minmax(lo, hi);
+      const float adj = softmax_shift(lo, hi);
       const float e0 = fast_expf_dev(g0 + adj), e1 = fast_expf_dev(g1 + adj);
       if (in0) ex[lane] = e0;
       if (in1) ex[lane + 64] = e1;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* one wave: its LDS writes are ordered */
-      /* the exponentials in index order, four float4 reads in flight instead of a read per addition */
-      float sum = 0.0f;
-      for (int i0 = 0; 4 * i0 < alen; i0 += 4) {
-        float4 q[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) q[i] = *reinterpret_cast<const float4 *>(ex + 4 * (4 * (i0 + i) < alenp ? i0 + i : 0));
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-          if (4 * (i0 + i) + 0 < alen) sum += q[i].x;
-          if (4 * (i0 + i) + 1 < alen) sum += q[i].y;
-          if (4 * (i0 + i) + 2 < alen) sum += q[i].z;
-          if (4 * (i0 + i) + 3 < alen) sum += q[i].w;
-        }
-      }
+      FenceOneWave{}();
+      const float sum = ordered_sum4(ex, alen, alenp); /* (as single reads in a loop the sum was the larger part of a head) */
       const float q0 = e0 / sum, q1 = e1 / sum;
-      if (in0) err[offset + lane] = (lane == next) ? -q0 + 1.0f : -q0;
-      if (in1) err[offset + lane + 64] = (lane + 64 == next) ? -q1 + 1.0f : -q1;
-      if (c == own && lane == 0) own_err_sh = -(ex[next] / sum) + 1.0f;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* before this wave's next head rewrites ex */
+      if (in0) err[offset + lane] = softmax_error(q0, lane == next);
+      if (in1) err[offset + lane + 64] = softmax_error(q1, lane + 64 == next);
+      if (c == own && lane == 0) own_err_sh = softmax_error(ex[next] / sum, true);
+      FenceOneWave{}(); /* before this wave's next head rewrites ex */
       continue;
     }
-    float lo = gs[0], hi = gs[0];
-    for (int i = lane; i < alen; i += 64) {
-      hi = fmaxf(hi, gs[i]);
-      lo = fminf(lo, gs[i]);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-      lo = fminf(lo, __shfl_xor(lo, off, 64));
-    }
-    float adj = 0.0f;
-    if (hi > 50.0f) adj = 50.0f - hi;
-    else if (lo < -60.0f) adj = fminf(-60.0f - lo, 50.0f - hi);
+    const float adj = softmax_shift_of(gs, alen, lane);
     for (int i = lane; i < alen; i += 64) ex[i] = fast_expf_dev(gs[i] + adj);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* one wave: its LDS writes are ordered */
-    float sum = 0.0f;
-    for (int i = 0; i < alen; i++) sum += ex[i];
-    for (int i = lane; i < alen; i += 64) {
-      float e = ex[i] / sum;
-      err[offset + i] = (i == next) ? -e + 1.0f : -e;
-    }
-    if (c == own && lane == 0) own_err_sh = -(ex[next] / sum) + 1.0f;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* before this wave's next head rewrites ex */
+    FenceOneWave{}();
+    const float sum = ordered_sum(ex, alen);
+    for (int i = lane; i < alen; i += 64) err[offset + i] = softmax_error(ex[i] / sum, i == next);
+    if (c == own && lane == 0) own_err_sh = softmax_error(ex[next] / sum, true);
+    FenceOneWave{}(); /* before this wave's next head rewrites ex */
   }
   __syncthreads();
   if (threadIdx.x == 0) {
     const float own_err = own_err_sh;
     float l = 1.0f - own_err;
     v.b.stat_err[r] += own_err;
-    v.b.stat_ent[r] += (l < 1e-30f) ? -100.0f : log2f(l);
+    v.b.stat_ent[r] += capped_log2f_dev(l);
     v.b.stat_count[r] += 1;
   }
 }
@@ -904,54 +633,9 @@ __global__ __launch_bounds__(64) void k_grouped_softmax_error(View v, int row0, 
   const int j = blockIdx.x, r = row0 + j, lane = threadIdx.x;
   const float *src = v.b.out + (size_t)r * s.O;
   float *err = v.b.o_error + (size_t)r * s.O;
-  int trained = 0, wins = 0;
-  float wrong = 0.0f;
-  for (int i = 0; i < ngroups; i++) {
-    const int o = goff[i], n = gsize[i], target = gt[(size_t)j * ngroups + i];
-    if (target < 0 || target >= n) {
-      for (int q = lane; q < n; q += 64) err[o + q] = 0.0f;
-      continue;
-    }
-    const float *gs = src + o;
-    float lo = gs[0], hi = gs[0];
-    for (int q = lane; q < n; q += 64) {
-      hi = fmaxf(hi, gs[q]);
-      lo = fminf(lo, gs[q]);
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-      lo = fminf(lo, __shfl_xor(lo, off, 64));
-    }
-    float adj = 0.0f;
-    if (hi > 50.0f) adj = 50.0f - hi;
-    else if (lo < -60.0f) adj = fminf(-60.0f - lo, 50.0f - hi);
-    __syncthreads();
-    for (int q = lane; q < n; q += 64) ex[q] = fast_expf_dev(gs[q] + adj);
-    __syncthreads();
-    float sum = 0.0f;
-    for (int q = 0; q < n; q++) sum += ex[q];
-    float best_e = -1.0f;
-    int best_i = 0x7fffffff;
-    for (int q = lane; q < n; q += 64) {
-      float e = ex[q] / sum;
-      err[o + q] = (q == target) ? -e + 1.0f : -e;
-      if (e > best_e) {
-        best_e = e;
-        best_i = q;
-      }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      float oe = __shfl_xor(best_e, off, 64);
-      int oi = __shfl_xor(best_i, off, 64);
-      if (oe > best_e || (oe == best_e && oi < best_i)) {
-        best_e = oe;
-        best_i = oi;
-      }
-    }
-    wins += (best_i == target);
-    wrong += -(ex[target] / sum) + 1.0f;
-    trained++;
-  }
+  int wins;
+  float wrong;
+  const int trained = grouped_softmax_wave(lane, ngroups, goff, gsize, gt + (size_t)j * ngroups, src, ex, err, FenceBlock{}, wins, wrong);
   if (trained && weight) {
     __syncthreads(); /* one wave: its own stores are ordered; this keeps the compiler honest */
     for (int q = lane; q < s.output_size; q += 64) err[q] *= weight[q];
@@ -971,25 +655,12 @@ __global__ __launch_bounds__(64) void k_xent_accumulate(View v, int r, int count
   const RamdShape &s = v.sh;
   const float *src = v.b.out + (size_t)r * s.O;
   int len = s.output_size;
-  float lo = src[0], hi = src[0];
-  for (int i = threadIdx.x; i < len; i += 64) {
-    hi = fmaxf(hi, src[i]);
-    lo = fminf(lo, src[i]);
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    lo = fminf(lo, __shfl_xor(lo, off, 64));
-  }
-  float adj = 0.0f;
-  if (hi > 50.0f) adj = 50.0f - hi;
-  else if (lo < -60.0f) adj = fminf(-60.0f - lo, 50.0f - hi);
+  const float adj = softmax_shift_of(src, len, threadIdx.x);
   for (int i = threadIdx.x; i < len; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
   __syncthreads();
   if (threadIdx.x != 0 || !count_it) return;
-  float sum = 0.0f;
-  for (int i = 0; i < len; i++) sum += ex[i];
-  float e = ex[v.b.target[r]] / sum;
-  v.b.xent[r] += (double)((e < 1e-30f) ? -100.0f : log2f(e));
+  float e = ex[v.b.target[r]] / ordered_sum(ex, len);
+  v.b.xent[r] += (double)capped_log2f_dev(e);
 }
 
 // rnn_char_multi_cross_entropy's inner step (charmodel-multi-predict.c:395-403): block c
@@ -1001,25 +672,12 @@ __global__ __launch_bounds__(64) void k_multi_xent_accumulate(View v, int r, int
   const RamdShape &s = v.sh;
   const int c = blockIdx.x;
   const float *src = v.b.out + (size_t)r * s.O + (size_t)c * alen;
-  float lo = src[0], hi = src[0];
-  for (int i = threadIdx.x; i < alen; i += 64) {
-    hi = fmaxf(hi, src[i]);
-    lo = fminf(lo, src[i]);
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-    lo = fminf(lo, __shfl_xor(lo, off, 64));
-  }
-  float adj = 0.0f;
-  if (hi > 50.0f) adj = 50.0f - hi;
-  else if (lo < -60.0f) adj = fminf(-60.0f - lo, 50.0f - hi);
+  const float adj = softmax_shift_of(src, alen, threadIdx.x);
   for (int i = threadIdx.x; i < alen; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
   __syncthreads();
   if (threadIdx.x != 0 || !count_it) return;
-  float sum = 0.0f;
-  for (int i = 0; i < alen; i++) sum += ex[i];
-  float e = ex[v.b.target[r]] / sum;
-  acc[c] += (double)((e < 1e-30f) ? -100.0f : log2f(e));
+  float e = ex[v.b.target[r]] / ordered_sum(ex, alen);
+  acc[c] += (double)capped_log2f_dev(e);
 }
 
 // rnnca's loss (gstrnnca.c:701-714, train_net): fast_sigmoid_array(answer, answer, n) IN

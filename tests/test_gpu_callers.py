@@ -107,11 +107,13 @@ def test_text_step_with_adagrad_in_the_delta_gemms_epilogue(amd):
 
 
 @pytest.mark.parametrize("A,NC,H,S,D,leakage", [(128, 11, 256, 40, 6, 0.3), (24, 64, 512, 300, 5, 0.05),
-                                                 (100, 3, 128, 7, 4, 0.9), (31, 20, 256, 64, 6, 0.2)])
+                                                 (100, 3, 128, 7, 4, 0.9), (31, 20, 256, 64, 6, 0.2),
+                                                 (130, 3, 128, 7, 4, 0.9)])
 def test_multi_head_generation_with_other_head_shapes(amd, A, NC, H, S, D, leakage):
     """The per-head top-layer kernels at their limits: the widest head (128 symbols), the narrowest they take (24)
     with the most heads (64) and more than 256 streams (two passes of the stream lists), three heads that nearly
-    every stream trains all of (leakage 0.9), 31-symbol heads (never aligned to a float4)."""
+    every stream trains all of (leakage 0.9), 31-symbol heads (never aligned to a float4), 130-symbol heads (past the
+    128 that a wave holds in registers: the loss kernel's strided form)."""
     _multi_head_generation(amd, A, NC, H, S, D, leakage)
 
 
