@@ -21,6 +21,7 @@
 #include <stdlib.h>
 #include <math.h>
 #include "ramd_internal.h"
+#include "k_tiles.h"
 
 #define HIP_CHECK(x)                                                              \
   do {                                                                            \
@@ -47,6 +48,13 @@ static inline void ramd_check_launch(const char *file, int line) {
     hipLaunchKernelGGL(__VA_ARGS__);           \
     ramd_check_launch(__FILE__, __LINE__);     \
   } while (0)
+// A kernel that takes more than 64 KB of dynamic LDS has its limit raised before its first launch, once.
+template <auto KERNEL> static void raise_lds_limit(int bytes) {
+  static bool done = false;
+  if (done) return;
+  HIP_CHECK(hipFuncSetAttribute((const void *)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  done = true;
+}
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -281,7 +289,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) void lds_void_t;
 typedef const __attribute__((address_space(1))) void glb_void_t;
 
-constexpr int CM = 32, CN = 32, CK = 128;
 constexpr int C_STAGES = 3;                    /* LDS ring: 2 stages in flight + 1 being read (a 4th buys nothing) */
 constexpr int C_STAGE_FLOATS = (CM + CN) * CK; /* 32 KB */
 

@@ -37,6 +37,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <utility>
+#include "k_tiles.h"
 
 typedef float dd_f4 __attribute__((ext_vector_type(4)));
 typedef float dd_f4u __attribute__((ext_vector_type(4), aligned(4)));
@@ -93,7 +94,6 @@ template <bool COLD = false> __device__ __forceinline__ float dd_load1(const voi
   return r;
 }
 typedef int dd_i4 __attribute__((ext_vector_type(4)));
-constexpr int DD_FLAG_LOADS = 8; /* 4 x 256 streams of n_exec, of ih_scale */
 __device__ __forceinline__ dd_i4 dd_load4i(const void *sbase, unsigned voff) {
   dd_i4 r;
   asm volatile("s_nop 4\n\tglobal_load_dwordx4 %0, %1, %2" : "=v"(r) : "v"(voff), "s"(sbase) : "memory");

@@ -32,8 +32,7 @@
 // range, different m tile) are given ids with equal L % 8 and therefore meet in
 // one XCD's L2 (MI355X_MICROARCH.md "Workgroup dispatch"; speed only).
 
-constexpr int BM = 64, BN = 64, BK = 32, LDK = BK + 4;
-constexpr int RAMD_MAX_REST_PLANES = 64;
+constexpr int LDK = BK + 4; /* (BM, BN, BK: k_tiles.h) */
 
 struct GemmOut {
   float *slab;   // [KS][M][ldc]
@@ -214,7 +213,7 @@ __global__ __launch_bounds__(256) void k_gemm_pair(ProbA pa, GemmOut oa, int fir
 // vice versa, so LDS reads, global loads and barriers per MFMA are halved or
 // quartered, and the four independent accumulator chains keep the matrix pipe
 // fed from a single wave.  Register prefetch depth 2.
-constexpr int BM2 = 128, BN2 = 128, PF2 = 2;
+constexpr int PF2 = 2; /* (BM2, BN2: k_tiles.h) */
 
 template <class Prob>
 __global__ __launch_bounds__(256) void k_gemm2(Prob p, GemmOut o) {
@@ -488,34 +487,6 @@ template <bool UNI> struct ProbDelta {
     return x;
   }
 };
-
-// Split-K factor: enough workgroups to give every CU two or three, without
-// shredding K into single tiles.
-static int pick_ks(int tiles, int nkt, size_t slab_floats, size_t out_floats) {
-  const int cus = 256;
-  double best = 1e30;
-  int ks = 1;
-  for (int k = 1; k <= 16 && k <= nkt; k++) {
-    long wgs = (long)tiles * k;
-    /* CUs run up to ~3 of these workgroups side by side; count time in
-     * "K tiles on the busiest CU" plus a fill/drain charge per workgroup */
-    double per_cu = (double)((wgs + cus - 1) / cus);
-    double cost = per_cu * ((double)nkt / k) + 2.0 * (per_cu > 3 ? per_cu / 3 : 1) + 0.15 * k;
-    if (cost < best) {
-      best = cost;
-      ks = k;
-    }
-  }
-  if (ks > nkt) ks = nkt;
-  if (ks < 1) ks = 1;
-  while (ks > 1 && (size_t)ks * out_floats > slab_floats) ks--;
-  if (out_floats > slab_floats) { /* the workspace is sized for every output at engine creation */
-    fprintf(stderr, "librecur_amd: a GEMM output of %zu floats does not fit the split-K workspace (%zu)\n",
-            out_floats, slab_floats);
-    abort();
-  }
-  return ks;
-}
 
 static GemmOut make_gemm_out(float *slab, int M, int N, int nkt, int ks, int col0, int ldc,
                              int row0m, int *blocks) {

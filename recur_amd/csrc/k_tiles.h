@@ -1,0 +1,42 @@
+// k_tiles.h -- the tile sizes that both the kernels and the launchers' planning (calc_plan.h) read, and the split-K
+// rule.  No HIP here: the host compiler alone can include it.
+#pragma once
+#include <stddef.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+constexpr int CM = 32, CN = 32, CK = 128; /* the BPTT chain's tile (k_common.h) */
+constexpr int BM = 64, BN = 64, BK = 32;  /* k_gemm (k_gemm.h) */
+constexpr int BM2 = 128, BN2 = 128;       /* k_gemm2 */
+constexpr int RAMD_MAX_REST_PLANES = 64;
+constexpr int THP_ROWS = 128;   /* k_top_heads_partial: rows of W_ho per workgroup */
+constexpr int XD_NT = 3;        /* k_extras_dense: column tiles of 16 */
+constexpr int DD_FLAG_LOADS = 8; /* k_delta_direct: 4 x 256 streams of n_exec, of ih_scale */
+
+// Split-K factor: enough workgroups to give every CU two or three, without
+// shredding K into single tiles.
+static inline int pick_ks(int tiles, int nkt, size_t slab_floats, size_t out_floats) {
+  const int cus = 256;
+  double best = 1e30;
+  int ks = 1;
+  for (int k = 1; k <= 16 && k <= nkt; k++) {
+    long wgs = (long)tiles * k;
+    /* CUs run up to ~3 of these workgroups side by side; count time in
+     * "K tiles on the busiest CU" plus a fill/drain charge per workgroup */
+    double per_cu = (double)((wgs + cus - 1) / cus);
+    double cost = per_cu * ((double)nkt / k) + 2.0 * (per_cu > 3 ? per_cu / 3 : 1) + 0.15 * k;
+    if (cost < best) {
+      best = cost;
+      ks = k;
+    }
+  }
+  if (ks > nkt) ks = nkt;
+  if (ks < 1) ks = 1;
+  while (ks > 1 && (size_t)ks * out_floats > slab_floats) ks--;
+  if (out_floats > slab_floats) { /* the workspace is sized for every output at engine creation */
+    fprintf(stderr, "librecur_amd: a GEMM output of %zu floats does not fit the split-K workspace (%zu)\n",
+            out_floats, slab_floats);
+    abort();
+  }
+  return ks;
+}

@@ -2,6 +2,7 @@
 // the one-workgroup small-net form, finalizes, and ramd_launch_calc_deltas which strings them together.
 #include "k_common.h"
 #include "k_gemm.h"
+#include "calc_plan.h"
 
 // cumulative_input_error of one stream (recur-nn.c:377-382): the input columns of
 // every executed step's error, summed in step order.  One workgroup per stream.
@@ -419,7 +420,7 @@ __global__ __launch_bounds__(256) void k_top_backprop_scale(View v, int row0, co
 //      reference's merged ranges -- adds |running value| to the row's share of the error sum (recur-nn.c:178-191);
 //      then the stale entries, the sum, the soft clip (recur-nn.c:719-721) and the row, which is
 //      what k_top_backprop_heads + k_top_backprop_scale left behind.
-constexpr int THP_ROWS = 128, THP_U = 10;
+constexpr int THP_U = 10; /* (THP_ROWS: k_tiles.h) */
 __global__ __launch_bounds__(256) void k_top_heads_partial(View v, int row0, int nrows, const int *ranges, int range_stride,
                                                            const unsigned char *active, int alen, int ncls, float *P) {
   extern __shared__ float thp_sh[]; /* [THP_ROWS][ld] rows of W_ho, [32][ld] error segments */
@@ -814,7 +815,7 @@ __global__ __launch_bounds__(64) void k_extras_finalize(View v, int row0, int nr
 // four k of a chunk go to the chunk's four MFMAs, the same permutation of k on both sides -- four chunks in flight;
 // the waves' sums meet in LDS, then 8 threads per row apply the row rule, store ex, and add the squares to the
 // row's total (with the chain's partial sums, or the row's own sum of squares where it left none).
-constexpr int XD_NT = 3, XD_PF = 8, XD_WAVES = 8;
+constexpr int XD_PF = 8, XD_WAVES = 8; /* (XD_NT: k_tiles.h) */
 /* (round 5: eight chunks in flight instead of four, and nothing in the epilogue waits for memory on its own -- the input
  * values of the row rule are requested before the K loop, the step's total apart from the extras (the chain's partial sums,
  * or the output row's sum of squares) is formed by ALL threads behind the loop, 32 or 16 per row, every load of a thread in
@@ -1734,641 +1735,472 @@ extern "C" int ramd_calc_wrote_images(void) {
   return w;
 }
 
+/* One call of ramd_launch_calc_deltas: its arguments, the kernels' view of the buffers, and the plan (calc_plan.h). */
+struct CalcCall {
+  hipStream_t st;
+  View v;
+  const RamdShape *sh;
+  const RamdBuffers *b; /* (from the weight deltas on, with the caller's workspace as its slab: CalcPlan::own_ws) */
+  int row0, nrows, accumulate;
+  const int *ranges;
+  int range_stride;
+  const unsigned char *active;
+  RamdPendingDelta *defer;
+  CalcPlan p;
+};
+
+static void calc_top_backprop(const CalcCall &c) {
+  const RamdShape *sh = c.sh;
+  const RamdBuffers *b = c.b;
+  const CalcPlan &p = c.p;
+  if (p.writeback_first) ramd_launch_err_writeback(c.st, sh, b, c.row0, c.nrows); /* the images, before anything below overwrites the planes */
+  const size_t shm = (size_t)(sh->O + sh->H) * sizeof(float);
+  if (p.top == TOP_SPARSE) {
+    /* the multi-head loss's ranges, only the heads a stream trained: partial products per (stream, head), then the
+     * ordered sums and the clip */
+    const int alen = b->mheads_alen, ncls = sh->output_size / alen;
+    const int span4 = (3 + alen + 3) / 4, ld = (4 * span4) | 1; /* (the widest span: a head that starts 3 columns into its float4) */
+    raise_lds_limit<k_top_heads_partial>(96 * 1024); /* (85 KB at 128 symbols) */
+    RAMD_LAUNCH(k_top_heads_partial, dim3(ncls, (sh->H + THP_ROWS - 1) / THP_ROWS), dim3(256),
+                (size_t)((THP_ROWS + 32) * ld + 4) * sizeof(float), c.st, c.v, c.row0, c.nrows, c.ranges, c.range_stride, c.active,
+                alen, ncls, b->mheads_part);
+    RAMD_LAUNCH(k_top_heads_combine, dim3(c.nrows), dim3(THC_THREADS), 0, c.st, c.v, c.row0, c.ranges, c.range_stride, c.active,
+                ncls, b->mheads_part, (p.flags & RAMD_IMAGES_PENDING) ? 1 : 0); /* (it takes the stale entries from the planes) */
+  } else if (p.top == TOP_HEADS) {
+    /* the multi-head loss's ranges: one GEMM over all streams (k_top_backprop_heads), then the sums and the clip */
+    const int tm = (c.nrows + 31) / 32, tn = (sh->H + 31) / 32;
+    RAMD_LAUNCH(k_top_backprop_heads, dim3(tm * tn), dim3(512), (size_t)((sh->O + 15) / 16) * sizeof(unsigned), c.st, c.v,
+                c.row0, c.nrows, c.ranges, c.range_stride, c.active, b->slab, p.top_nb, tm);
+    RAMD_LAUNCH(k_top_backprop_scale, dim3(c.nrows), dim3(256), 0, c.st, c.v, c.row0, c.active, b->slab, p.top_nb);
+  } else if (p.top == TOP_RANGED) {
+    RAMD_LAUNCH(k_top_backprop_ranged, dim3(c.nrows, p.top_nb), dim3(1024), shm, c.st, c.v, c.row0, c.ranges, c.range_stride,
+                c.active, b->slab);
+    if (p.top_nb > 1) RAMD_LAUNCH(k_top_backprop_scale, dim3(c.nrows), dim3(256), 0, c.st, c.v, c.row0, c.active, b->slab, p.top_nb);
+  } else if (p.top == TOP_PLAIN)
+    RAMD_LAUNCH(k_top_backprop, dim3(c.nrows), dim3(256), shm, c.st, c.v, c.row0, c.ranges, c.range_stride, c.active);
+}
+
+/* What the top layer's delta still owes after its stage: a split-K GEMM into b->ho_slab that waits for a launch of the
+ * weight-delta stage to share, and whether its planes are summed in this call (sum_here) or by the optimiser launch
+ * that follows (defer->ho_*). */
+struct HoOwed {
+  bool gemm, sum_here;
+  ProbHoDelta prob;
+  int nkt, ks;
+};
+
+/* The top layer's delta, unless k_delta_direct forms it (ho_in_delta) or the fused single-net path updates W_ho
+ * directly (RAMD_NO_HO_DELTA).  Called in front of the chain launch -- which takes it as a request where the plan
+ * asks (req) -- and, where it was asked, again with the chain's answer: the GEMM when the chain declined. */
+static HoOwed calc_top_delta(const CalcCall &c, HoWork *req, bool chain_answered) {
+  const RamdShape *sh = c.sh;
+  const RamdBuffers *b = c.b;
+  RamdPendingDelta *defer = c.defer;
+  HoOwed owed = {};
+  if (c.p.ho_in_delta || (c.p.flags & RAMD_NO_HO_DELTA)) return owed;
+  if (c.p.ho_asked && !chain_answered) {
+    req->dst = (defer && b->ho_slab) ? b->ho_slab : b->ho_delta;
+    req->active = c.active;
+    req->row0 = c.row0;
+    req->nrows = c.nrows;
+    return owed;
+  }
+  if (c.p.ho_asked && req->done) {
+    if (defer) { /* one plane for the optimiser launch to take (or ho_delta is complete already) */
+      defer->ho_slab = req->dst == b->ho_slab ? b->ho_slab : nullptr;
+      defer->ho_n = (size_t)sh->H * sh->O;
+      defer->ho_ks = 1;
+      defer->ho_delta_out = b->ho_delta;
+    }
+    return owed;
+  }
+  const HoGemmPlan h = ramd_plan_ho_gemm(sh, b, c.p, c.nrows, c.accumulate, c.ranges != nullptr, c.range_stride,
+                                         c.active != nullptr, defer != nullptr);
+  if (defer) defer->ho_slab = nullptr;
+  if (h.form == HO_HEADS) { /* only the heads a stream trained carry error */
+    const int alen = b->mheads_alen, ncls = sh->output_size / alen;
+    RAMD_LAUNCH(k_ho_delta_heads, dim3(ncls, (sh->H + 31) / 32), dim3(256), (size_t)(HDH_K * ((alen | 1) + 32) + 8) * sizeof(float),
+                c.st, c.v, c.row0, c.nrows, c.ranges, c.range_stride, c.active, alen, ncls, c.accumulate);
+    return owed;
+  }
+  /* per-stream 1.0 / 0.0 participation flags as floats (b->coef plane 0 is free here:
+   * k_bptt_control rewrites it later in this call) */
+  const float *live = b->ones + c.row0;
+  if (c.active) {
+    RAMD_LAUNCH(k_live_mask, dim3((c.nrows + 255) / 256), dim3(256), 0, c.st, b->coef + c.row0, c.active, c.nrows);
+    live = b->coef + c.row0;
+  }
+  const ProbHoDelta prob = {c.v, c.row0, c.nrows, live};
+  if (h.form == HO_PLANES_PAIRED || h.form == HO_PAIRED_SUMMED)
+    owed = {true, h.form == HO_PAIRED_SUMMED, prob, h.nkt, h.ks};
+  else
+    launch_gemm<true, true, ProbHoDelta>(c.st, prob, h.form == HO_PLANES ? b->ho_slab : b->slab, sh->H, sh->O, h.nkt, h.ks, T_OTHER);
+  if (h.form == HO_PLANES || h.form == HO_PLANES_PAIRED) {
+    defer->ho_slab = b->ho_slab;
+    defer->ho_n = (size_t)sh->H * sh->O;
+    defer->ho_ks = h.ks;
+    defer->ho_delta_out = b->ho_delta;
+  }
+  if (h.form == HO_SUMMED)
+    /* with one range list per stream the set of touched columns differs per stream; the
+     * error is zero outside a stream's own ranges, so every column may take its sum */
+    RAMD_LAUNCH(k_ho_delta_finalize, dim3((sh->H * sh->O + 255) / 256), dim3(256), 0, c.st, c.v, b->slab, h.ks, c.accumulate,
+                c.range_stride ? nullptr : c.ranges);
+  return owed;
+}
+
+/* The owed top-layer GEMM (launch_it; the pair launch has launched it already) and, where its planes are summed in
+ * this call, their sum -- unless the k_delta_finalize that ends the call may take it along (may_ride): returns that. */
+static bool calc_settle_owed(const CalcCall &c, HoOwed &owed, bool launch_it, bool may_ride) {
+  if (!owed.gemm) return false;
+  if (launch_it) launch_gemm<true, true, ProbHoDelta>(c.st, owed.prob, c.b->ho_slab, c.sh->H, c.sh->O, owed.nkt, owed.ks, T_OTHER);
+  owed.gemm = false;
+  if (!owed.sum_here) return false;
+  if (may_ride && !c.ranges) return true;
+  RAMD_LAUNCH(k_ho_delta_finalize, dim3((c.sh->H * c.sh->O + 255) / 256), dim3(256), 0, c.st, c.v, c.b->ho_slab, owed.ks,
+              c.accumulate, c.range_stride ? nullptr : c.ranges);
+  return false;
+}
+
+/* one stream of a small net: chain, extras, control and weight deltas in one workgroup */
+static void calc_small(const CalcCall &c) {
+  raise_lds_limit<k_bptt_small>(150 * 1024);
+  if (c.defer) c.defer->slab = nullptr; /* ih_delta is written here: nothing left for the optimiser to sum */
+  int ev = timing_begin(c.st, T_CHAIN, 1);
+  RAMD_LAUNCH(k_bptt_small, dim3(1), dim3(1024), c.p.small_lds, c.st, c.v, c.row0, c.accumulate, c.p.flags, c.p.nx, c.p.nxp);
+  timing_end(c.st, ev);
+  g_calc_wrote_images = 1; /* the error images are done: no k_err_writeback for this call */
+}
+
+/* the extras and the control logic as a request to the one-launch chain's tail */
+static XcWork calc_xc_request(const CalcCall &c) {
+  XcWork xc = {};
+  if (c.p.xc_req == XC_NONE) return xc;
+  xc.on = 1;
+  xc.dense = c.p.xc_req == XC_DENSE;
+  xc.row0 = c.row0;
+  xc.nx = c.p.nx;
+  xc.nxp = c.p.nxp;
+  xc.active = c.active;
+  xc.flags = c.p.flags;
+  return xc;
+}
+
+/* ... and where the chain declined (tn_parts: the partial sums of squares per (step, stream) it left) */
+static void calc_extras_control(const CalcCall &c, int tn_parts) {
+  const RamdShape *sh = c.sh;
+  const CalcPlan &p = c.p;
+  const size_t shm = (size_t)(2 * sh->D + 1) * sizeof(float);
+  if (p.extras == XF_CONTROL5) /* extras and control in one launch, one workgroup per stream */
+    RAMD_LAUNCH((k_extras_control<5, 1024>), dim3(c.nrows), dim3(1024), shm, c.st, c.v, c.row0, c.nrows, p.nx, p.nxp, tn_parts,
+                c.active, p.flags);
+  else if (p.extras == XF_CONTROL8)
+    RAMD_LAUNCH((k_extras_control<8, 512>), dim3(c.nrows), dim3(512), shm, c.st, c.v, c.row0, c.nrows, p.nx, p.nxp, tn_parts,
+                c.active, p.flags);
+  else if (p.extras == XF_CONTROL9)
+    RAMD_LAUNCH((k_extras_control<9, 512>), dim3(c.nrows), dim3(512), shm, c.st, c.v, c.row0, c.nrows, p.nx, p.nxp, tn_parts,
+                c.active, p.flags);
+  else if (p.extras == XF_DENSE)
+    ramd_launch_extras_dense(c.st, c.v, sh, c.row0, c.nrows, p.nx, p.nxp, tn_parts, 0, sh->D);
+  else {
+    const int M = sh->D * c.nrows;
+    ProbExtras prob = {c.v, c.row0, c.nrows, p.nx};
+    launch_gemm<false, false, ProbExtras>(c.st, prob, c.b->slab, M, p.nxp, (sh->H + BK - 1) / BK, p.xks, T_OTHER);
+    RAMD_LAUNCH(k_extras_finalize, dim3(M), dim3(64), 0, c.st, c.v, c.row0, c.nrows, p.nx, p.nxp, p.xks, tn_parts);
+  }
+  if (p.extras == XF_DENSE || p.extras == XF_GEMM)
+    RAMD_LAUNCH(k_bptt_control, dim3((c.nrows + 3) / 4), dim3(256), 0, c.st, c.v, c.row0, c.nrows, c.active, p.flags, p.tn);
+}
+
+/* What a weight-delta GEMM left in the workspace for the optimiser launch, or k_delta_finalize, to sum: ks planes of
+ * the rows below rows_core and ks_rest planes of the rows from there on. */
+struct DeltaPlanes {
+  int ks, rows_core, ks_rest;
+  const float *rest; /* plane z of the rest rows: rest + z * rest_stride */
+  size_t rest_stride;
+  bool ho_rides; /* the owed top-layer planes are summed along with them */
+};
+/* whole planes, every row of ih_delta in each of the ks (ks_rest: the rest is empty, nobody reads it) */
+static DeltaPlanes whole_planes(const CalcCall &c, int ks, int ks_rest) {
+  return {ks, c.sh->I, ks_rest, c.b->slab + c.p.n, c.p.n, false};
+}
+
+static void launch_delta_finalize(const CalcCall &c, size_t first, size_t floats, int ks, int rows_core, int ks_rest, const float *rest,
+                                  size_t rest_stride, const float *ho_slab, size_t ho_n, int ho_ks) {
+  const size_t n4 = floats / 4;
+  const unsigned blocks = (unsigned)((n4 + 255) / 256) + (ho_slab ? (unsigned)(((size_t)c.sh->H * c.sh->O / 4 + 255) / 256) : 0u);
+  RAMD_LAUNCH(k_delta_finalize, dim3(blocks), dim3(256), 0, c.st, c.b->ih_delta + first, c.b->slab + first, n4, c.p.n, ks,
+              c.accumulate, c.sh->H, c.sh->hidden_size, rows_core, ks_rest, rest, rest_stride, c.b->ho_delta, ho_slab, ho_n, ho_ks);
+}
+
+template <int NPW> static void launch_delta_direct(const CalcCall &c, const DdArgs &a, const HoWork *hw, const HoApply *ap) {
+  const int tiles = c.p.dtm * c.p.dtn;
+  if (hw) {
+    raise_lds_limit<k_delta_direct_ho<DNW, DP, NPW>>(dd_lds_bytes(DNW, NPW));
+    RAMD_LAUNCH((k_delta_direct_ho<DNW, DP, NPW>), dim3(tiles), dim3(64 * DNW), dd_lds_bytes(DNW, NPW), c.st, a, c.v, *hw, *ap);
+  } else {
+    raise_lds_limit<k_delta_direct<DNW, DP, NPW>>(dd_lds_bytes(DNW, NPW));
+    RAMD_LAUNCH((k_delta_direct<DNW, DP, NPW>), dim3(c.p.dks * tiles), dim3(64 * DNW), dd_lds_bytes(DNW, NPW), c.st, a);
+  }
+}
+
+/* k_delta_direct (k_delta_direct.h): 64 x 64 tiles that own ALL of K, where those fill the chip (hidden 1024: 256 tiles);
+ * the sum goes straight into ih_delta -- and, when the caller's update is the momentum rule and nothing else wants the
+ * sums first, weights and momentum are updated in the same epilogue (fuse_want).  Returns whether the call is complete
+ * (no K split); else *out are the planes. */
+static bool calc_delta_direct(const CalcCall &c, HoOwed &owed, DeltaPlanes *out) {
+  const RamdShape *sh = c.sh;
+  const RamdBuffers *b = c.b;
+  const CalcPlan &p = c.p;
+  RamdPendingDelta *defer = c.defer;
+  calc_settle_owed(c, owed, true, false);
+  /* the top layer's sum as ONE array by now?  (the chain launch formed it, or a finalize has run) */
+  const bool ho_planes = defer && defer->ho_slab; /* (planes of a split-K GEMM: the epilogue adds them) */
+  const float *ho_src = ho_planes ? defer->ho_slab : b->ho_delta;
+  const bool fuse = p.direct_fuse && (ho_src || p.ho_in_delta);
+  DdArgs a = {};
+  a.x = b->arena + (size_t)c.row0 * sh->I;
+  a.e = b->ehi + (size_t)c.row0 * sh->I + 1;
+  a.coef = b->coef + c.row0;
+  a.n_exec = b->n_exec + c.row0;
+  a.ih_scale = b->ih_scale + c.row0;
+  a.w = b->ih_w + 1;
+  a.m = b->ih_m + 1;
+  a.delta = b->ih_delta + 1;
+  a.plane = (size_t)sh->Scap * sh->I;
+  a.I = sh->I;
+  a.H = sh->H;
+  a.Scap = sh->Scap;
+  a.nrows = c.nrows;
+  a.D = sh->D;
+  a.uidx = b->uniform_idx;
+  a.tm = p.dtm;
+  a.tn = p.dtn;
+  a.rest = p.drest;
+  a.rgroups = p.drg;
+  a.fast_its = p.fast_its;
+  a.hidden_size = sh->hidden_size;
+  a.mode = fuse ? 2 : c.accumulate ? 1 : 0;
+  if (p.dks > 1) { /* planes: stored, summed (and added to ih_delta where the call accumulates) by what follows */
+    a.delta = b->slab + 1;
+    a.ksplit = p.dks;
+    a.kplane = p.n;
+    a.mode = 0;
+  }
+  if (fuse) {
+    a.rate = defer->fuse_rate;
+    a.momentum = defer->fuse_momentum;
+    a.mw = defer->fuse_mw;
+    a.method = defer->fuse_method;
+    if (!p.ho_in_delta) { /* the top layer's sums are there (the chain launch formed them): its update, shared out */
+      a.ho_w = b->ho_w;
+      a.ho_m = b->ho_m;
+      a.ho_delta = ho_src;
+      a.ho_delta_out = ho_src == b->ho_delta ? nullptr : b->ho_delta;
+      a.ho_ks = ho_planes ? defer->ho_ks : 1;
+      a.ho_plane = defer->ho_n;
+      a.ho_n4 = (unsigned)((size_t)sh->H * sh->O / 4);
+      a.ho_rate = defer->fuse_ho_rate;
+    }
+  }
+  /* ... or formed HERE, in the launch's first microseconds (its waves wait ~2 us for their first operands anyway):
+   * workgroup i sums and updates rows 5 i .. of ho_delta / W_ho / its momentum -- 2.5 us less in the chain launch */
+  const bool ho_here = fuse && p.ho_in_delta;
+  HoWork hw = {};
+  hw.dst = b->ho_delta;
+  hw.row0 = c.row0;
+  hw.nrows = c.nrows;
+  hw.workers = p.dtm * p.dtn;
+  const HoApply ap = ho_here ? HoApply{b->ho_w, b->ho_m, defer->fuse_ho_rate, defer->fuse_momentum, defer->fuse_mw} : HoApply{};
+  int ev = timing_begin(c.st, T_DELTA);
+  if (p.npw == 2)
+    launch_delta_direct<2>(c, a, ho_here ? &hw : nullptr, &ap);
+  else
+    launch_delta_direct<1>(c, a, ho_here ? &hw : nullptr, &ap);
+  timing_end(c.st, ev);
+  if (p.dks > 1) {
+    *out = whole_planes(c, p.dks, p.ks);
+    return false;
+  }
+  if (defer) {
+    defer->slab = nullptr; /* ih_delta is complete */
+    if (fuse) {
+      defer->ho_slab = nullptr;
+      defer->fuse_done = 1;
+    }
+  }
+  return true;
+}
+
+/* rest: its rest rows (DeltaRest) ride along, their planes d.rest_off floats into the workspace */
+static void launch_delta_dma(const CalcCall &c, const GemmOut &o, int blocks, const DmaPlan &d, bool rest) {
+  const size_t shm = (size_t)DD_STAGES * DD_STAGE_FLOATS * sizeof(float), shm_rest = shm + (size_t)DD_REST_FLOATS * sizeof(float);
+  DeltaRest dr = {};
+  if (rest) dr = {c.b->slab + d.rest_off, d.rest_plane, d.rest_rows, d.rows_core};
+  if (!rest) {
+    raise_lds_limit<k_delta_dma<0>>((int)shm);
+    RAMD_LAUNCH(k_delta_dma<0>, dim3(blocks), dim3(512), shm, c.st, c.v, c.row0, c.nrows, o, dr);
+  } else if (d.rest_rows <= 64) {
+    raise_lds_limit<k_delta_dma<64>>((int)shm_rest);
+    RAMD_LAUNCH(k_delta_dma<64>, dim3(blocks), dim3(512), shm_rest, c.st, c.v, c.row0, c.nrows, o, dr);
+  } else {
+    raise_lds_limit<k_delta_dma<128>>((int)shm_rest);
+    RAMD_LAUNCH(k_delta_dma<128>, dim3(blocks), dim3(512), shm_rest, c.st, c.v, c.row0, c.nrows, o, dr);
+  }
+}
+
+/* The two-halves form (see g_delta_half_hook): rows [0, tm / 2 tiles), summed into ih_delta, hook; then the upper tiles
+ * with the rest rows riding along, the top layer's deltas (ho_direct: complete since the chain launch), summed, hook. */
+static void calc_delta_dma_halves(const CalcCall &c, const DmaPlan &d, GemmOut o, const HoOwed &owed, bool ho_direct) {
+  const RamdShape *sh = c.sh;
+  const size_t half_floats = (size_t)d.tmh * 128 * sh->H, up_floats = c.p.n - half_floats, ho_n = (size_t)sh->H * sh->O;
+  o.tm = d.tmh;
+  o.ks = d.kd2;
+  int ev = timing_begin(c.st, T_DELTA, 2);
+  launch_delta_dma(c, o, d.blocks2, d, false); /* lower half: no rest rows */
+  launch_delta_finalize(c, 0, half_floats, d.kd2, d.tmh * 128, 0, c.b->slab, 0, nullptr, 0, 0);
+  g_delta_half_hook(g_delta_half_ctx, 0, 0, half_floats);
+  o.row0m = d.tmh * 128; /* upper half + rest rows + the top layer */
+  launch_delta_dma(c, o, d.blocks2, d, true);
+  timing_end(c.st, ev);
+  if (!ho_direct) launch_gemm<true, true, ProbHoDelta>(c.st, owed.prob, c.b->ho_slab, sh->H, sh->O, owed.nkt, owed.ks, T_OTHER);
+  launch_delta_finalize(c, half_floats, up_floats, d.kd2, d.rows_core - d.tmh * 128, d.kd2 * d.tmh, c.b->slab + d.rest_off,
+                        d.rest_plane, ho_direct ? nullptr : c.b->ho_slab, ho_direct ? 0 : ho_n, ho_direct ? 0 : owed.ks);
+  g_delta_half_hook(g_delta_half_ctx, 1, half_floats, up_floats + ho_n);
+}
+
+/* k_delta_dma: whole 128-row tiles by LDS-DMA, one workgroup per CU; the rows above them (the input rows of a text
+ * net) inside the launch, or by the generic kernel with its own K split -- one launch with the owed top-layer GEMM.
+ * Returns whether the call is complete (the two halves); else *out are the planes. */
+static bool calc_delta_dma(const CalcCall &c, HoOwed &owed, bool ho_direct, DeltaPlanes *out) {
+  const RamdShape *sh = c.sh;
+  const RamdBuffers *b = c.b;
+  const CalcPlan &p = c.p;
+  const DmaPlan d = ramd_plan_delta_dma(sh, p, c.ranges != nullptr, c.defer != nullptr, g_delta_half_hook != nullptr,
+                                        (owed.gemm && owed.sum_here) || ho_direct);
+  const int ncol = sh->hidden_size + 1;
+  GemmOut o;
+  o.slab = b->slab;
+  o.M = sh->I;
+  o.N = ncol;
+  o.ldc = sh->H;
+  o.zs = p.n;
+  o.nkt = p.nkt;
+  o.tm = d.tm;
+  o.tn = d.tn;
+  o.ks = d.kd;
+  o.col0 = 1;
+  o.row0m = 0;
+  if (d.halves) {
+    calc_delta_dma_halves(c, d, o, owed, ho_direct);
+    return true;
+  }
+  int ev = timing_begin(c.st, T_DELTA);
+  launch_delta_dma(c, o, d.blocks, d, d.rest_in);
+  timing_end(c.st, ev);
+  *out = {d.kd, d.rows_core, d.ks_rest, d.ks_rest ? b->slab + d.rest_off : b->slab + (size_t)d.rows_core * sh->H,
+          d.ks_rest ? d.rest_plane : p.n, false};
+  if (d.rest_in) {
+    out->ho_rides = calc_settle_owed(c, owed, true, true);
+  } else if (d.rest_rows > 0) {
+    ProbDelta<true> prob = {c.v, c.row0, c.nrows, p.rtiles};
+    float *rest_slab = b->slab + d.rest_off - (size_t)d.rows_core * sh->H; /* (row rows_core of its planes is their first) */
+    if (owed.gemm) {
+      int blocks_a, blocks_b;
+      GemmOut oa = make_gemm_out(b->ho_slab, sh->H, sh->O, owed.nkt, owed.ks, 0, 0, 0, &blocks_a);
+      GemmOut ob = make_gemm_out(rest_slab, sh->I, ncol, p.nkt, d.ks_rest, 1, sh->H, d.rows_core, &blocks_b);
+      ob.zs = d.rest_plane;
+      int ev2 = timing_begin(c.st, T_DELTA);
+      RAMD_LAUNCH((k_gemm_pair<ProbHoDelta, ProbDelta<true>>), dim3(blocks_a + blocks_b), dim3(256), 0, c.st, owed.prob, oa,
+                  blocks_a, prob, ob);
+      timing_end(c.st, ev2);
+      out->ho_rides = calc_settle_owed(c, owed, false, true);
+    } else {
+      launch_gemm<true, true, ProbDelta<true>>(c.st, prob, rest_slab, sh->I, ncol, p.nkt, d.ks_rest, T_DELTA, 1, sh->H,
+                                               d.rows_core, d.rest_plane);
+    }
+  }
+  return false;
+}
+
+/* the generic GEMMs: 128 x 128 tiles where there are enough of them */
+static DeltaPlanes calc_delta_generic(const CalcCall &c) {
+  const RamdShape *sh = c.sh;
+  const CalcPlan &p = c.p;
+  const int ncol = sh->hidden_size + 1;
+  if (c.b->uniform_idx >= 0) {
+    ProbDelta<true> prob = {c.v, c.row0, c.nrows, p.rtiles};
+    if (p.big)
+      launch_gemm2<ProbDelta<true>>(c.st, prob, c.b->slab, sh->I, ncol, p.nkt, p.ks, T_DELTA, 1, sh->H);
+    else
+      launch_gemm<true, true, ProbDelta<true>>(c.st, prob, c.b->slab, sh->I, ncol, p.nkt, p.ks, T_DELTA, 1, sh->H);
+  } else {
+    ProbDelta<false> prob = {c.v, c.row0, c.nrows, p.rtiles};
+    if (p.big)
+      launch_gemm2<ProbDelta<false>>(c.st, prob, c.b->slab, sh->I, ncol, p.nkt, p.ks, T_DELTA, 1, sh->H);
+    else
+      launch_gemm<true, true, ProbDelta<false>>(c.st, prob, c.b->slab, sh->I, ncol, p.nkt, p.ks, T_DELTA, 1, sh->H);
+  }
+  return whole_planes(c, p.ks, p.ks);
+}
+
+/* the planes go to the optimiser launch that follows, which sums the slabs itself, or are summed here */
+static void calc_hand_over(const CalcCall &c, const DeltaPlanes &d, const HoOwed &owed) {
+  RamdPendingDelta *defer = c.defer;
+  if (defer && !c.accumulate) {
+    defer->slab = c.b->slab;
+    defer->n = c.p.n;
+    defer->ks = d.ks;
+    defer->H = c.sh->H;
+    defer->hidden_size = c.sh->hidden_size;
+    defer->rows_core = d.rows_core;
+    defer->ks_rest = d.ks_rest;
+    defer->rest = d.rest;
+    defer->rest_stride = d.rest_stride;
+    defer->delta_out = c.b->ih_delta;
+    return;
+  }
+  if (defer) defer->slab = nullptr;
+  launch_delta_finalize(c, 0, c.p.n, d.ks, d.rows_core, d.ks_rest, d.rest, d.rest_stride, d.ho_rides ? c.b->ho_slab : nullptr,
+                        (size_t)c.sh->H * c.sh->O, owed.ks);
+}
+
 extern "C" void ramd_launch_calc_deltas(ramd_stream_t st_, const RamdShape *sh,
                                         const RamdBuffers *b, int row0, int nrows, int accumulate,
                                         const int *ranges, int range_stride,
                                         const unsigned char *active, unsigned flags,
                                         RamdPendingDelta *defer) {
   g_calc_wrote_images = 0;
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  // top layer
-  size_t shm = (size_t)(sh->O + sh->H) * sizeof(float);
-  bool images_done = !(flags & RAMD_IMAGES_PENDING);
-  const int h_alen0 = b->mheads_alen, h_ncls0 = h_alen0 > 0 ? sh->output_size / h_alen0 : 0;
-  const bool top_sparse = !(flags & RAMD_TOP_DONE) && ranges && range_stride && (flags & RAMD_RANGES_ARE_HEADS) &&
-                          h_alen0 >= 24 && h_alen0 <= 128 && h_ncls0 <= 64 && sh->output_size == h_ncls0 * h_alen0 &&
-                          b->mheads_part && (size_t)sh->Scap * h_ncls0 * sh->H <= b->mheads_part_floats &&
-                          row0 + nrows <= sh->Scap && env_int("RECUR_AMD_TOP_SPARSE", 1);
-  if (!images_done && !(top_sparse && env_int("RECUR_AMD_STALE_FROM_PLANES", 1))) {
-    ramd_launch_err_writeback(st_, sh, b, row0, nrows); /* the images, before anything below overwrites the planes */
-    images_done = true;
-    flags &= ~RAMD_IMAGES_PENDING;
-  }
-  if (!(flags & RAMD_TOP_DONE)) { /* ramd_launch_text_top has already done the top backprop */
-    const int h_alen = h_alen0, h_ncls = h_ncls0;
-    if (top_sparse) {
-      /* the multi-head loss's ranges, only the heads a stream trained: partial products per (stream, head), then the
-       * ordered sums and the clip */
-      const int span4 = (3 + h_alen + 3) / 4, ld = (4 * span4) | 1; /* (the widest span: a head that starts 3 columns into its float4) */
-      static bool thp_attr = false;
-      if (!thp_attr) { /* (85 KB at 128 symbols) */
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_top_heads_partial, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        thp_attr = true;
-      }
-      RAMD_LAUNCH(k_top_heads_partial, dim3(h_ncls, (sh->H + THP_ROWS - 1) / THP_ROWS), dim3(256),
-                  (size_t)((THP_ROWS + 32) * ld + 4) * sizeof(float), st, v, row0, nrows, ranges, range_stride, active, h_alen,
-                  h_ncls, b->mheads_part);
-      RAMD_LAUNCH(k_top_heads_combine, dim3(nrows), dim3(THC_THREADS), 0, st, v, row0, ranges, range_stride, active, h_ncls,
-                  b->mheads_part, (flags & RAMD_IMAGES_PENDING) ? 1 : 0);
-      images_done = true; /* (it took the stale entries from the planes) */
-    } else if (ranges && range_stride && (flags & RAMD_RANGES_ARE_HEADS) && sh->O % 4 == 0 && sh->O >= 64 &&
-        (size_t)nrows * 2 * ((sh->H + 31) / 32) <= b->slab_floats && env_int("RECUR_AMD_TOP_HEADS", 1)) {
-      /* the multi-head loss's ranges: one GEMM over all streams (k_top_backprop_heads), then the sums and the clip */
-      const int tm = (nrows + 31) / 32, tn = (sh->H + 31) / 32, nb = 2 * tn;
-      RAMD_LAUNCH(k_top_backprop_heads, dim3(tm * tn), dim3(512), (size_t)((sh->O + 15) / 16) * sizeof(unsigned), st, v,
-                  row0, nrows, ranges, range_stride, active, b->slab, nb, tm);
-      RAMD_LAUNCH(k_top_backprop_scale, dim3(nrows), dim3(256), 0, st, v, row0, active, b->slab, nb);
-    } else if (ranges && env_int("RECUR_AMD_TOP_RANGED", 1)) {
-      /* up to 16 workgroups per stream (their partial sums sit in the split-K workspace, which
-       * nothing uses at this point) */
-      /* (measured: 256 streams with 1 / 2 / 4 / 8 / 16 workgroups per stream = 552 / 548 / 538 /
-       * 550 / 629 us per generation; 64 streams with 4 / 16: 347 / 358; 32 streams with 8 / 16: 306 / 312) */
-      int nb = 256 / nrows;
-      if (nb < 4) nb = nrows > 1024 ? 1 : 4;
-      if (nb > 16) nb = 16;
-      if ((size_t)nrows * nb > b->slab_floats) nb = 1;
-      RAMD_LAUNCH(k_top_backprop_ranged, dim3(nrows, nb), dim3(1024), shm, st, v, row0, ranges, range_stride,
-                  active, b->slab);
-      if (nb > 1)
-        RAMD_LAUNCH(k_top_backprop_scale, dim3(nrows), dim3(256), 0, st, v, row0, active, b->slab, nb);
-    } else
-      RAMD_LAUNCH(k_top_backprop, dim3(nrows), dim3(256), shm, st, v, row0, ranges, range_stride, active);
-  }
-  /* the weight-delta GEMM's path is decided here already: when it ends with the small GEMM
-   * over the rows above the last whole 128-row tile, the top layer's equally small delta
-   * GEMM can share that launch (nothing before the optimiser needs its result) */
-  const bool dma = b->uniform_idx >= 0 && nrows % BK == 0 && sh->hidden_size % 128 == 0 &&
-                   sh->I >= 128 && sh->activation != 5 && env_int("RECUR_AMD_DELTA_DMA", 1);
-  const bool has_rest = dma && (sh->I / 128) * 128 < sh->I;
-  /* ---- the weight-delta GEMM's form is decided here already (k_delta_direct below): when it carries the update, the top
-   * layer's delta and update ride in ITS first microseconds instead of the chain launch's (ho_in_delta) */
-  constexpr int DNW = 8, DP = 5;
-  /* row tiles: as many whole ones as make whole rounds of 256 workgroups, or nearly -- a multi-head net's 1100
-   * input rows are 17 x 16 = 272 tiles, a round of 256 and a round of 16: twice the time; as 16 row tiles they
-   * are one round with 76 rest rows, two pieces of them per workgroup (NPW) */
-  const int dtn = sh->hidden_size / 64;
-  int dtm = sh->I / 64, drest = sh->I - 64 * dtm;
-  auto rounds_ok = [&](int tm_) {
-    const int tiles = tm_ * dtn, rounds = (tiles + 255) / 256;
-    return tiles >= 192 && 10 * tiles >= 9 * 256 * rounds;
-  };
-  if (!rounds_ok(dtm) && dtm > 16 && sh->I - 64 * (dtm - 1) <= 128 && rounds_ok(dtm - 1)) {
-    dtm--;
-    drest = sh->I - 64 * dtm;
-  }
-  /* the rest rows' pieces: 16 per column tile (up to 64 rest rows) or 32, one or two per workgroup of the tile's first
-   * 16 row tiles -- or two per workgroup where there are only 8 row tiles (hidden 512) */
-  const int npw = dtm >= 16 ? (drest > 64 ? 2 : 1) : 2;
-  const int drg = dtm >= 16 ? 4 * npw : 4;
-  const int dQPS = nrows / 4, dn_it = dQPS % DNW == 0 ? sh->D * (dQPS / DNW) : -1;
-  /* fewer tiles than that (hidden 512: 8 x 8): K split two or four ways over workgroups, the parts' sums as planes for the
-   * optimiser's launch (or k_delta_finalize) to add -- what k_delta_dma leaves, from 64 x 64 tiles without LDS staging:
-   * 43.5 -> ... us at 512 / 128 / 30 */
-  int dks = 1;
-  if (!rounds_ok(dtm) && dn_it > 0 && env_int("RECUR_AMD_DELTA_DIRECT_SPLIT", 1))
-    for (int k = 4; k >= 2 && dks == 1; k -= 2)
-      if (dtm * dtn * k >= 192 && dtm * dtn * k <= 256 && dn_it % (k * DP) == 0 && dn_it / k >= DP) dks = k;
-  const bool direct = b->uniform_idx >= 0 && sh->hidden_size % 64 == 0 && dtn > 0 && (rounds_ok(dtm) || dks > 1) &&
-                      (drest == 0 || (dtm >= 16 && drest <= 128) || (dtm >= 8 && drest <= 64)) &&
-                      nrows % (4 * DNW) == 0 && nrows <= 256 * (DD_FLAG_LOADS / 2) && row0 + nrows <= sh->Scap &&
-                      sh->activation != 5 && dn_it >= DP && dn_it % DP == 0 &&
-                      !(g_delta_half_hook && env_int("RECUR_AMD_DIST_OVERLAP", 0)) && env_int("RECUR_AMD_DELTA_DIRECT", 1);
-  const bool direct_fuse = direct && dks == 1 && defer && defer->fuse_want && !accumulate && !(flags & (RAMD_NO_HO_DELTA | RAMD_IH_SCALE_IN_RATE));
-  /* (HoWork's preconditions: up to 256 streams, o_size <= 48, five rows of ho_delta per workgroup at most) */
-  /* (not where the chain launch has workgroups without chain work -- half of it or more, ramd_chain_steps: there the
-   * request costs the chain nothing, here it costs 2.4 us: the 48 loads per wave queue behind the ring's at the CU's
-   * 64 bytes per clock.  256 streams at hidden 1024: chain 107.6 -> 104.1 us, this launch 91.9 -> 94.3, generation 221.0 -> 219.9) */
-  const bool ho_in_delta = direct_fuse && defer->fuse_method == 0 && !ranges && !active && nrows >= 16 && nrows <= 256 && sh->O <= 48 && sh->O % 4 == 0 &&
-                           sh->H <= 5 * dtm * dtn && (nrows / 32) * (sh->hidden_size / 32) > 128 &&
-                           env_int("RECUR_AMD_HO_IN_DELTA", 1);
-  bool ho_paired = false, ho_finalize_after = false, ho_in_final = false;
-  ProbHoDelta ho_p = {};
-  int ho_nkt = 0, ho_ks = 0;
-  /* The top layer's delta.  Where the one-launch chain will run it is handed to that launch as a request
-   * (HoWork: formed while the chain's weight panels are on their way, no launch of its own); otherwise, and
-   * when the chain declines, the GEMM below. */
+  CalcCall c = {(hipStream_t)st_, make_view(sh, b), sh, b, row0, nrows, accumulate, ranges, range_stride, active, defer,
+                ramd_plan_calc_deltas(sh, b, row0, nrows, accumulate, ranges != nullptr, range_stride, active != nullptr, flags,
+                                      defer, g_delta_half_hook != nullptr)};
+  calc_top_backprop(c);
   HoWork ho_req = {};
-  /* (up to 256 streams: the request costs the chain launch 0.014 us per stream -- 3.6 us at 256 against the GEMM's
-   * 6.2 us launch -- and nothing where the set leaves workgroups of that launch without chain work: 32 streams
-   * 145.3 -> 141.0 us per generation, 64: 155.7 -> 151.2, 256: 244.8 -> 242.4) */
-  const bool ho_asked = !ho_in_delta && !(flags & RAMD_NO_HO_DELTA) && !ranges && !accumulate && nrows >= 16 && nrows <= 256 && sh->O <= 48 &&
-                        env_int("RECUR_AMD_HO_IN_CHAIN", 1);
-  auto ho_classic = [&]() { /* (the fused single-net path, RAMD_NO_HO_DELTA, updates W_ho directly) */
-    if (ranges && range_stride && (flags & RAMD_RANGES_ARE_HEADS) && b->mheads_alen >= 24 && b->mheads_alen <= 128 &&
-        sh->output_size % b->mheads_alen == 0 && sh->output_size / b->mheads_alen <= 64 && env_int("RECUR_AMD_HO_HEADS", 1)) {
-      /* the multi-head loss: only the heads a stream trained carry error (k_ho_delta_heads) */
-      const int alen = b->mheads_alen, ncls = sh->output_size / alen;
-      if (defer) defer->ho_slab = nullptr;
-      RAMD_LAUNCH(k_ho_delta_heads, dim3(ncls, (sh->H + 31) / 32), dim3(256),
-                  (size_t)(HDH_K * ((alen | 1) + 32) + 8) * sizeof(float), st, v, row0, nrows, ranges, range_stride, active, alen,
-                  ncls, accumulate);
-      return;
-    }
-    int tm = (sh->H + BM - 1) / BM, tn = (sh->O + BN - 1) / BN;
-    int nkt = (nrows + BK - 1) / BK;
-    int ho = sh->H * sh->O;
-    int ks = pick_ks(tm * tn, nkt, b->slab_floats, (size_t)ho);
-    /* per-stream 1.0 / 0.0 participation flags as floats (b->coef plane 0 is free here:
-     * k_bptt_control rewrites it later in this call) */
-    const float *live = b->ones + row0;
-    if (active) {
-      RAMD_LAUNCH(k_live_mask, dim3((nrows + 255) / 256), dim3(256), 0, st, b->coef + row0,
-                         active, nrows);
-      live = b->coef + row0;
-    }
-    ProbHoDelta p = {v, row0, nrows, live};
-    if (defer) defer->ho_slab = nullptr;
-    if (defer && !accumulate && !ranges && b->ho_slab) {
-      /* the optimiser launch that follows sums these slabs itself (and stores ho_delta) */
-      if (ks > 8) ks = 8;
-      if (has_rest && !active && env_int("RECUR_AMD_PAIR_HO", 1)) {
-        ho_paired = true; /* launched together with the rest rows of the weight-delta GEMM */
-        ho_p = p;
-        ho_nkt = nkt;
-        ho_ks = ks;
-      } else {
-        launch_gemm<true, true, ProbHoDelta>(st, p, b->ho_slab, sh->H, sh->O, nkt, ks, T_OTHER);
-      }
-      defer->ho_slab = b->ho_slab;
-      defer->ho_n = (size_t)ho;
-      defer->ho_ks = ks;
-      defer->ho_delta_out = b->ho_delta;
-    } else if (has_rest && !active && b->ho_slab && env_int("RECUR_AMD_PAIR_HO", 1)) {
-      /* not deferred (the deltas are wanted as such: accumulation, an all-reduce between the
-       * ranks): still one launch with the rest rows, summed right after it */
-      if (ks > 8) ks = 8;
-      ho_paired = true;
-      ho_finalize_after = true;
-      ho_p = p;
-      ho_nkt = nkt;
-      ho_ks = ks;
-    } else {
-      launch_gemm<true, true, ProbHoDelta>(st, p, b->slab, sh->H, sh->O, nkt, ks, T_OTHER);
-      /* with one range list per stream the set of touched columns differs per stream; the
-       * error is zero outside a stream's own ranges, so every column may take its sum */
-      RAMD_LAUNCH(k_ho_delta_finalize, dim3((ho + 255) / 256), dim3(256), 0, st, v, b->slab,
-                         ks, accumulate, range_stride ? nullptr : ranges);
-    }
-  };
-  if (ho_asked) {
-    ho_req.dst = (defer && b->ho_slab) ? b->ho_slab : b->ho_delta;
-    ho_req.active = active;
-    ho_req.row0 = row0;
-    ho_req.nrows = nrows;
-  } else if (!(flags & RAMD_NO_HO_DELTA) && !ho_in_delta) {
-    ho_classic();
-  }
-  // BPTT chain: D dependent steps, one launch each, then the extras of all steps
-  bool control_done = false;
-  const int tn = (sh->hidden_size + CN - 1) / CN;
-  int tn_parts = tn; /* partial sums of squares per (step, stream): one per column tile of the chain kernel used */
-  const int nx = sh->I - sh->hidden_size; /* column 0 + the input columns */
-  const int nxp = (nx + 3) & ~3;
-  if (nrows == 1 && !active && row0 < sh->Scap && sh->H <= 256 &&
-      env_int("RECUR_AMD_BPTT_SMALL", 1)) {
-    /* one stream of a small net (the per-net calls): chain, extras, control and weight deltas
-     * in one workgroup */
-    /* h_size <= 128 and i_size <= 256 (text-predict's default 99 hidden units: 100 x 142):
-     * the matrix lives in the workgroup's registers; larger nets take the launch-per-step route */
-    const size_t shm = (size_t)(128 + 256 + 256 + 20 + ((sh->D + 3) & ~3) + (size_t)sh->D * sh->I) * sizeof(float);
-    if (sh->H <= 128 && sh->I <= 256 && shm <= 150 * 1024) {
-      static bool attr_set = false;
-      if (!attr_set) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_bptt_small,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        attr_set = true;
-      }
-      if (defer) defer->slab = nullptr; /* ih_delta is written here: nothing left for the optimiser to sum */
-      int ev = timing_begin(st, T_CHAIN, 1);
-      RAMD_LAUNCH(k_bptt_small, dim3(1), dim3(1024), shm, st, v, row0, accumulate, flags, nx, nxp);
-      timing_end(st, ev);
-      g_calc_wrote_images = 1; /* the error images are done: no k_err_writeback for this call */
-      return;
-    }
-  }
-  {
-    /* the extras and the control logic ride in the one-launch chain's tail where they are the gather form
-     * (XcWork, k_common.h); where the chain declines, the launch below */
-    const bool extras_gather = sh->H <= 2304 && !(b->dense_inputs && nx > 8);
-    XcWork xc_req = {};
-    if (extras_gather && nx <= 128 && env_int("RECUR_AMD_XC_IN_CHAIN", 1) &&
-        (size_t)(sh->D + 1) * sh->Scap * sh->I * sizeof(float) < ((size_t)1 << 31)) { /* (32-bit byte offsets into the planes) */
-      xc_req.on = 1;
-      xc_req.row0 = row0;
-      xc_req.nx = nx;
-      xc_req.nxp = nxp;
-      xc_req.active = active;
-      xc_req.flags = flags;
-    } else if (b->dense_inputs && nx > 8 && nx <= 16 * XD_NT && (sh->hidden_size == 512 || sh->hidden_size == 1024) &&
-               sh->D <= 63 && env_int("RECUR_AMD_XC_IN_CHAIN", 1) &&
-               env_int("RECUR_AMD_XC_DENSE_IN_CHAIN", 1) &&
-               (size_t)(sh->D + 1) * sh->Scap * sh->I * sizeof(float) < ((size_t)1 << 31)) {
-      /* dense inputs (gstclassify's features): the extras as a small GEMM in the one-launch chain's tail (extras_dense_tail) */
-      xc_req.on = 1;
-      xc_req.dense = 1;
-      xc_req.row0 = row0;
-      xc_req.nx = nx;
-      xc_req.nxp = nxp;
-      xc_req.active = active;
-      xc_req.flags = flags;
-    }
-    tn_parts = ramd_chain_steps(st, v, sh, b, row0, nrows, ho_asked ? &ho_req : nullptr, xc_req.on ? &xc_req : nullptr);
-    if (ho_asked && ho_req.done) {
-      if (defer) { /* one plane for the optimiser launch to take (or ho_delta is complete already) */
-        defer->ho_slab = ho_req.dst == b->ho_slab ? b->ho_slab : nullptr;
-        defer->ho_n = (size_t)sh->H * sh->O;
-        defer->ho_ks = 1;
-        defer->ho_delta_out = b->ho_delta;
-      }
-    } else if (ho_asked) {
-      ho_classic();
-    }
-    int M = sh->D * nrows;
-    int etm = (M + BM - 1) / BM, etn = (nx + BN - 1) / BN, nkt = (sh->H + BK - 1) / BK;
-    int ks = pick_ks(etm * etn, nkt, b->slab_floats, (size_t)M * nxp);
-    /* the gather over the non-zero input rows (one-hot symbols: two rows per step and stream) or,
-     * for dense inputs with more than a handful of columns, the GEMM over all of them */
-    if (xc_req.done) {
-      control_done = true; /* extras and control: done in the chain launch */
-    } else if (extras_gather) {
-      const int nq = (sh->H / 4 + 63) / 64;
-      /* extras and control in one launch, one workgroup per stream */
-      const size_t shm = (size_t)(2 * sh->D + 1) * sizeof(float);
-      if (nq <= 5)
-        RAMD_LAUNCH((k_extras_control<5, 1024>), dim3(nrows), dim3(1024), shm, st, v, row0, nrows,
-                           nx, nxp, tn_parts, active, flags);
-      else if (nq <= 8)
-        RAMD_LAUNCH((k_extras_control<8, 512>), dim3(nrows), dim3(512), shm, st, v, row0, nrows,
-                           nx, nxp, tn_parts, active, flags);
-      else /* h_size 2052: hidden 2048 */
-        RAMD_LAUNCH((k_extras_control<9, 512>), dim3(nrows), dim3(512), shm, st, v, row0, nrows,
-                           nx, nxp, tn_parts, active, flags);
-      control_done = true;
-    } else if (nx <= 16 * XD_NT && env_int("RECUR_AMD_EXTRAS_DENSE", 1)) {
-      /* dense inputs, up to 47 of them: GEMM and finalize in one launch */
-      ramd_launch_extras_dense(st, v, sh, row0, nrows, nx, nxp, tn_parts, 0, sh->D);
-    } else { /* very wide nets: the dense GEMM over all extra columns */
-      ProbExtras p = {v, row0, nrows, nx};
-      launch_gemm<false, false, ProbExtras>(st, p, b->slab, M, nxp, nkt, ks, T_OTHER);
-      RAMD_LAUNCH(k_extras_finalize, dim3(M), dim3(64), 0, st, v, row0, nrows, nx, nxp, ks, tn_parts);
-    }
-  }
-  if (!control_done)
-    RAMD_LAUNCH(k_bptt_control, dim3((nrows + 3) / 4), dim3(256), 0, st, v, row0, nrows,
-                       active, flags, tn);
+  HoOwed owed = calc_top_delta(c, &ho_req, false);
+  if (c.p.small) return calc_small(c);
+  // BPTT chain: D dependent steps, then the extras of all steps and the control logic -- in its tail, or behind it
+  XcWork xc_req = calc_xc_request(c);
+  const int tn_parts = ramd_chain_steps(c.st, c.v, sh, b, row0, nrows, c.p.ho_asked ? &ho_req : nullptr, xc_req.on ? &xc_req : nullptr);
+  if (c.p.ho_asked) owed = calc_top_delta(c, &ho_req, true);
+  if (!xc_req.done) calc_extras_control(c, tn_parts);
   // weight deltas: one GEMM over (step, stream)
   RamdBuffers own_ws;
-  if (defer && defer->own_slab && !accumulate) {
-    /* planes that are to outlive this call go to the caller's workspace (the kernels' View, made above, is not
-     * concerned: the planes reach them as arguments) */
+  if (c.p.own_ws) { /* (the kernels' View, made above, is not concerned: the planes reach them as arguments) */
     own_ws = *b;
     own_ws.slab = defer->own_slab;
     own_ws.slab_floats = defer->own_slab_floats;
-    b = &own_ws;
+    c.b = &own_ws;
   }
-  {
-    /* only columns 1..hidden_size of the delta can be non-zero (h_error[0] and the pad are
-     * zero, recur-nn.c:334-337), so the column tiles start at 1: at hidden 1024 that is 16
-     * exact tiles instead of 17 */
-    const int ncol = sh->hidden_size + 1;
-    int tm = (sh->I + BM - 1) / BM, tn = (ncol - 1 + BN - 1) / BN;
-    int rtiles = (nrows + BK - 1) / BK;
-    int nkt = sh->D * rtiles;
-    size_t n = (size_t)sh->I * sh->H;
-    int ks = pick_ks(tm * tn, nkt, b->slab_floats, n);
-    const bool big = sh->I >= 256 && nkt >= 16;
-    if (big) {
-      int tm2 = (sh->I + BM2 - 1) / BM2, tn2 = (ncol - 1 + BN2 - 1) / BN2;
-      ks = pick_ks(tm2 * tn2, nkt, b->slab_floats, n);
-    }
-    int rows_core = sh->I, ks_rest = ks;
-    float *rest_base = b->slab; /* planes of the rows from rows_core on: rest_base + z * rest_stride */
-    size_t rest_stride = n;
-    /* ---- k_delta_direct (k_delta_direct.h): 64 x 64 tiles that own ALL of K, where those fill the chip (hidden 1024:
-     * 256 tiles); the sum goes straight into ih_delta -- and, when the caller's update is the momentum rule and
-     * nothing else wants the sums first, weights and momentum are updated in the same epilogue (fuse_want) */
-    bool gemm_done = false;
-    {
-      constexpr int NW = DNW, P = DP;
-      if (direct && (dks == 1 || (size_t)dks * n <= b->slab_floats)) {
-        static bool attr_set = false;
-        if (!attr_set) {
-          HIP_CHECK(hipFuncSetAttribute((const void *)(k_delta_direct<NW, P, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        dd_lds_bytes(NW, 1)));
-          HIP_CHECK(hipFuncSetAttribute((const void *)(k_delta_direct<NW, P, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        dd_lds_bytes(NW, 2)));
-          HIP_CHECK(hipFuncSetAttribute((const void *)(k_delta_direct_ho<NW, P, 1>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        dd_lds_bytes(NW, 1)));
-          HIP_CHECK(hipFuncSetAttribute((const void *)(k_delta_direct_ho<NW, P, 2>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        dd_lds_bytes(NW, 2)));
-          attr_set = true;
-        }
-        if (ho_paired) { /* the top layer's delta GEMM had been waiting for a pair launch */
-          launch_gemm<true, true, ProbHoDelta>(st, ho_p, b->ho_slab, sh->H, sh->O, ho_nkt, ho_ks, T_OTHER);
-          ho_paired = false;
-          if (ho_finalize_after)
-            RAMD_LAUNCH(k_ho_delta_finalize, dim3((sh->H * sh->O + 255) / 256), dim3(256), 0, st, v, b->ho_slab, ho_ks,
-                        accumulate, range_stride ? nullptr : ranges);
-        }
-        /* the top layer's sum as ONE array by now?  (the chain launch formed it, or a finalize has run) */
-        const float *ho_src = nullptr;
-        int ho_src_ks = 1;
-        if (defer && defer->ho_slab) { /* (planes of a split-K GEMM: the epilogue adds them) */
-          ho_src = defer->ho_slab;
-          ho_src_ks = defer->ho_ks;
-        } else
-          ho_src = b->ho_delta;
-        const bool fuse = direct_fuse && (ho_src || ho_in_delta);
-        DdArgs a = {};
-        a.x = b->arena + (size_t)row0 * sh->I;
-        a.e = b->ehi + (size_t)row0 * sh->I + 1;
-        a.coef = b->coef + row0;
-        a.n_exec = b->n_exec + row0;
-        a.ih_scale = b->ih_scale + row0;
-        a.w = b->ih_w + 1;
-        a.m = b->ih_m + 1;
-        a.delta = b->ih_delta + 1;
-        a.plane = (size_t)sh->Scap * sh->I;
-        a.I = sh->I;
-        a.H = sh->H;
-        a.Scap = sh->Scap;
-        a.nrows = nrows;
-        a.D = sh->D;
-        a.uidx = b->uniform_idx;
-        a.tm = dtm;
-        a.tn = dtn;
-        a.rest = drest;
-        a.rgroups = drg;
-        { /* the shares of a SIMD's two waves (dd_body): 5 / 8 to the first where the loop is long, rounded to whole rings */
-          const int pct = env_int("RECUR_AMD_DELTA_FAST_PCT", 66), n_pair = 2 * (dn_it / dks);
-          if (pct > 0 && dn_it / dks >= 40) {
-            int nf = (n_pair * pct / 100 + P / 2) / P * P;
-            if (nf < P) nf = P;
-            if (nf > n_pair - P) nf = n_pair - P;
-            a.fast_its = nf;
-          }
-        }
-        a.hidden_size = sh->hidden_size;
-        a.mode = fuse ? 2 : accumulate ? 1 : 0;
-        if (dks > 1) { /* planes: stored, summed (and added to ih_delta where the call accumulates) by what follows */
-          a.delta = b->slab + 1;
-          a.ksplit = dks;
-          a.kplane = n;
-          a.mode = 0;
-        }
-        if (fuse) {
-          a.rate = defer->fuse_rate;
-          a.momentum = defer->fuse_momentum;
-          a.mw = defer->fuse_mw;
-          a.method = defer->fuse_method;
-          if (!ho_in_delta) { /* the top layer's sums are there (the chain launch formed them): its update, shared out */
-            a.ho_w = b->ho_w;
-            a.ho_m = b->ho_m;
-            a.ho_delta = ho_src;
-            a.ho_delta_out = ho_src == b->ho_delta ? nullptr : b->ho_delta;
-            a.ho_ks = ho_src_ks;
-            a.ho_plane = defer->ho_n;
-            a.ho_n4 = (unsigned)((size_t)sh->H * sh->O / 4);
-            a.ho_rate = defer->fuse_ho_rate;
-          }
-        }
-        int ev = timing_begin(st, T_DELTA);
-        if (fuse && ho_in_delta) {
-          /* ... or formed HERE, in the launch's first microseconds (its waves wait ~2 us for their first operands anyway):
-           * workgroup i sums and updates rows 5 i .. of ho_delta / W_ho / its momentum -- 2.5 us less in the chain launch */
-          HoWork hw = {};
-          hw.dst = b->ho_delta;
-          hw.row0 = row0;
-          hw.nrows = nrows;
-          hw.workers = dtm * dtn;
-          HoApply ap = {b->ho_w, b->ho_m, defer->fuse_ho_rate, defer->fuse_momentum, defer->fuse_mw};
-          if (npw == 2)
-            RAMD_LAUNCH((k_delta_direct_ho<NW, P, 2>), dim3(dtm * dtn), dim3(64 * NW), dd_lds_bytes(NW, 2), st, a, v, hw, ap);
-          else
-            RAMD_LAUNCH((k_delta_direct_ho<NW, P, 1>), dim3(dtm * dtn), dim3(64 * NW), dd_lds_bytes(NW, 1), st, a, v, hw, ap);
-        } else if (npw == 2)
-          RAMD_LAUNCH((k_delta_direct<NW, P, 2>), dim3(dks * dtm * dtn), dim3(64 * NW), dd_lds_bytes(NW, 2), st, a);
-        else
-          RAMD_LAUNCH((k_delta_direct<NW, P, 1>), dim3(dks * dtm * dtn), dim3(64 * NW), dd_lds_bytes(NW, 1), st, a);
-        timing_end(st, ev);
-        if (dks == 1) {
-          if (defer) {
-            defer->slab = nullptr; /* ih_delta is complete */
-            if (fuse) {
-              defer->ho_slab = nullptr;
-              defer->fuse_done = 1;
-            }
-          }
-          return;
-        }
-        ks = dks; /* whole planes: every row and column of ih_delta in each */
-        gemm_done = true;
-      }
-    }
-    if (gemm_done) {
-    } else if (dma) {
-      /* whole 128-row tiles by LDS-DMA, one workgroup per CU; the rows above them (the
-       * input rows of a text net) by the generic kernel with its own K split */
-      static bool attr_set = false;
-      size_t shm = (size_t)DD_STAGES * DD_STAGE_FLOATS * sizeof(float);
-      const size_t shm_rest = shm + (size_t)DD_REST_FLOATS * sizeof(float);
-      if (!attr_set) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_delta_dma<0>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_delta_dma<64>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_rest));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_delta_dma<128>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_rest));
-        attr_set = true;
-      }
-      rows_core = (sh->I / 128) * 128;
-      GemmOut o;
-      o.slab = b->slab;
-      o.M = sh->I;
-      o.N = ncol;
-      o.ldc = sh->H;
-      o.zs = n;
-      o.nkt = nkt;
-      o.tm = rows_core / 128;
-      o.tn = sh->hidden_size / 128;
-      o.col0 = 1;
-      o.row0m = 0;
-      int tiles = o.tm * o.tn;
-      int kd = 8;
-      while (kd > 1 && tiles * kd > 256) kd >>= 1;
-      while (kd > 1 && (kd > nkt || (size_t)kd * n > b->slab_floats)) kd >>= 1;
-      o.ks = ks = kd;
-      const int per = 8 / kd;
-      int blocks = ((tiles + per - 1) / per) * 8;
-      /* the rows above the last whole tile inside the same launch (see DeltaRest) when there are at
-       * most 128 of them, at least four row tiles to share them out, and room for ks * tm planes */
-      const int rest_rows = sh->I - rows_core;
-      const size_t rest_plane = (size_t)rest_rows * sh->H;
-      const bool rest_in = rest_rows > 0 && rest_rows <= 128 && o.tm >= 4 && kd * o.tm <= RAMD_MAX_REST_PLANES &&
-                           (size_t)kd * n + (size_t)kd * o.tm * rest_plane <= b->slab_floats &&
-                           env_int("RECUR_AMD_DELTA_REST_IN", 1);
-      /* ---- the two-halves form (see g_delta_half_hook): rows [0, tm / 2 tiles) with twice the K split
-       * (the same number of workgroups and of slab bytes), summed into ih_delta, hook; then the upper
-       * tiles with the rest rows riding along, the top layer's deltas, summed, hook */
-      const bool ho_direct = ho_asked && ho_req.done && ho_req.dst == b->ho_delta; /* complete since the chain launch */
-      if (g_delta_half_hook && !defer && rest_in && o.tm >= 8 && o.tm % 2 == 0 &&
-          ((ho_paired && ho_finalize_after) || ho_direct) && !ranges && env_int("RECUR_AMD_DIST_OVERLAP", 0)) {
-        /* OFF by default -- measured with ONE rank (bench.py --dist, round 3): 305 against 255 us per
-         * generation.  Two launches of half the rows with twice the K split cost the GEMM class +24 us
-         * (each workgroup's prologue, epilogue and ring fill amortise over 20 instead of 40 K tiles, the
-         * finalize sums 8 planes twice), the two event hand-overs and RCCL calls another ~25 us: more
-         * than the ~2.2 MB all-reduce it could hide is expected to take over xGMI.  And while a half's
-         * GEMM holds every CU with 148 KB of LDS, RCCL's own workgroups can only become resident as that
-         * launch drains.  Kept for the day a multi-GPU node says otherwise (RECUR_AMD_DIST_OVERLAP=1;
-         * results equal the one-launch form: tests/test_gpu_dist.py). */
-        const int tmh = o.tm / 2;
-        int kd2 = 8;
-        while (kd2 > 1 && (tmh * o.tn * kd2 > 256 || kd2 > nkt ||
-                           (size_t)kd2 * n + (size_t)kd2 * tmh * rest_plane > b->slab_floats))
-          kd2 >>= 1;
-        const int per2 = 8 / kd2;
-        const int blocks2 = ((tmh * o.tn + per2 - 1) / per2) * 8;
-        const size_t half_floats = (size_t)tmh * 128 * sh->H, n4h = half_floats / 4;
-        GemmOut oh = o;
-        oh.tm = tmh;
-        oh.ks = kd2;
-        int evh = timing_begin(st, T_DELTA, 2);
-        { /* lower half: no rest rows */
-          DeltaRest none = {};
-          oh.row0m = 0;
-          RAMD_LAUNCH(k_delta_dma<0>, dim3(blocks2), dim3(512), shm, st, v, row0, nrows, oh, none);
-          RAMD_LAUNCH(k_delta_finalize, dim3((unsigned)((n4h + 255) / 256)), dim3(256), 0, st, b->ih_delta, b->slab, n4h, n,
-                      kd2, accumulate, sh->H, sh->hidden_size, tmh * 128, 0, b->slab, (size_t)0, b->ho_delta,
-                      (const float *)nullptr, (size_t)0, 0);
-          g_delta_half_hook(g_delta_half_ctx, 0, 0, half_floats);
-        }
-        { /* upper half + rest rows + the top layer */
-          DeltaRest dr;
-          dr.planes = b->slab + (size_t)kd2 * n;
-          dr.stride = rest_plane;
-          dr.rows = rest_rows;
-          dr.col = rows_core;
-          oh.row0m = tmh * 128;
-          if (rest_rows <= 64)
-            RAMD_LAUNCH(k_delta_dma<64>, dim3(blocks2), dim3(512), shm_rest, st, v, row0, nrows, oh, dr);
-          else
-            RAMD_LAUNCH(k_delta_dma<128>, dim3(blocks2), dim3(512), shm_rest, st, v, row0, nrows, oh, dr);
-          timing_end(st, evh);
-          if (!ho_direct) launch_gemm<true, true, ProbHoDelta>(st, ho_p, b->ho_slab, sh->H, sh->O, ho_nkt, ho_ks, T_OTHER);
-          const size_t up_floats = n - half_floats, n4u = up_floats / 4, ho_n = (size_t)sh->H * sh->O;
-          const unsigned fin_blocks = (unsigned)((n4u + 255) / 256) + (ho_direct ? 0u : (unsigned)((ho_n / 4 + 255) / 256));
-          RAMD_LAUNCH(k_delta_finalize, dim3(fin_blocks), dim3(256), 0, st, b->ih_delta + half_floats, b->slab + half_floats,
-                      n4u, n, kd2, accumulate, sh->H, sh->hidden_size, rows_core - tmh * 128, kd2 * tmh, dr.planes,
-                      rest_plane, b->ho_delta, ho_direct ? (const float *)nullptr : b->ho_slab, ho_direct ? (size_t)0 : ho_n,
-                      ho_direct ? 0 : ho_ks);
-          g_delta_half_hook(g_delta_half_ctx, 1, half_floats, up_floats + ho_n);
-        }
-        return;
-      }
-      int ev = timing_begin(st, T_DELTA);
-      if (rest_in) {
-        DeltaRest dr;
-        dr.planes = b->slab + (size_t)kd * n;
-        dr.stride = rest_plane;
-        dr.rows = rest_rows;
-        dr.col = rows_core;
-        if (rest_rows <= 64)
-          RAMD_LAUNCH(k_delta_dma<64>, dim3(blocks), dim3(512), shm_rest, st, v, row0, nrows, o, dr);
-        else
-          RAMD_LAUNCH(k_delta_dma<128>, dim3(blocks), dim3(512), shm_rest, st, v, row0, nrows, o, dr);
-      } else {
-        DeltaRest dr = {};
-        RAMD_LAUNCH(k_delta_dma<0>, dim3(blocks), dim3(512), shm, st, v, row0, nrows, o, dr);
-      }
-      timing_end(st, ev);
-      ks_rest = 0;
-      if (rest_in) {
-        ks_rest = kd * o.tm;
-        rest_base = b->slab + (size_t)kd * n;
-        rest_stride = rest_plane;
-        if (ho_paired) { /* the top layer's delta GEMM had been waiting for the pair launch */
-          launch_gemm<true, true, ProbHoDelta>(st, ho_p, b->ho_slab, sh->H, sh->O, ho_nkt, ho_ks, T_OTHER);
-          ho_paired = false;
-          if (ho_finalize_after && !ranges) {
-            ho_in_final = true; /* summed by the k_delta_finalize launch below */
-          } else if (ho_finalize_after) {
-            RAMD_LAUNCH(k_ho_delta_finalize, dim3((sh->H * sh->O + 255) / 256), dim3(256), 0, st, v,
-                               b->ho_slab, ho_ks, accumulate, range_stride ? nullptr : ranges);
-          }
-        }
-      } else if (rows_core < sh->I) {
-        /* The rest rows' planes are compact ([ks_rest][I - rows_core][H], behind the core planes).
-         * This GEMM is a few rows tall and K = S * D deep; measured at the north star its time does
-         * not fall below 17 us for any K split from 16 to 48 (one workgroup per CU and ten K tiles
-         * each, or three per CU and three tiles each: 0.87 us per 64 x 64 x 32 tile step and CU
-         * either way), while every further plane costs the optimiser's sum: 16 it is. */
-        int tmr = (rest_rows + BM - 1) / BM, tnr = (ncol - 1 + BN - 1) / BN;
-        ks_rest = pick_ks(tmr * tnr, nkt, (size_t)RAMD_MAX_REST_PLANES, 1);
-        if (ks_rest > RAMD_MAX_REST_PLANES) ks_rest = RAMD_MAX_REST_PLANES;
-        if (ks_rest > nkt) ks_rest = nkt;
-        while (ks_rest > 1 && (size_t)ks * n + (size_t)ks_rest * rest_plane > b->slab_floats) ks_rest--;
-        if (ks_rest < 1) ks_rest = 1;
-        rest_base = b->slab + (size_t)ks * n;
-        rest_stride = rest_plane;
-        ProbDelta<true> p = {v, row0, nrows, rtiles};
-        if (ho_paired) {
-          int blocks_a, blocks_b;
-          GemmOut oa = make_gemm_out(b->ho_slab, sh->H, sh->O, ho_nkt, ho_ks, 0, 0, 0, &blocks_a);
-          GemmOut ob = make_gemm_out(rest_base - (size_t)rows_core * sh->H, sh->I, ncol, nkt, ks_rest, 1,
-                                     sh->H, rows_core, &blocks_b);
-          ob.zs = rest_stride;
-          int ev2 = timing_begin(st, T_DELTA);
-          RAMD_LAUNCH((k_gemm_pair<ProbHoDelta, ProbDelta<true>>), dim3(blocks_a + blocks_b),
-                             dim3(256), 0, st, ho_p, oa, blocks_a, p, ob);
-          timing_end(st, ev2);
-          ho_paired = false;
-          if (ho_finalize_after && !ranges) {
-            ho_in_final = true; /* summed by the k_delta_finalize launch below */
-          } else if (ho_finalize_after) {
-            RAMD_LAUNCH(k_ho_delta_finalize, dim3((sh->H * sh->O + 255) / 256), dim3(256), 0, st, v,
-                               b->ho_slab, ho_ks, accumulate, range_stride ? nullptr : ranges);
-          }
-        } else {
-          launch_gemm<true, true, ProbDelta<true>>(st, p, rest_base - (size_t)rows_core * sh->H, sh->I, ncol,
-                                                   nkt, ks_rest, T_DELTA, 1, sh->H, rows_core, rest_stride);
-        }
-      }
-    } else if (big && b->uniform_idx >= 0) {
-      ProbDelta<true> p = {v, row0, nrows, rtiles};
-      launch_gemm2<ProbDelta<true>>(st, p, b->slab, sh->I, ncol, nkt, ks, T_DELTA, 1, sh->H);
-    } else if (big) {
-      ProbDelta<false> p = {v, row0, nrows, rtiles};
-      launch_gemm2<ProbDelta<false>>(st, p, b->slab, sh->I, ncol, nkt, ks, T_DELTA, 1, sh->H);
-    } else if (b->uniform_idx >= 0) {
-      ProbDelta<true> p = {v, row0, nrows, rtiles};
-      launch_gemm<true, true, ProbDelta<true>>(st, p, b->slab, sh->I, ncol, nkt, ks, T_DELTA, 1, sh->H);
-    } else {
-      ProbDelta<false> p = {v, row0, nrows, rtiles};
-      launch_gemm<true, true, ProbDelta<false>>(st, p, b->slab, sh->I, ncol, nkt, ks, T_DELTA, 1, sh->H);
-    }
-    size_t n4 = n / 4;
-    if (defer && !accumulate) { /* the optimiser launch that follows sums the slabs itself */
-      defer->slab = b->slab;
-      defer->n = n;
-      defer->ks = ks;
-      defer->H = sh->H;
-      defer->hidden_size = sh->hidden_size;
-      defer->rows_core = rows_core;
-      defer->ks_rest = ks_rest;
-      defer->rest = rest_base == b->slab ? b->slab + (size_t)rows_core * sh->H : rest_base;
-      defer->rest_stride = rest_stride;
-      defer->delta_out = b->ih_delta;
-      return;
-    }
-    if (defer) defer->slab = nullptr;
-    const size_t ho_n = (size_t)sh->H * sh->O;
-    const unsigned fin_blocks = (unsigned)((n4 + 255) / 256) + (ho_in_final ? (unsigned)((ho_n / 4 + 255) / 256) : 0u);
-    RAMD_LAUNCH(k_delta_finalize, dim3(fin_blocks), dim3(256), 0, st, b->ih_delta, b->slab, n4, n, ks,
-                       accumulate, sh->H, sh->hidden_size, rows_core, ks_rest,
-                       rest_base == b->slab ? b->slab + (size_t)rows_core * sh->H : rest_base, rest_stride, b->ho_delta,
-                       ho_in_final ? b->ho_slab : nullptr, ho_n, ho_ks);
-  }
+  const bool ho_direct = c.p.ho_asked && ho_req.done && ho_req.dst == b->ho_delta; /* complete since the chain launch */
+  DeltaPlanes planes = {};
+  bool complete = false;
+  if (c.p.direct_runs)
+    complete = calc_delta_direct(c, owed, &planes);
+  else if (c.p.dma)
+    complete = calc_delta_dma(c, owed, ho_direct, &planes);
+  else
+    planes = calc_delta_generic(c);
+  if (!complete) calc_hand_over(c, planes, owed);
 }
 
 extern "C" void ramd_launch_err_writeback(ramd_stream_t st_, const RamdShape *sh,

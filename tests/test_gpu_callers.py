@@ -318,11 +318,13 @@ def _rnnca_inputs(rs, S, n_in=35):
                                                          # (hidden 512 / 1024: the extras in the one-launch chain's tail --
                                                          # extras_dense_tail -- with whole and with padded 16-stream tiles)
                                                          (512, 48, 7, 33, rc.RESQRT), (512, 33, 5, 46, rc.RELU),
-                                                         (1024, 32, 4, 20, rc.RECLIP20)])
+                                                         (1024, 32, 4, 20, rc.RECLIP20),
+                                                         # (60 inputs, 64 extra columns: past k_extras_dense, the generic GEMM + k_extras_finalize)
+                                                         (64, 9, 4, 60, rc.RELU)])
 def test_dense_input_generation_with_other_shapes(amd, hidden, S, D, n_in, activation):
     """k_extras_dense at its edges: 1 to 47 dense inputs (2 to 48 extra columns: the three 16-column tiles full), h_size
     not a multiple of the 16-deep K chunks, fewer (step, stream) rows than a workgroup takes, every activation's row
-    rule.  (48 inputs and more take the generic GEMM: the rnnca test below at 35, the fuzzer at others.)"""
+    rule.  (48 inputs and more take the generic GEMM: the last case here, the fuzzer at others.)"""
     _rnnca_generation(amd, hidden, S, D, n_in=n_in, activation=activation)
 
 
