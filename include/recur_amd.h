@@ -613,6 +613,26 @@ double rnn_amd_run_text(RecurNN *net, const u8 *text, int len, int skip);
  * without the final negation and division. */
 void rnn_amd_run_text_heads(RecurNN *net, const u8 *text, int len, int skip, int alphabet_len,
                             double *sums);
+/* Many texts against one net in ONE batched device run: the set form of rnn_amd_run_text.  For every k, sums[k] is what
+ * rnn_amd_run_text(c_k, texts[k], lens[k], skips[k]) returns, where c_k is a forward-only clone of `net` whose hidden
+ * row starts as a copy of net's hidden row at the moment of the call -- with one-hot inputs and no bottom layer the
+ * hidden row is the only state that carries from symbol to symbol (charmodel-helpers.h:16-33).  The texts do not see
+ * one another (the reference's text-cross-entropy.c:156-200 carries the net's state from one file into the next, so its
+ * figures depend on the order of its arguments; these do not), noise is 0 and no generator is touched
+ * (charmodel-predict.c:62-76), and `net` itself -- host and device copies, generator included -- is left exactly as it
+ * was.  The clones are state rows of the engine's own, not nets; the texts run side by side, longest first, in waves of
+ * up to 256 rows with one device synchronisation per wave.
+ * skips may be NULL (all zeros); a text with len < 2 scores 0.0; n_texts == 0 returns 0 and touches nothing.
+ * Returns 0, or -1 with a message on stderr and nothing computed (checked before anything needs a device): n_texts < 0,
+ * a NULL array with n_texts > 0, heads that do not divide the output row, a net with a bottom layer -- the layer has
+ * ONE input buffer shared by every clone (recur-nn-init.c:345-346, charmodel-helpers.h:20-31), which leaves
+ * "independent clones" of such a net undefined. */
+int rnn_amd_run_texts(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
+                      double *sums); /* sums[n_texts] */
+/* The same for a net whose output row is output_size / alphabet_len heads (rnn_amd_run_text_heads,
+ * charmodel-multi-predict.c:388-403): sums[k * n_heads + c] is head c's sum for text k. */
+int rnn_amd_run_texts_heads(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
+                            int alphabet_len, double *sums); /* [n_texts][output_size / alphabet_len] */
 /* Block until all queued device work of the library has finished. */
 void rnn_amd_synchronize(void);
 

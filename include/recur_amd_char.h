@@ -142,6 +142,15 @@ int rnn_char_prime(RecurNN *net, RnnCharAlphabet *alphabet, const u8 *text, cons
 double rnn_char_cross_entropy(RecurNN *net, RnnCharAlphabet *alphabet, const u8 *text,
                               const int len, const int ignore_first, const u8 *prefix_text,
                               const int prefix_len);
+/* get_cross_entropy (charmodel-predict.c:62-80) for many texts in one batched device run (rnn_amd_run_texts,
+ * recur_amd.h): primes `net` once with the prefix, if there is one (rnn_char_prime: this DOES move net's state, as
+ * rnn_char_cross_entropy does), then scores every text from the state the net then has, each on its own, and leaves
+ * the net there: entropy[k] = sums[k] / -(double)(lens[k] - ignore_first - 1), the expression rnn_char_cross_entropy
+ * uses (so degenerate lengths give what it gives).  Returns 0 (n_texts == 0: at once, nothing primed), or -1 as
+ * rnn_amd_run_texts does, with nothing primed. */
+int rnn_amd_char_cross_entropy_texts(RecurNN *net, RnnCharAlphabet *alphabet, const u8 *const *texts, const int *lens,
+                                     int n_texts, int ignore_first, const u8 *prefix_text, int prefix_len,
+                                     double *entropy);
 
 /* ---- the multi-head text trainer (charmodel.h:132-152, 242-265;
  *      charmodel-multi-predict.c): py-recur-text.c's Net.train / Net.test backend ---- */

@@ -43,6 +43,30 @@ double rnn_char_cross_entropy(RecurNN *net, RnnCharAlphabet *alphabet, const u8 
   return bits_per_symbol(net, text, len, skip);
 }
 
+/* the same figure for many texts, each scored on its own from the net's (primed) state, in one batched device run */
+int rnn_amd_char_cross_entropy_texts(RecurNN *net, RnnCharAlphabet *alphabet, const u8 *const *texts, const int *lens,
+                                     int n_texts, int skip, const u8 *prefix_text, int prefix_len, double *entropy) {
+  if (ramd_run_texts_refused("rnn_amd_char_cross_entropy_texts", net, texts, lens, n_texts, 0, entropy)) {
+    return -1;
+  }
+  if (n_texts == 0) {
+    return 0;
+  }
+  if (prefix_text) {
+    rnn_char_prime(net, alphabet, prefix_text, prefix_len);
+  }
+  int *skips = malloc((size_t)n_texts * sizeof(int));
+  for (int k = 0; k < n_texts; k++) {
+    skips[k] = skip;
+  }
+  const int r = rnn_amd_run_texts(net, texts, lens, skips, n_texts, entropy);
+  free(skips);
+  for (int k = 0; r == 0 && k < n_texts; k++) {
+    entropy[k] = entropy[k] / -(double)(lens[k] - skip - 1);
+  }
+  return r;
+}
+
 /* ------------------------------------------------------- validation entropy -- */
 
 void rnn_char_init_ventropy(RnnCharVentropy *v, RecurNN *net, const u8 *text, const int len,

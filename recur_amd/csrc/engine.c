@@ -759,7 +759,7 @@ void rnn_amd_host_written(RecurNN *net, int what) { ramd_host_wrote(net, what); 
 
 /* Allocate (or grow) the device image.  Growing evicts everything to the host
  * first and starts over; it only happens when nets are cloned after the first
- * device call. */
+ * device call, or when rnn_amd_run_texts asks for more scratch rows than before. */
 void ramd_engine_ensure_device(RamdEngine *e) {
   ramd_require_device("this call");
   /* the bottom layer is attached after rnn_new returns (recur-nn-init.c:215) */
@@ -771,7 +771,7 @@ void ramd_engine_ensure_device(RamdEngine *e) {
     abort();
   }
   int same_bottom = bI == e->sh.bI && bO == e->sh.bO;
-  if (e->dev_ready && e->sh.Scap >= e->n_streams && e->sh.Fcap >= e->n_fwd && same_bottom) {
+  if (e->dev_ready && e->sh.Scap >= e->n_streams && e->sh.Fcap >= e->n_fwd + e->scratch_fwd && same_bottom) {
     return;
   }
   if (e->dev_ready && e->xchg_world) {
@@ -818,7 +818,7 @@ void ramd_engine_ensure_device(RamdEngine *e) {
   s->b_in = obl ? obl->input_size : 0;
   s->b_out = obl ? obl->output_size : 0;
   s->Scap = (RAMD_MAX(e->n_streams, 1) + 15) / 16 * 16; /* whole 16-row tiles (k_chain_persist's PAD launches run over the rows above a set) */
-  s->Fcap = RAMD_MAX(e->n_fwd, 1);
+  s->Fcap = RAMD_MAX(e->n_fwd + e->scratch_fwd, 1); /* the clones' rows, then the engine's scratch rows (rnn_amd_run_texts) */
   if (s->D < 1) {
     s->D = 1;
   }

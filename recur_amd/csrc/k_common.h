@@ -177,6 +177,40 @@ __device__ __forceinline__ float block_sum_256(float v, float *red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// The input row of one stream, by a workgroup of 256 threads: bias, the previous hidden values from `hid`, the real
+// inputs as `mode` says (recur-nn.c:104-112: kept, a dense row, or the one-hot of `hot`), the padding as it is (zero);
+// then the emergency soft clip of the whole row (maybe_scale_inputs, recur-nn.c:68-81).  The rule is stated here once,
+// for k_assemble (kernels_forward.hip) and the feed half of k_texts_step (kernels_loss.hip).  Every thread of the
+// workgroup calls it (block_sum_256's barriers); red: 4 floats of LDS.
+__device__ __forceinline__ void assemble_input_row(const RamdShape &s, float *slot, const float *hid, int mode, int hot,
+                                                   const float *dense_row, float *red) {
+  const int off = s.hidden_size + 1;
+  float sum = 0.0f;
+  for (int i = threadIdx.x; i < s.I; i += 256) {
+    float x;
+    if (i == 0) {
+      x = 1.0f;
+    } else if (i < off) {
+      x = hid[i];
+    } else if (i < off + s.input_size) {
+      int k = i - off;
+      if (mode == RAMD_IN_KEEP) x = slot[i];
+      else if (mode == RAMD_IN_DENSE) x = dense_row[k];
+      else x = (k == hot) ? 1.0f : 0.0f;
+    } else {
+      x = slot[i]; /* padding: stays as it is (zero) */
+    }
+    slot[i] = x;
+    sum += x;
+  }
+  sum = block_sum_256(sum, red);
+  float softclip = s.I * INPUT_MEAN_SOFT_TOP_F;
+  if (sum > softclip) {
+    float scale = soft_clip_dev(sum, softclip);
+    for (int i = threadIdx.x; i < s.I; i += 256) slot[i] *= scale;
+  }
+}
+
 __device__ __forceinline__ float4 ld4(const float *p) {
   return *reinterpret_cast<const float4 *>(p);
 }

@@ -40,7 +40,6 @@ __global__ __launch_bounds__(256) void k_assemble(View v, int row0, int mode,
     slot = input_row(v, r, 0);
   }
   const float *hid = v.b.hidden + (size_t)r * s.H;
-  int off = s.hidden_size + 1;
   int hot = -1;
   if (mode == RAMD_IN_ONE_HOT) {
     hot = v.b.hot[r];
@@ -53,30 +52,7 @@ __global__ __launch_bounds__(256) void k_assemble(View v, int row0, int mode,
     hot = v.b.text[o];
     if (threadIdx.x == 0) v.b.target[r] = v.b.text[o + 1];
   }
-  float sum = 0.0f;
-  for (int i = threadIdx.x; i < s.I; i += 256) {
-    float x;
-    if (i == 0) {
-      x = 1.0f;
-    } else if (i < off) {
-      x = hid[i];
-    } else if (i < off + s.input_size) {
-      int k = i - off;
-      if (mode == RAMD_IN_KEEP) x = slot[i];
-      else if (mode == RAMD_IN_DENSE) x = dense[(size_t)j * ld + k];
-      else x = (k == hot) ? 1.0f : 0.0f;
-    } else {
-      x = slot[i]; /* padding: stays as it is (zero) */
-    }
-    slot[i] = x;
-    sum += x;
-  }
-  sum = block_sum_256(sum, red);
-  float softclip = s.I * INPUT_MEAN_SOFT_TOP_F;
-  if (sum > softclip) {
-    float scale = soft_clip_dev(sum, softclip);
-    for (int i = threadIdx.x; i < s.I; i += 256) slot[i] *= scale;
-  }
+  assemble_input_row(s, slot, hid, mode, hot, mode == RAMD_IN_DENSE ? dense + (size_t)j * ld : nullptr, red);
 }
 
 // plain "sum the K slabs" finalize: dst[r][c] (+)= sum_z slab[z][r][c]

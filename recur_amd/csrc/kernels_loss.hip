@@ -680,6 +680,54 @@ __global__ __launch_bounds__(64) void k_multi_xent_accumulate(View v, int r, int
   acc[c] += (double)capped_log2f_dev(e);
 }
 
+// The one launch between two forward passes of rnn_amd_run_texts (texts_api.c): N texts of different lengths through one
+// net, a state row each, the rows ordered longest text first (texts_plan.h) so that the rows still running are a prefix.
+// One workgroup per row, two halves:
+//   score step t_score, rows [0, a_score) from the row's skip on: what k_xent_accumulate / k_multi_xent_accumulate do --
+//     softmax of the output row, or of each of its n_sums heads of alen outputs (a wave per head, the heads shared out over
+//     the waves; badmaths.h:71-111, the sum in the reference's order), capped log2 of the probability of the text's next
+//     symbol added to the row's own double(s).  An accumulator has one writer: no atomics.
+//   feed step t_feed, rows [0, a_feed): the input row of the next forward pass -- assemble_input_row with the one-hot of
+//     text[t_feed] (charmodel-helpers.h:16-33).  The hidden values come from the row's own hidden row, or, in a wave's
+//     first launch, from hid0: the hidden row of the net the texts are scored against, which every text starts from.
+// a_score == 0: a wave's first launch, which only feeds; a_feed == 0: its last, which only scores.
+struct TextsStep {
+  const unsigned char *text;     /* the wave's texts behind one another           */
+  const unsigned long long *off; /* [rows] where row j's text starts              */
+  const int *skip;               /* [rows] steps fed but not scored               */
+  double *acc;                   /* [rows][n_sums] running sums                   */
+  const float *hid0;             /* the hidden row of the first feed, or nullptr   */
+  int row0;                      /* state row of the wave's row 0 (forward-only)  */
+  int alen, n_sums;
+  int t_score, a_score, t_feed, a_feed;
+};
+constexpr int TS_WAVES = 4;
+__global__ __launch_bounds__(64 * TS_WAVES) void k_texts_step(View v, TextsStep p) {
+  extern __shared__ float tex[]; /* [TS_WAVES][alen rounded up to 4] exponentials */
+  __shared__ float red[4];
+  const RamdShape &s = v.sh;
+  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const unsigned char *text = p.text + p.off[j];
+  if (j < p.a_score && p.t_score >= p.skip[j]) {
+    const int target = text[p.t_score + 1];
+    float *ex = tex + wave * ((p.alen + 3) & ~3);
+    for (int c = wave; c < p.n_sums; c += TS_WAVES) {
+      const float *src = v.b.out + (size_t)r * s.O + (size_t)c * p.alen;
+      const float adj = softmax_shift_of(src, p.alen, lane);
+      for (int i = lane; i < p.alen; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
+      FenceOneWave{}();
+      if (lane == 0) { /* (a symbol outside the head has no probability: the cap) */
+        const float e = target < p.alen ? ex[target] / ordered_sum(ex, p.alen) : 0.0f;
+        p.acc[(size_t)j * p.n_sums + c] += (double)capped_log2f_dev(e);
+      }
+      FenceOneWave{}(); /* before this wave's next head rewrites ex */
+    }
+  }
+  if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
+    assemble_input_row(s, input_row(v, r, 0), p.hid0 ? p.hid0 : v.b.hidden + (size_t)r * s.H, RAMD_IN_ONE_HOT,
+                       text[p.t_feed], nullptr, red);
+}
+
 // rnnca's loss (gstrnnca.c:701-714, train_net): fast_sigmoid_array(answer, answer, n) IN
 // PLACE on the first n outputs (badmaths.h:33-44), then o_error[i] = a (1 - a) (target - a).
 // One thread per (stream, output); the rest of the error row stays as it was (zero).
@@ -772,6 +820,28 @@ extern "C" void ramd_launch_multi_xent_accumulate(ramd_stream_t st_, const RamdS
   View v = make_view(sh, b);
   RAMD_LAUNCH(k_multi_xent_accumulate, dim3(n_classes), dim3(64), (size_t)alphabet_len * sizeof(float), st,
               v, row, alphabet_len, acc, count_it);
+}
+
+extern "C" void ramd_launch_texts_step(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
+                                       const unsigned char *text, const unsigned long long *off, const int *skip,
+                                       double *acc, const float *hid0, int alphabet_len, int n_sums, int t_score,
+                                       int a_score, int t_feed, int a_feed) {
+  const int rows = a_score > a_feed ? a_score : a_feed;
+  if (rows < 1) return;
+  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
+    fprintf(stderr, "librecur_amd: ramd_launch_texts_step: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
+    abort();
+  }
+  hipStream_t st = (hipStream_t)st_;
+  View v = make_view(sh, b);
+  const size_t shm = (size_t)TS_WAVES * ((alphabet_len + 3) & ~3) * sizeof(float);
+  if (shm > 160 * 1024 - 64) {
+    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", alphabet_len);
+    abort();
+  }
+  if (shm > 64 * 1024) raise_lds_limit<k_texts_step>(160 * 1024 - 64);
+  TextsStep p = {text, off, skip, acc, hid0, row0, alphabet_len, n_sums, t_score, a_score, t_feed, a_feed};
+  RAMD_LAUNCH(k_texts_step, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
 }
 
 extern "C" void ramd_launch_sigmoid_mse_error(ramd_stream_t st_, const RamdShape *sh,

@@ -240,6 +240,16 @@ void ramd_launch_multi_softmax_error(ramd_stream_t st, const RamdShape *sh, cons
 void ramd_launch_multi_xent_accumulate(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
                                        int row, int alphabet_len, int n_classes, double *acc,
                                        int count_it);
+/* the launch between two forward passes of rnn_amd_run_texts, for a wave of texts on forward-only state rows row0 ...
+ * (texts_plan.h's order): scores step t_score on the wave's first a_score rows (the log2 probability of text[t_score + 1]
+ * added to acc[row][n_sums], one sum for the whole output row when n_sums == 1, else one per head of alphabet_len
+ * outputs; rows with skip[row] > t_score left out) and builds the input rows of step t_feed for its first a_feed rows
+ * (one-hot of text[t_feed] on the row's hidden values, or on hid0's when that is not NULL).  All pointers are device
+ * pointers; off[row] is where the row's text starts in `text`.  a_score or a_feed may be 0. */
+void ramd_launch_texts_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
+                            const unsigned char *text, const unsigned long long *off, const int *skip, double *acc,
+                            const float *hid0, int alphabet_len, int n_sums, int t_score, int a_score, int t_feed,
+                            int a_feed);
 /* rnnca's loss (gstrnnca.c:701-714): sigmoid in place on the first n outputs, slope * (target -
  * a) into o_error; targets is a device array [nrows][ld] */
 void ramd_launch_sigmoid_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,

@@ -40,6 +40,9 @@ typedef struct RamdEngine {
   RecurNN **streams;
   int n_fwd, cap_fwd;
   RecurNN **fwd;
+  /* forward-only state rows of the engine's own, behind the clones' (rows Scap + n_fwd ...): where rnn_amd_run_texts
+   * runs its batch.  The widest batch so far; the device image keeps room for that many (ramd_engine_ensure_device) */
+  int scratch_fwd;
   int dev_ready;
   /* coherence of the engine-level array classes (RNN_AMD_WEIGHTS, _MOMENTUMS,
    * _DELTAS): bit set = that copy is current */
@@ -210,6 +213,11 @@ void ramd_check_method_arrays(RamdEngine *e, int method);
 int ramd_update_rule(const RecurNNBPTT *bptt, int learning_style, float momentum, float *mw, float *rate, float *ho_rate);
 void ramd_apply_learning(RecurNN *net, int learning_method, float momentum, const RamdPendingDelta *pend);
 void ramd_fused_net_update(RamdEngine *e, RecurNN *net, int row, unsigned batch_size);
+
+/* texts_api.c: the refusals of rnn_amd_run_texts / _heads (alphabet_len 0: no heads), which need no device: -1 with a
+ * message on stderr, else 0 */
+int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const *texts, const int *lens, int n_texts,
+                           int alphabet_len, const void *out);
 
 /* set_api.c */
 void ramd_set_need_training(const RnnAmdSet *set, const char *what);

@@ -1,0 +1,150 @@
+/* texts_api.c -- many texts against one net in one batched device run (gnu11 C): rnn_amd_run_texts and
+ * rnn_amd_run_texts_heads, the set form of rnn_amd_run_text / _heads (net_api.c).  Where those feed one net a symbol per
+ * launch sequence, these give every text a forward-only state row of the engine's own and run the rows together: which
+ * text gets which row, in how many waves and with how many rows at each step is texts_plan.h's business; between two
+ * forward passes of the rows there is one launch (k_texts_step, kernels_loss.hip) that scores the step just computed and
+ * builds the input rows of the next.  The net the caller passes is read -- its weights, its hidden row -- and not written. */
+#define RAMD_HIP_HOST 1
+#include "rnn_host.h"
+#include "texts_plan.h"
+
+int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const *texts, const int *lens, int n_texts,
+                           int alphabet_len, const void *out) {
+  if (!net || n_texts < 0) {
+    fprintf(stderr, "librecur_amd: %s: %d texts\n", who, n_texts);
+    return -1;
+  }
+  if (net->bottom_layer) {
+    /* the layer has ONE input buffer for every clone (recur-nn-init.c:345-346; RamdBuffers.blast): "independent clones
+     * of the net" is not a state the reference can be in */
+    fprintf(stderr, "librecur_amd: %s: the net has a bottom layer, whose one shared input buffer leaves independent "
+                    "clones undefined\n", who);
+    return -1;
+  }
+  if (alphabet_len && (alphabet_len < 0 || net->output_size % alphabet_len != 0)) {
+    fprintf(stderr, "librecur_amd: %s: %d outputs are not whole heads of %d\n", who, net->output_size, alphabet_len);
+    return -1;
+  }
+  if (n_texts > 0 && (!texts || !lens || !out)) {
+    fprintf(stderr, "librecur_amd: %s: a NULL array for %d texts\n", who, n_texts);
+    return -1;
+  }
+  for (int k = 0; k < n_texts; k++) {
+    if (lens[k] >= 2 && !texts[k]) {
+      fprintf(stderr, "librecur_amd: %s: text %d is NULL\n", who, k);
+      return -1;
+    }
+  }
+  return 0;
+}
+
+/* one wave of the plan on the state rows from r0 on; the d_* arrays have room for the plan's first (largest) wave, the
+ * h_* ones are the pinned-or-not host sides of them and stay untouched until the wave's synchronisation */
+typedef struct TextsBuffers {
+  u8 *h_text, *d_text;
+  unsigned long long *h_off, *d_off;
+  int *d_skip;
+  double *h_acc, *d_acc;
+} TextsBuffers;
+
+static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, int w, const u8 *const *texts, int r0,
+                     int alphabet_len, int n_sums, const TextsBuffers *tb, double *sums) {
+  const RamdShape *s = &e->sh;
+  const TextsWave *wave = &plan->waves[w];
+  const int n = wave->nrows;
+  size_t at = 0;
+  for (int j = 0; j < n; j++) {
+    const int len = plan->len[wave->row0 + j];
+    tb->h_off[j] = at;
+    memcpy(tb->h_text + at, texts[plan->order[wave->row0 + j]], (size_t)len);
+    at += (size_t)len;
+  }
+  ramd_h2d(tb->d_text, tb->h_text, at);
+  ramd_h2d(tb->d_off, tb->h_off, (size_t)n * sizeof(unsigned long long));
+  ramd_h2d(tb->d_skip, plan->skip + wave->row0, (size_t)n * sizeof(int));
+  HIP_OK(hipMemsetAsync(tb->d_acc, 0, (size_t)n * n_sums * sizeof(double), ramd_stream));
+  /* every row starts from the net's hidden row: the first launch builds the input rows from it */
+  const float *hid0 = e->b.hidden + (size_t)ramd_state_row(e, ramd_priv(net)) * s->H;
+  int scored = 0; /* a(t - 1): the rows whose step t - 1 waits to be scored */
+  for (int t = 0; t <= wave->steps; t++) {
+    const int a = t < wave->steps ? texts_plan_active(plan, w, t) : 0;
+    ramd_launch_texts_step(ramd_stream, s, &e->b, r0, tb->d_text, tb->d_off, tb->d_skip, tb->d_acc, t == 0 ? hid0 : NULL,
+                           alphabet_len ? alphabet_len : s->output_size, n_sums, t - 1, scored, t, a);
+    if (a) {
+      ramd_launch_forward(ramd_stream, s, &e->b, r0, a, 0.0f);
+    }
+    scored = a;
+  }
+  ramd_d2h(tb->h_acc, tb->d_acc, (size_t)n * n_sums * sizeof(double));
+  ramd_dsync(); /* the wave's one synchronisation */
+  for (int j = 0; j < n; j++) {
+    memcpy(sums + (size_t)plan->order[wave->row0 + j] * n_sums, tb->h_acc + (size_t)j * n_sums, (size_t)n_sums * sizeof(double));
+  }
+}
+
+static int run_texts(const char *who, RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
+                     int alphabet_len, double *sums) {
+  if (ramd_run_texts_refused(who, net, texts, lens, n_texts, alphabet_len, sums)) {
+    return -1;
+  }
+  const int n_sums = alphabet_len ? net->output_size / alphabet_len : 1;
+  for (size_t q = 0; q < (size_t)n_texts * n_sums; q++) {
+    sums[q] = 0.0;
+  }
+  TextsPlan plan;
+  if (texts_plan_make(&plan, lens, skips, n_texts, TEXTS_PLAN_WIDTH)) {
+    fprintf(stderr, "librecur_amd: %s: out of memory planning %d texts\n", who, n_texts);
+    return -1;
+  }
+  if (plan.n_rows == 0) { /* nothing to score: no device is asked for */
+    return 0;
+  }
+  RamdEngine *e = ramd_engine_of(net);
+  const int widest = plan.waves[0].nrows;
+  if (e->scratch_fwd < widest) {
+    e->scratch_fwd = widest; /* the image grows once (every net's state survives: ramd_engine_ensure_device) */
+  }
+  ramd_engine_ensure_device(e);
+  ramd_engine_need_dev(e, RNN_AMD_WEIGHTS);
+  ramd_stream_need_dev(e, net);
+  ramd_set_uniform_idx(e, e->n_streams, 0); /* forward-only rows: no ring position */
+  const int r0 = e->sh.Scap + e->n_fwd; /* the engine's scratch rows lie behind the clones' */
+  size_t bytes = 0;
+  for (int j = 0; j < widest; j++) {
+    bytes += (size_t)plan.len[j];
+  }
+  TextsBuffers tb;
+  tb.h_text = ramd_zalloc(bytes);
+  tb.h_off = ramd_zalloc((size_t)widest * sizeof(unsigned long long));
+  tb.h_acc = ramd_zalloc((size_t)widest * n_sums * sizeof(double));
+  tb.d_text = ramd_dev_alloc(bytes);
+  tb.d_off = ramd_dev_alloc((size_t)widest * sizeof(unsigned long long));
+  tb.d_skip = ramd_dev_alloc((size_t)widest * sizeof(int));
+  tb.d_acc = ramd_dev_alloc((size_t)widest * n_sums * sizeof(double));
+  for (int w = 0; w < plan.n_waves; w++) {
+    run_wave(e, net, &plan, w, texts, r0, alphabet_len, n_sums, &tb, sums);
+  }
+  ramd_dev_free(tb.d_text);
+  ramd_dev_free(tb.d_off);
+  ramd_dev_free(tb.d_skip);
+  ramd_dev_free(tb.d_acc);
+  free(tb.h_text);
+  free(tb.h_off);
+  free(tb.h_acc);
+  texts_plan_free(&plan);
+  return 0;
+}
+
+int rnn_amd_run_texts(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
+                      double *sums) {
+  return run_texts("rnn_amd_run_texts", net, texts, lens, skips, n_texts, 0, sums);
+}
+
+int rnn_amd_run_texts_heads(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
+                            int alphabet_len, double *sums) {
+  if (alphabet_len < 1) {
+    fprintf(stderr, "librecur_amd: rnn_amd_run_texts_heads: heads of %d outputs\n", alphabet_len);
+    return -1;
+  }
+  return run_texts("rnn_amd_run_texts_heads", net, texts, lens, skips, n_texts, alphabet_len, sums);
+}

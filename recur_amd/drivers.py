@@ -3,7 +3,8 @@
 ``ApiSet`` drives a library that speaks the recur-nn.h ABI (librecur_amd.so through its per-net drop-in calls; the
 tests also point it at the compiled reference) exactly the way the reference's own caller does (rnn_char_epoch,
 charmodel-predict.c:288-311).  ``AmdBatchedSet`` drives the additive batched entry points (include/recur_amd.h
-part 2): the whole set per call, text on the device.  ``synthetic_text_np`` is the seeded symbol stream of
+part 2): the whole set per call, text on the device.  ``run_texts`` scores a list of encoded texts against one net in
+one batched call (rnn_amd_run_texts / _heads).  ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
 """
@@ -43,6 +44,34 @@ def synthetic_text_np(n=6000, alphabet=42, seed=7):
         out[i] = int(x * alphabet)
     return out
 
+
+
+def text_pointers(texts):
+    """(arrays kept alive, u8 *const *texts, int *lens) for a list of numpy uint8 arrays."""
+    keep = [np.ascontiguousarray(t, dtype=np.uint8) for t in texts]
+    ptrs = (rc.c_u8_p * max(len(keep), 1))(*[rc.u8ptr(t) if len(t) else None for t in keep])
+    lens = np.array([len(t) for t in keep], np.int32)
+    return keep, ptrs, lens
+
+
+def run_texts(lib, net, texts, skips=None, alphabet_len=0):
+    """rnn_amd_run_texts for a list of numpy uint8 arrays: the array of their sums of log2 p, each text scored on its
+    own from the net's current hidden state.  With alphabet_len the net's output row is heads of that many symbols
+    (rnn_amd_run_texts_heads) and the result is [len(texts)][heads]."""
+    keep, ptrs, lens = text_pointers(texts)
+    sk = None if skips is None else np.ascontiguousarray(skips, dtype=np.int32)
+    assert sk is None or len(sk) == len(keep)
+    heads = net.contents.output_size // alphabet_len if alphabet_len else 1
+    sums = np.full((len(keep), heads), np.nan)
+    out = sums.ctypes.data_as(C.POINTER(C.c_double))
+    skp = None if sk is None else rc.iptr(sk)
+    if alphabet_len:
+        r = lib.rnn_amd_run_texts_heads(net, ptrs, rc.iptr(lens), skp, len(keep), alphabet_len, out)
+    else:
+        r = lib.rnn_amd_run_texts(net, ptrs, rc.iptr(lens), skp, len(keep), out)
+    if r != 0:
+        raise ValueError("rnn_amd_run_texts refused the batch (see stderr)")
+    return sums if alphabet_len else sums[:, 0]
 
 
 class ApiSet:
