@@ -9,8 +9,6 @@
 #include "ramd_internal.h"
 #include "k_tiles.h"
 
-int env_int(const char *name, int dflt); /* the switches (kernels_support.hip; the test's harness has its own) */
-
 constexpr int DNW = 8, DP = 5; /* k_delta_direct: waves per workgroup, K quads in flight per wave */
 
 enum CalcTop { TOP_DONE, TOP_SPARSE, TOP_HEADS, TOP_RANGED, TOP_PLAIN };

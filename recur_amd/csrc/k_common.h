@@ -460,12 +460,6 @@ static inline View make_view(const RamdShape *sh, const RamdBuffers *b) {
   return v;
 }
 
-// segments of the hidden row in the output-layer kernels (k_out_layer, k_text_top)
-constexpr int OUT_SEGS = 16;
-// 64 x 64 tiles of the wide chain step and the wide forward GEMM (k_chain_wide, k_fwd_wide)
-constexpr int WM = 64, WN = 64, WK = 64, W_STAGES = 4;
-constexpr int W_STAGE_FLOATS = (WM + WN) * WK; /* 32 KB */
-
 // ---- development builds (tools/mkabl.sh bnd -DBND_STAMPS -- NOT with -DPC_STAMPS: the half-step stamps of one workgroup slow its
 // whole row tile down, 6.5 us per chain launch): when every workgroup of a launch starts and ends, by the 100 MHz
 // clock all CUs share -- tools/gpu_boundary_stamps.py turns the four launches' marks into what the launch boundaries of a

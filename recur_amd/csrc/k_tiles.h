@@ -1,4 +1,4 @@
-// k_tiles.h -- the tile sizes that both the kernels and the launchers' planning (calc_plan.h) read, and the split-K
+// k_tiles.h -- the tile sizes that both the kernels and the launchers' planning (calc_plan.h, fwd_plan.h) read, and the split-K
 // rule.  No HIP here: the host compiler alone can include it.
 #pragma once
 #include <stddef.h>
@@ -12,6 +12,15 @@ constexpr int RAMD_MAX_REST_PLANES = 64;
 constexpr int THP_ROWS = 128;   /* k_top_heads_partial: rows of W_ho per workgroup */
 constexpr int XD_NT = 3;        /* k_extras_dense: column tiles of 16 */
 constexpr int DD_FLAG_LOADS = 8; /* k_delta_direct: 4 x 256 streams of n_exec, of ih_scale */
+constexpr int OUT_SEGS = 16;    /* segments of the hidden row in the output-layer kernels (k_out_layer, k_text_top) */
+/* 64 x 64 tiles of the wide chain step and the wide forward GEMM (k_chain_wide, k_fwd_wide) */
+constexpr int WM = 64, WN = 64, WK = 64, W_STAGES = 4;
+constexpr int W_STAGE_FLOATS = (WM + WN) * WK; /* 32 KB */
+constexpr int FF_MAXIN = 64;    /* k_fwd_fused: dense input columns at most */
+
+/* the RECUR_AMD_* switches, which the plans read: kernels_support.hip in the library (k_common.h declares it hidden there,
+ * the version script keeps it unexported); the plans' test harnesses have their own */
+int env_int(const char *name, int dflt);
 
 // Split-K factor: enough workgroups to give every CU two or three, without
 // shredding K into single tiles.

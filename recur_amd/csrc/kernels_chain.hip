@@ -1249,28 +1249,14 @@ static void launch_chain_persist_k(hipStream_t st, const View *d_view, const Ram
    * not beside this process's own side streams); 0: a ticket per workgroup */
   const int use_static = g_seat_table ? 2 : (g_xcd_static && !g_side_streams) ? 1 : 0;
   const unsigned tseq = use_static ? 0u : ++g_ticket_launches;
-  static bool attr_set = false;
-  if (!attr_set) {
-    HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_persist<ACT, K, false>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, pc_lds_bytes(K)));
-    HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_persist<ACT, K, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, pc_lds_bytes(K)));
-    HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_persist<ACT, K, true, true>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, pc_lds_bytes(K)));
-    attr_set = true;
-  }
+  raise_lds_limit<k_chain_persist<ACT, K, false>>(pc_lds_bytes(K));
+  raise_lds_limit<k_chain_persist<ACT, K, true>>(pc_lds_bytes(K));
+  raise_lds_limit<k_chain_persist<ACT, K, true, true>>(pc_lds_bytes(K));
   if constexpr (K >= 512) {
     if (xc.on && xc.dense) { /* the tail for dense inputs */
-      static bool attr_xd = false;
-      if (!attr_xd) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)(k_chain_persist<ACT, K, false, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, pc_lds_bytes(K)));
-        HIP_CHECK(hipFuncSetAttribute((const void *)(k_chain_persist<ACT, K, true, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, pc_lds_bytes(K)));
-        HIP_CHECK(hipFuncSetAttribute((const void *)(k_chain_persist<ACT, K, true, true, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, pc_lds_bytes(K)));
-        attr_xd = true;
-      }
+      raise_lds_limit<k_chain_persist<ACT, K, false, false, true>>(pc_lds_bytes(K));
+      raise_lds_limit<k_chain_persist<ACT, K, true, false, true>>(pc_lds_bytes(K));
+      raise_lds_limit<k_chain_persist<ACT, K, true, true, true>>(pc_lds_bytes(K));
       if (one && (nvalid < nrows || vlo > 0))
         RAMD_LAUNCH((k_chain_persist<ACT, K, true, true, true>), dim3(256), dim3(512), pc_lds_bytes(K), st, d_view,
                     b->uniform_idx, row0, nrows, sh->D, seq, g_chain_sync, g_chain_abort_dev, nvalid, vlo, hw, xc, (int)use_static, tseq, g_seats);
@@ -1432,17 +1418,13 @@ int ramd_chain_steps(hipStream_t st, const View &v, const RamdShape *sh, const R
                     (wide_ns == 16 || wide_ns == 24 || wide_ns == 32) &&
                     ((nrows / WM) * (sh->hidden_size / WN) >= 128 || wide_half) && env_int("RECUR_AMD_CHAIN_WIDE", 1);
   if (wide) {
-    static bool attr_set = false;
     const size_t shm = (size_t)W_STAGES * W_STAGE_FLOATS * sizeof(float);
-    if (!attr_set) {
-      HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_wide<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_wide<24>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_wide<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      HIP_CHECK(hipFuncSetAttribute((const void *)(k_chain_wide<16, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      HIP_CHECK(hipFuncSetAttribute((const void *)(k_chain_wide<24, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      HIP_CHECK(hipFuncSetAttribute((const void *)(k_chain_wide<32, 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      attr_set = true;
-    }
+    raise_lds_limit<k_chain_wide<16>>((int)shm);
+    raise_lds_limit<k_chain_wide<24>>((int)shm);
+    raise_lds_limit<k_chain_wide<32>>((int)shm);
+    raise_lds_limit<k_chain_wide<16, 32>>((int)shm);
+    raise_lds_limit<k_chain_wide<24, 32>>((int)shm);
+    raise_lds_limit<k_chain_wide<32, 32>>((int)shm);
     const int wtm = nrows / (wide_half ? 32 : WM), wtn = sh->hidden_size / WN;
     const int wblocks = ((wtn + 7) / 8) * 8 * wtm;
     tn_parts = wtn;

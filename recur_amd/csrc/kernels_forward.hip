@@ -2,6 +2,7 @@
 // presynaptic noise, the bottom layer, the hidden-layer GEMM in its four forms and the output layer.
 #include "k_common.h"
 #include "k_gemm.h"
+#include "fwd_plan.h"
 
 // ------------------------------------------------------------ K0: advance --
 
@@ -511,7 +512,6 @@ extern "C" void ramd_fwd_stamps(unsigned long long *out) {
 #define FF_STAMP(i) do { } while (0)
 #endif
 BND_DECL(g_bnd_fwd, ramd_bnd_fwd_stamps)
-constexpr int FF_MAXIN = 64;
 template <int NS = 0>
 __global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, int new_idx, int row0,
                                                    int nrows, int tm, int tn, int nstages_arg,
@@ -1046,214 +1046,123 @@ __global__ __launch_bounds__(256) void k_out_layer_o4(View v, int row0, int nrow
 }
 #pragma clang fp contract(fast)
 
-extern "C" void ramd_launch_advance(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b,
-                                    int row0, int nrows) {
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  RAMD_LAUNCH(k_advance, dim3((nrows + 255) / 256), dim3(256), 0, st, v, row0, nrows);
-}
+// ------------------------------------------------- the pass: plan, then a short function per stage --
+// fwd_plan.h decides; what follows launches what the plan says, each kernel from one place.
 
-extern "C" void ramd_launch_assemble(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b,
-                                     int row0, int nrows, int mode, const float *dense, int ld,
-                                     int text_i, int global_first, int n_set, int advance) {
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  RAMD_LAUNCH(k_assemble, dim3(nrows), dim3(256), 0, st, v, row0, mode, dense, ld, text_i,
-                     global_first, n_set, advance);
+template <int NS>
+static void launch_fwd_wide_ns(hipStream_t st, const View *d_view, const RamdBuffers *b, int row0, int nrows, const FwdTiles &t,
+                               const WideOp &op) {
+  const size_t shm = (size_t)W_STAGES * W_STAGE_FLOATS * sizeof(float);
+  raise_lds_limit<k_fwd_wide<NS>>((int)shm);
+  RAMD_LAUNCH(k_fwd_wide<NS>, dim3(t.blocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, t.tm, t.tn, op);
 }
-
-extern "C" void ramd_launch_bottom_forward(ramd_stream_t st_, const RamdShape *sh,
-                                           const RamdBuffers *b, int row0, int nrows, int mode,
-                                           const float *dense, int ld, int text_i,
-                                           int global_first, int n_set, float noise) {
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  size_t shm = (size_t)(sh->bI + sh->bO) * sizeof(float);
-  RAMD_LAUNCH(k_bottom_forward, dim3(nrows), dim3(256), shm, st, v, row0, mode, dense, ld,
-                     text_i, global_first, n_set, noise);
-}
-
-/* assemble + hidden layer in one launch for the text step (k_fwd_fused); returns what
- * ramd_launch_text_top wants as fwd_ks (negative: one plane of sums + per-tile padding
- * partials), or 0 when the preconditions do not hold and nothing was launched */
-extern "C" int ramd_launch_forward_fused(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b,
-                                         int row0, int nrows, int mode, int text_i,
-                                         int global_first, int n_set, int for_top, const float *dense, int ld) {
-  /* for_top: the text step, which stops after the hidden layer's sums (k_text_top takes them from there); otherwise a
-   * one-hot or text pass that goes on to ramd_launch_forward_finish */
-  const bool dense_ok = mode == RAMD_IN_DENSE && dense && sh->input_size <= FF_MAXIN && env_int("RECUR_AMD_FWD_FUSED_DENSE", 1);
-  if (b->uniform_idx < 0 || sh->bI || sh->hidden_size % CN != 0 || row0 + nrows > sh->Scap ||
-      (for_top ? ((mode != RAMD_IN_TEXT && !dense_ok) || !ramd_text_top_ok(sh))
-               : ((mode != RAMD_IN_TEXT && mode != RAMD_IN_ONE_HOT && !dense_ok) || !env_int("RECUR_AMD_FWD_FUSED_ANY", 1))) ||
-      env_int("RECUR_AMD_NO_FWD_FUSED", 0)) {
-    return 0;
-  }
-  const int tm = (nrows + CM - 1) / CM, tn = sh->hidden_size / CN;
-  /* dense inputs: where the 32 x 32 tiles are one round of workgroups (gstclassify's 512 / 128: 64 tiles; one launch less,
-   * the time of assemble + GEMM).  Beyond that the tiles' operand traffic decides -- 8 flop per byte from L2: 67.7 us at
-   * 2048 / 512 (1024 tiles) against 58.7 + 6.3 us for k_assemble and the 128 x 128 tiles of k_gemm */
-  if (mode == RAMD_IN_DENSE && tm * tn > 256) return 0;
-  /* plane 0: sums; plane 1: [tn][nrows][4] padding partials */
-  if ((size_t)nrows * sh->H + (size_t)tn * nrows * 4 > b->slab_floats || tn * 4 > sh->H) return 0;
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
+/* op.a == nullptr: the hidden layer's operands, from the View */
+static void launch_fwd_wide(hipStream_t st, const View &v, const RamdBuffers *b, int row0, int nrows, const FwdTiles &t,
+                            const WideOp &op, int cls) {
   const View *d_view = device_view(st, v);
-  const int nstages = (sh->hidden_size + CK - 1) / CK;
-  const int blocks = ((tn + 7) / 8) * 8 * tm;
-  int ev = timing_begin(st, T_FWD);
-  const bool exact = sh->hidden_size % CK == 0;
-#define FWD_FUSED(NS)                                                                              \
-  RAMD_LAUNCH((k_fwd_fused<NS>), dim3(blocks), dim3(512), 0, st, d_view, b->uniform_idx, row0, \
-                     nrows, tm, tn, nstages, mode, text_i, global_first, n_set, dense, ld)
-  if (exact && nstages == 8) FWD_FUSED(8);
-  else if (exact && nstages == 4) FWD_FUSED(4);
-  else if (exact && nstages == 2) FWD_FUSED(2);
-  else if (exact && nstages == 16) FWD_FUSED(16);
-  else FWD_FUSED(0);
-#undef FWD_FUSED
+  int ev = timing_begin(st, cls);
+  if (t.ns == 33) launch_fwd_wide_ns<33>(st, d_view, b, row0, nrows, t, op);
+  else if (t.ns == 17) launch_fwd_wide_ns<17>(st, d_view, b, row0, nrows, t, op);
+  else launch_fwd_wide_ns<9>(st, d_view, b, row0, nrows, t, op);
   timing_end(st, ev);
-  return -tn;
 }
 
-extern "C" int ramd_launch_forward_hidden(ramd_stream_t st_, const RamdShape *sh,
-                                          const RamdBuffers *b, int row0, int nrows, float noise,
-                                          int leave_slabs);
-
-/* rnn_opinion's device work for one stream of a small net in one launch (k_fwd_small); returns 0
- * when the shape is not its kind and nothing was launched */
-extern "C" int ramd_launch_forward_small(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int r) {
-  if (sh->H > 256 || sh->I > 512 || sh->O > 64 || sh->bI || !env_int("RECUR_AMD_FWD_SMALL", 1)) return 0;
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  int ev = timing_begin(st, T_FWD);
-  RAMD_LAUNCH(k_fwd_small, dim3(1), dim3(1024), 0, st, v, r);
-  timing_end(st, ev);
-  return 1;
+template <int NS>
+static void launch_fwd_fused_ns(hipStream_t st, const View *d_view, const RamdBuffers *b, const RamdFwdCall *c, const FwdPlan &p) {
+  RAMD_LAUNCH((k_fwd_fused<NS>), dim3(p.ht.blocks), dim3(512), 0, st, d_view, b->uniform_idx, c->row0, c->nrows, p.ht.tm,
+              p.ht.tn, p.nstages, c->mode, c->text_i, c->global_first, c->global_count, c->dense, c->ld);
 }
 
-static void launch_output_layer(hipStream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows);
-
-extern "C" void ramd_launch_forward(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b,
-                                    int row0, int nrows, float noise) {
-  ramd_launch_forward_hidden(st_, sh, b, row0, nrows, noise, 0);
-  launch_output_layer((hipStream_t)st_, sh, b, row0, nrows);
-}
-
-/* what follows ramd_launch_forward_fused(for_top = 0): the sums' tail columns, the noise generated ahead
- * (b->noise_spec_use), the activation; then the output layer */
-extern "C" void ramd_launch_forward_finish(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
-                                           int nrows, int fused, int part) {
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  if (part != 2) { /* the hidden layer's end */
-    const int nmain = (nrows * (sh->H / 4 - 1) + 255) / 256;
-    RAMD_LAUNCH(k_fwd_finalize_fused, dim3(nmain + (nrows + 7) / 8), dim3(256), 0, st, v, row0, nrows, -fused,
-                b->noise_spec_use, nmain);
+static void stage_input(hipStream_t st, const View &v, const RamdShape *sh, const RamdFwdCall *c, const FwdPlan &p) {
+  if (p.input == FIN_BOTTOM) {
+    if (p.advance_first) RAMD_LAUNCH(k_advance, dim3((c->nrows + 255) / 256), dim3(256), 0, st, v, c->row0, c->nrows);
+    RAMD_LAUNCH(k_bottom_forward, dim3(c->nrows), dim3(256), (size_t)(sh->bI + sh->bO) * sizeof(float), st, v, c->row0,
+                c->mode, c->dense, c->ld, c->text_i, c->global_first, c->global_count, c->noise);
   }
-  if (part != 1) launch_output_layer(st, sh, b, row0, nrows);
+  if (p.input == FIN_BOTTOM || p.input == FIN_ASSEMBLE) {
+    const bool keep = p.input == FIN_BOTTOM; /* the layer's outputs are the real inputs, and the ring has stepped */
+    RAMD_LAUNCH(k_assemble, dim3(c->nrows), dim3(256), 0, st, v, c->row0, keep ? (int)RAMD_IN_KEEP : c->mode,
+                keep ? nullptr : c->dense, keep ? 0 : c->ld, keep ? 0 : c->text_i, c->global_first, c->global_count,
+                keep ? 0 : c->advance);
+  }
 }
 
-static void launch_output_layer(hipStream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows) {
-  View v = make_view(sh, b);
-  if (sh->O == 4 && nrows >= 64) {
-    RAMD_LAUNCH(k_out_layer_o4, dim3((nrows + 3) / 4), dim3(256), 0, st, v, row0, nrows);
-  } else if (sh->O <= 256) {
-    RAMD_LAUNCH(k_out_layer, dim3(nrows), dim3(1024),
-                       (size_t)(sh->H + OUT_SEGS * 64) * sizeof(float), st, v, row0);
-  } else if (nrows % WM == 0 && sh->O >= 1024 && ((sh->H + WK - 1) / WK == 9 || (sh->H + WK - 1) / WK == 17 || (sh->H + WK - 1) / WK == 33) &&
-             (nrows / WM) * ((sh->O + WN - 1) / WN) >= 128 && env_int("RECUR_AMD_OUT_WIDE", 1)) {
-    /* wide output layers with enough tiles to fill the device (the multi-head nets: 4 x 58 at 256 streams): k_fwd_wide's
-     * 64 x 64 tiles with the full K in every workgroup write `out` directly (33 + 6 us as k_gemm + k_sum_slabs) */
-    static bool attr_set2 = false;
-    const size_t shm = (size_t)W_STAGES * W_STAGE_FLOATS * sizeof(float);
-    if (!attr_set2) {
-      HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_wide<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_wide<17>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_wide<33>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-      attr_set2 = true;
-    }
-    const View *d_view = device_view(st, v);
-    const int ns = (sh->H + WK - 1) / WK;
-    const int wtm = nrows / WM, wtn = (sh->O + WN - 1) / WN;
-    const int supertiles = ((wtm + 3) / 4) * ((wtn + 7) / 8);
-    const int wblocks = ((supertiles + 7) / 8) * 8 * 32;
-    WideOp op = {b->hidden + (size_t)row0 * sh->H, b->ho_w, b->out + (size_t)row0 * sh->O, sh->H, sh->O, sh->O, sh->H, sh->O};
-    int ev = timing_begin(st, T_OTHER);
-    if (ns == 33) RAMD_LAUNCH(k_fwd_wide<33>, dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, wtm, wtn, op);
-    else if (ns == 17) RAMD_LAUNCH(k_fwd_wide<17>, dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, wtm, wtn, op);
-    else RAMD_LAUNCH(k_fwd_wide<9>, dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, wtm, wtn, op);
+static void stage_hidden(hipStream_t st, const View &v, const RamdBuffers *b, const RamdFwdCall *c, const FwdPlan &p) {
+  const int row0 = c->row0, nrows = c->nrows;
+  if (p.hidden == FH_SMALL) {
+    int ev = timing_begin(st, T_FWD);
+    RAMD_LAUNCH(k_fwd_small, dim3(1), dim3(1024), 0, st, v, row0);
     timing_end(st, ev);
-  } else { /* wide output layers (multi-head nets, O in the thousands): the MFMA GEMM */
-    int tm = (nrows + BM - 1) / BM;
-    int tn = (sh->O + BN - 1) / BN, nkt = (sh->H + BK - 1) / BK;
-    int ks = pick_ks(tm * tn, nkt, b->slab_floats, (size_t)nrows * sh->O);
-    ProbOut p = {v, row0, nrows};
-    launch_gemm<false, true, ProbOut>(st, p, b->slab, nrows, sh->O, nkt, ks, T_OTHER);
-    int n4 = nrows * (sh->O / 4);
-    RAMD_LAUNCH(k_sum_slabs, dim3((n4 + 255) / 256), dim3(256), 0, st,
-                       b->out + (size_t)row0 * sh->O, sh->O, b->slab, nrows, sh->O, ks, 0);
+  } else if (p.hidden == FH_FUSED) {
+    const View *d_view = device_view(st, v);
+    int ev = timing_begin(st, T_FWD);
+    if (p.ht.ns == 8) launch_fwd_fused_ns<8>(st, d_view, b, c, p);
+    else if (p.ht.ns == 4) launch_fwd_fused_ns<4>(st, d_view, b, c, p);
+    else if (p.ht.ns == 2) launch_fwd_fused_ns<2>(st, d_view, b, c, p);
+    else if (p.ht.ns == 16) launch_fwd_fused_ns<16>(st, d_view, b, c, p);
+    else launch_fwd_fused_ns<0>(st, d_view, b, c, p);
+    timing_end(st, ev);
+  } else if (p.hidden == FH_WIDE) {
+    launch_fwd_wide(st, v, b, row0, nrows, p.ht, WideOp{}, T_FWD);
+  } else if (p.uniform) {
+    ProbFwd<true> pr = {v, row0, nrows};
+    launch_gemm<false, true, ProbFwd<true>>(st, pr, b->slab, nrows, v.sh.H, p.nkt, p.ks, T_FWD);
+  } else {
+    ProbFwd<false> pr = {v, row0, nrows};
+    launch_gemm<false, true, ProbFwd<false>>(st, pr, b->slab, nrows, v.sh.H, p.nkt, p.ks, T_FWD);
   }
 }
 
-/* the hidden layer only: hidden = act(X . W_ih) (recur-nn.c:117-148).  With leave_slabs the
- * K slabs of the GEMM (noise included) stay in the workspace un-summed for
- * ramd_launch_text_top; the return value is their number. */
-extern "C" int ramd_launch_forward_hidden(ramd_stream_t st_, const RamdShape *sh,
-                                          const RamdBuffers *b, int row0, int nrows, float noise,
-                                          int leave_slabs) {
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  int tm = (nrows + BM - 1) / BM;
-  {
-    int tn = (sh->H + BN - 1) / BN, nkt = (sh->I + BK - 1) / BK;
-    int ks = pick_ks(tm * tn, nkt, b->slab_floats, (size_t)nrows * sh->H);
-    const int wide_ns = (sh->I + WK - 1) / WK;
-    /* (from 2048 rows: h_size = hidden_size + 4 makes 33 column tiles of 64, and with a few hundred
-     * rows that 33rd tile is a second round of workgroups: 97 us against the generic kernel's 60
-     * at 512 x 2048; at 13,824 rows it is 1406 us against 1515) */
-    if (nrows % WM == 0 && nrows >= 2048 && (wide_ns == 9 || wide_ns == 17 || wide_ns == 33) &&
-        (size_t)nrows * sh->H <= b->slab_floats && env_int("RECUR_AMD_FWD_WIDE", 1)) {
-      /* big sets: 64 x 64 tiles, operands by LDS-DMA (k_fwd_wide); one plane of sums */
-      static bool attr_set = false;
-      const size_t shm = (size_t)W_STAGES * W_STAGE_FLOATS * sizeof(float);
-      if (!attr_set) {
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_wide<9>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_wide<17>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        HIP_CHECK(hipFuncSetAttribute((const void *)k_fwd_wide<33>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-        attr_set = true;
-      }
-      const View *d_view = device_view(st, v);
-      const int wtm = nrows / WM, wtn = (sh->H + WN - 1) / WN;
-      const int supertiles = ((wtm + 3) / 4) * ((wtn + 7) / 8); /* of 4 x 8 tiles, 32 blocks each */
-      const int wblocks = ((supertiles + 7) / 8) * 8 * 32;
-      int ev = timing_begin(st, T_FWD);
-      if (wide_ns == 33)
-        RAMD_LAUNCH(k_fwd_wide<33>, dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, wtm, wtn, WideOp{});
-      else if (wide_ns == 17)
-        RAMD_LAUNCH(k_fwd_wide<17>, dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, wtm, wtn, WideOp{});
-      else
-        RAMD_LAUNCH(k_fwd_wide<9>, dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, wtm, wtn, WideOp{});
-      timing_end(st, ev);
-      ks = 1;
-    } else if (b->uniform_idx >= 0) {
-      ProbFwd<true> p = {v, row0, nrows};
-      launch_gemm<false, true, ProbFwd<true>>(st, p, b->slab, nrows, sh->H, nkt, ks, T_FWD);
-    } else {
-      ProbFwd<false> p = {v, row0, nrows};
-      launch_gemm<false, true, ProbFwd<false>>(st, p, b->slab, nrows, sh->H, nkt, ks, T_FWD);
-    }
-    if (noise != 0.0f && b->noise_spec_use) {
-      int n4 = nrows * (sh->H / 4);
-      RAMD_LAUNCH(k_noise_apply, dim3((n4 + 255) / 256), dim3(256), 0, st, v, row0, nrows);
-    } else if (noise != 0.0f) {
-      RAMD_LAUNCH(k_presynaptic_noise, dim3((nrows + 63) / 64), dim3(64), 0, st, v, row0, nrows,
-                         noise);
-    }
-    if (leave_slabs) return ks;
-    int n4 = nrows * (sh->H / 4);
-    RAMD_LAUNCH(k_fwd_finalize, dim3((n4 + 255) / 256), dim3(256), 0, st, v, row0, nrows, ks);
+/* (behind k_fwd_fused the values generated ahead are added by its finishing kernel: stage_hidden_end) */
+static void stage_noise(hipStream_t st, const View &v, const RamdFwdCall *c, const FwdPlan &p) {
+  if (p.hidden == FH_FUSED) return;
+  if (p.noise == FN_APPLY)
+    RAMD_LAUNCH(k_noise_apply, dim3((c->nrows * (v.sh.H / 4) + 255) / 256), dim3(256), 0, st, v, c->row0, c->nrows);
+  else if (p.noise == FN_GENERATE)
+    RAMD_LAUNCH(k_presynaptic_noise, dim3((c->nrows + 63) / 64), dim3(64), 0, st, v, c->row0, c->nrows, c->noise);
+}
+
+static void stage_hidden_end(hipStream_t st, const View &v, const RamdFwdCall *c, const FwdPlan &p) {
+  const int nrows = c->nrows;
+  if (p.end == FE_FINALIZE) {
+    RAMD_LAUNCH(k_fwd_finalize, dim3((nrows * (v.sh.H / 4) + 255) / 256), dim3(256), 0, st, v, c->row0, nrows, p.ks);
+  } else if (p.end == FE_FINALIZE_FUSED) { /* the sums' tail columns, the noise generated ahead, the activation */
+    const int nmain = (nrows * (v.sh.H / 4 - 1) + 255) / 256;
+    RAMD_LAUNCH(k_fwd_finalize_fused, dim3(nmain + (nrows + 7) / 8), dim3(256), 0, st, v, c->row0, nrows, p.ht.tn,
+                p.noise == FN_APPLY, nmain);
   }
-  return 0;
+}
+
+static void stage_output(hipStream_t st, const View &v, const RamdShape *sh, const RamdBuffers *b, const RamdFwdCall *c,
+                         const FwdPlan &p) {
+  const int row0 = c->row0, nrows = c->nrows;
+  if (p.output == FO_O4) {
+    RAMD_LAUNCH(k_out_layer_o4, dim3((nrows + 3) / 4), dim3(256), 0, st, v, row0, nrows);
+  } else if (p.output == FO_ROWS) {
+    RAMD_LAUNCH(k_out_layer, dim3(nrows), dim3(1024), (size_t)(sh->H + OUT_SEGS * 64) * sizeof(float), st, v, row0);
+  } else if (p.output == FO_WIDE) {
+    WideOp op = {b->hidden + (size_t)row0 * sh->H, b->ho_w, b->out + (size_t)row0 * sh->O, sh->H, sh->O, sh->O, sh->H, sh->O};
+    launch_fwd_wide(st, v, b, row0, nrows, p.ot, op, T_OTHER);
+  } else if (p.output == FO_GEMM) {
+    ProbOut pr = {v, row0, nrows};
+    launch_gemm<false, true, ProbOut>(st, pr, b->slab, nrows, sh->O, p.o_nkt, p.o_ks, T_OTHER);
+    RAMD_LAUNCH(k_sum_slabs, dim3((nrows * (sh->O / 4) + 255) / 256), dim3(256), 0, st, b->out + (size_t)row0 * sh->O, sh->O,
+                b->slab, nrows, sh->O, p.o_ks, 0);
+  }
+}
+
+extern "C" RamdHandover ramd_launch_forward(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, const RamdFwdCall *c,
+                                            void (*seam)(void *ctx), void *ctx) {
+  hipStream_t st = (hipStream_t)st_;
+  const FwdPlan p = ramd_plan_forward(sh, b, c);
+  View v = make_view(sh, b);
+  stage_input(st, v, sh, c, p);
+  stage_hidden(st, v, b, c, p);
+  stage_noise(st, v, c, p);
+  stage_hidden_end(st, v, c, p);
+  if (seam && p.end == FE_FINALIZE_FUSED) seam(ctx);
+  stage_output(st, v, sh, b, c, p);
+  return p.left;
 }
 
 extern "C" void ramd_launch_noise_speculate(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b,

@@ -10,6 +10,7 @@ __device__ unsigned long long g_tt_stamps[16];
 #define TT_STAMP(i) do { } while (0)
 #endif
 #include "k_top.h"
+#include "fwd_plan.h"
 BND_DECL(g_bnd_top, ramd_bnd_top_stamps)
 #pragma clang fp contract(off)
 
@@ -754,13 +755,16 @@ __global__ void k_sigmoid_outputs(View v, int r0, int nrows, int n) {
 
 #pragma clang fp contract(fast)
 
-extern "C" int ramd_text_top_ok(const RamdShape *sh) {
-  return sh->O <= 256 && sh->H <= 3072 && !env_int("RECUR_AMD_NO_TEXT_TOP", 0);
-}
+extern "C" int ramd_text_top_ok(const RamdShape *sh) { return text_top_takes(sh); } /* (fwd_plan.h: the forward plan asks too) */
+
+/* what the forward pass left in the workspace as the top kernels' fwd_ks (top_hidden_row, k_top.h): n > 0: n K slabs;
+ * n < 0: one plane of sums and -n per-tile padding partials; 0: nothing, the hidden rows are complete */
+static int handover_fwd_ks(RamdHandover left) { return left.partials ? -left.partials : left.planes; }
 
 extern "C" void ramd_launch_text_top(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b,
-                                     int row0, int nrows, int fwd_ks) {
+                                     int row0, int nrows, RamdHandover left) {
   hipStream_t st = (hipStream_t)st_;
+  const int fwd_ks = handover_fwd_ks(left);
   View v = make_view(sh, b);
   /* round 6's form where its preconditions hold (k_text_top2): o_size a multiple of 4 up to 64 (sixteen lanes a row of
    * W_ho), a wave's rows of W_ho in one batch of T2_NB x 4 */
@@ -783,9 +787,10 @@ extern "C" int ramd_dense_top_ok(const RamdShape *sh) {
 }
 
 extern "C" int ramd_launch_dense_top(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
-                                     int fwd_ks, const float *targets, int ld, int n, int ngroups, const int *goff,
+                                     RamdHandover left, const float *targets, int ld, int n, int ngroups, const int *goff,
                                      const int *gsize, const int *gt, const float *weight) {
   if (!ramd_dense_top_ok(sh)) return 0;
+  const int fwd_ks = handover_fwd_ks(left);
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
   size_t shm = (size_t)(sh->H + OUT_SEGS * 64 * 4 + (OUT_SEGS + 3) * sh->O) * sizeof(float);

@@ -545,14 +545,12 @@ float *rnn_opinion(RecurNN *net, const float *inputs, float presynaptic_noise) {
   }
   ramd_set_uniform_idx(e, p->stream >= 0 ? p->stream : e->n_streams, p->stream >= 0 ? 1 : 0);
   ramd_mail_in_flush();
+  /* (the inputs are in place: the bottom layer's in its own row, the net's in the slot) */
+  const RamdFwdCall call = {.row0 = r, .nrows = 1, .mode = RAMD_IN_KEEP, .global_count = 1, .noise = presynaptic_noise,
+                            .one_net = 1};
+  ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
   if (bl) {
-    ramd_launch_bottom_forward(ramd_stream, s, &e->b, r, 1, RAMD_IN_KEEP, NULL, 0, 0, 0, 1,
-                               presynaptic_noise);
     ramd_mail_out(bl->outputs, e->b.bout + (size_t)r * s->bO, sizeof(float) * s->bO);
-  }
-  if (bl || presynaptic_noise != 0.0f || !ramd_launch_forward_small(ramd_stream, s, &e->b, r)) {
-    ramd_launch_assemble(ramd_stream, s, &e->b, r, 1, RAMD_IN_KEEP, NULL, 0, 0, 0, 1, 0);
-    ramd_launch_forward(ramd_stream, s, &e->b, r, 1, presynaptic_noise);
   }
   if (presynaptic_noise != 0.0f) {
     ramd_mail_out(&net->rng, (char *)e->b.rng + (size_t)r * sizeof(rand_ctx), sizeof(rand_ctx));
@@ -910,13 +908,8 @@ static void run_text(RecurNN *net, const u8 *text, int len, int skip, int alphab
   e->b.text_len = len;
   ramd_set_uniform_idx(e, p->stream >= 0 ? p->stream : e->n_streams, p->stream >= 0 ? 1 : 0);
   for (int i = 0; i < len - 1; i++) {
-    if (s->bI) {
-      ramd_launch_bottom_forward(ramd_stream, s, &e->b, r, 1, RAMD_IN_TEXT, NULL, 0, i, 0, 1, 0.0f);
-      ramd_launch_assemble(ramd_stream, s, &e->b, r, 1, RAMD_IN_KEEP, NULL, 0, 0, 0, 1, 0);
-    } else {
-      ramd_launch_assemble(ramd_stream, s, &e->b, r, 1, RAMD_IN_TEXT, NULL, 0, i, 0, 1, 0);
-    }
-    ramd_launch_forward(ramd_stream, s, &e->b, r, 1, 0.0f);
+    const RamdFwdCall call = {.row0 = r, .nrows = 1, .mode = RAMD_IN_TEXT, .text_i = i, .global_count = 1};
+    ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
     if (alphabet_len) {
       if (i >= skip) {
         ramd_launch_multi_xent_accumulate(ramd_stream, s, &e->b, r, alphabet_len, n_sums, d_acc, 1);

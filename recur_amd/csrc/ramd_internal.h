@@ -135,36 +135,43 @@ typedef void *ramd_stream_t;
 void ramd_launch_pending_finalize(ramd_stream_t st, const RamdPendingDelta *p);
 
 /* ---- forward ---- */
-void ramd_launch_advance(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
-                         int row0, int nrows);
-/* builds the input rows (recur-nn.c:104-115 + 68-81).  mode selects where the
- * real inputs come from; dense is a device pointer with leading dimension ld;
- * text_i is the text position for RAMD_IN_TEXT (also fills b->target); the
- * row's global stream number is global_first + (row - row0) of global_count.
- * advance != 0 steps each stream's ring index first (rnn_bptt_advance). */
-void ramd_launch_assemble(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
-                          int row0, int nrows, int mode, const float *dense, int ld,
-                          int text_i, int global_first, int global_count, int advance);
-/* the bottom layer of rnn_opinion (recur-nn.c:88-103): fills each stream's bottom input
- * row as `mode` says (as ramd_launch_assemble), multiplies it through the bottom
- * weights, adds the presynaptic noise and writes the rectified result as the stream's
- * real inputs.  The ring index must already be the current one. */
-void ramd_launch_bottom_forward(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
-                                int row0, int nrows, int mode, const float *dense, int ld,
-                                int text_i, int global_first, int global_count,
-                                float presynaptic_noise);
+/* What a caller wants of a forward pass (rnn_opinion, recur-nn.c:83-154).  The real inputs of state rows
+ * [row0, row0 + nrows) come as `mode` says: dense is a device pointer with leading dimension ld; text_i is the text
+ * position for RAMD_IN_TEXT (also fills b->target); the row's global stream number is global_first + (row - row0) of
+ * global_count.  With a bottom layer (recur-nn.c:88-103) the inputs feed that layer, whose rectified outputs become
+ * the real inputs. */
+enum {
+  RAMD_FWD_WHOLE = 0,         /* hidden = act(X . W_ih), out = hidden . W_ho (recur-nn.c:117-151) */
+  RAMD_FWD_FOR_TEXT_TOP = 1,  /* the hidden layer's sums stay in the workspace for ramd_launch_text_top */
+  RAMD_FWD_FOR_DENSE_TOP = 2  /* ... for ramd_launch_dense_top */
+};
+typedef struct RamdFwdCall {
+  int row0, nrows, mode;
+  const float *dense;
+  int ld, text_i, global_first, global_count;
+  int advance;     /* step each stream's ring index first (rnn_bptt_advance) */
+  float noise;     /* presynaptic_noise */
+  int fwd_only;    /* forward-only rows (above Scap) */
+  int want;        /* RAMD_FWD_* */
+  int rows_built;  /* the input rows are there already (ramd_launch_texts_step built them) */
+  int one_net;     /* rnn_opinion for one net: the one-launch form for small nets may take it */
+} RamdFwdCall;
+/* What a pass that stops for a top launch leaves in the workspace: `planes` K slabs of the hidden layer's sums
+ * (0: nothing), or one plane and `partials` per-tile partial sums of the h_size padding columns behind it */
+typedef struct RamdHandover {
+  int planes, partials;
+} RamdHandover;
+/* The pass: fwd_plan.h says which kernels, this enqueues them.  `seam` (or NULL) is called with `ctx` between the
+ * hidden layer's end and the output layer where the hidden layer was the fused launch with its own finishing kernel,
+ * and nowhere else (set_api.c: the multi-head step starts the next pass's noise there). */
+RamdHandover ramd_launch_forward(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdFwdCall *call,
+                                 void (*seam)(void *ctx), void *ctx);
 /* the bottom layer's share of rnn_bptt_calc_deltas (recur-nn.c:377-382, 750-757) for
  * rows that ramd_launch_calc_deltas has just processed; flips b->bcarry_cur */
 void ramd_launch_bottom_deltas(ramd_stream_t st, const RamdShape *sh, RamdBuffers *b, int row0,
                                int nrows, int accumulate, const unsigned char *active);
-/* hidden = act(X . W_ih), out = hidden . W_ho (recur-nn.c:117-151) */
-void ramd_launch_forward(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
-                         int row0, int nrows, float presynaptic_noise);
-/* the hidden layer only (the first half of ramd_launch_forward) */
-int ramd_launch_forward_hidden(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
-                               int row0, int nrows, float presynaptic_noise, int leave_slabs);
 /* output layer + softmax error against b->target + dense top backprop in one launch (what
- * ramd_launch_forward's second half, ramd_launch_softmax_error and the first kernel of
+ * the forward pass's output layer, ramd_launch_softmax_error and the first kernel of
  * ramd_launch_calc_deltas do); follow with ramd_launch_calc_deltas(flags | RAMD_TOP_DONE).
  * ramd_text_top_ok says whether the shape allows it. */
 #define RAMD_TOP_DONE 0x40000000u
@@ -188,18 +195,11 @@ int ramd_launch_forward_hidden(ramd_stream_t st, const RamdShape *sh, const Ramd
 #define RAMD_MULTI_RANGE_STRIDE 132
 int ramd_text_top_ok(const RamdShape *sh);
 int ramd_dense_top_ok(const RamdShape *sh); /* ramd_launch_dense_top will take the shape (O <= 64, RECUR_AMD_DENSE_TOP) */
-int ramd_launch_forward_fused(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
-                              int nrows, int mode, int text_i, int global_first, int n_set, int for_top,
-                              const float *dense, int ld); /* (dense, ld: the inputs of mode RAMD_IN_DENSE, [nrows][ld]) */
-/* after ramd_launch_forward_fused(for_top = 0) returned `fused` != 0: tail columns, noise generated ahead, activation,
- * output layer */
-void ramd_launch_forward_finish(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
-                                int fused, int part); /* part 1: the hidden layer's end, 2: the output layer, 0: both */
 void ramd_launch_text_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
-                          int nrows, int fwd_ks);
+                          int nrows, RamdHandover left);
 /* the same launch with rnnca's loss (targets [nrows][ld] on the device, first n outputs; ngroups == 0) or gstclassify's
  * class groups between output layer and backprop; 0: not this kernel's shape, nothing launched */
-int ramd_launch_dense_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, int fwd_ks,
+int ramd_launch_dense_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, RamdHandover left,
                           const float *targets, int ld, int n, int ngroups, const int *goff, const int *gsize, const int *gt,
                           const float *weight);
 /* o_error = onehot(target) - softmax(out) and statistics
@@ -257,8 +257,6 @@ void ramd_launch_sigmoid_mse_error(ramd_stream_t st, const RamdShape *sh, const 
 /* fast_sigmoid_array in place on the first n outputs of state rows r0 .. r0 + nrows */
 void ramd_launch_sigmoid_outputs(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int r0,
                                  int nrows, int n);
-/* rnn_opinion's device work for one stream of a small net in one launch; 0: not its kind of shape */
-int ramd_launch_forward_small(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int r);
 /* The next ramd_launch_calc_deltas calls may run the weight-delta GEMM in two row halves and call `hook`
  * (ctx, half 0 / 1, first float from ih_delta, floats) after each half's deltas are complete; NULL: off. */
 void ramd_set_delta_half_hook(void (*hook)(void *ctx, int half, size_t first_float, size_t n_floats), void *ctx);

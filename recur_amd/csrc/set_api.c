@@ -255,10 +255,19 @@ static void noise_speculate_from(RnnAmdSet *set, int loss_classes) {
 }
 static void noise_speculate(RnnAmdSet *set) { noise_speculate_from(set, 0); }
 
-/* hidden_only: stop after the hidden layer's GEMM and leave its K slabs for
- * ramd_launch_text_top; returns their number (0 otherwise) */
-static int set_forward(RnnAmdSet *set, int mode, const float *d_dense, int ld, int text_i,
-                       float *outputs, int advance, int hidden_only) {
+/* the multi-head step: the next pass's noise from the fused hidden layer's end on, beside the output layer and the loss */
+static void early_speculate(void *ctx) {
+  RnnAmdSet *set = ctx;
+  if (set->early_spec_classes > 0 && set->eng->sp_adopted >= 0) {
+    noise_speculate_from(set, set->early_spec_classes);
+    set->early_spec_classes = -1; /* done */
+  }
+}
+
+/* want (RAMD_FWD_*): the whole pass, or stop after the hidden layer's sums and leave them for ramd_launch_text_top /
+ * ramd_launch_dense_top; returns what was left (nothing otherwise) */
+static RamdHandover set_forward(RnnAmdSet *set, int mode, const float *d_dense, int ld, int text_i,
+                                float *outputs, int advance, int want) {
   RamdEngine *e = set->eng;
   ramd_top_done_clear(e);
   ramd_engine_need_dev(e, RNN_AMD_WEIGHTS);
@@ -308,67 +317,18 @@ static int set_forward(RnnAmdSet *set, int mode, const float *d_dense, int ld, i
       abort();
     }
   }
-  if (e->sh.bI) {
-    /* the caller's inputs feed the bottom layer, whose rectified outputs become the real
-     * inputs of the current slot: the ring has to step before it runs */
-    if (advance) {
-      ramd_launch_advance(ramd_stream, &e->sh, &e->b, set->row0, set->n);
-    }
-    ramd_launch_bottom_forward(ramd_stream, &e->sh, &e->b, r0, set->n, mode, d_dense, ld, text_i,
-                               set->global_first, set->global_count, noise);
-    ramd_launch_assemble(ramd_stream, &e->sh, &e->b, r0, set->n, RAMD_IN_KEEP, NULL, 0, 0,
-                         set->global_first, set->global_count, 0);
-  } else {
-    if (hidden_only && (advance || mode == RAMD_IN_DENSE) && noise == 0.0f && !set->fwd_only) {
-      /* the text step: building the input rows and the hidden layer's GEMM in one launch
-       * (the ring index the kernel stores is the host's, which has just stepped); dense inputs on their way to
-       * ramd_launch_dense_top likewise */
-      int fused = ramd_launch_forward_fused(ramd_stream, &e->sh, &e->b, r0, set->n, mode, text_i,
-                                            set->global_first, set->global_count, 1, d_dense, ld);
-      if (fused) {
-        set_streams_dev_wrote(set);
-        return fused;
-      }
-    } else if (!hidden_only && (advance || mode == RAMD_IN_DENSE) && !set->fwd_only && (noise == 0.0f || e->b.noise_spec_use)) {
-      /* the same launch for the one-hot and text passes that go on to a generic output layer (the multi-head step),
-       * and for dense inputs (gstclassify's features, rnnca's neighbourhoods; their callers advance on their own, and
-       * the index the kernel stores is the one that is there); presynaptic noise only as the values generated
-       * ahead, which the finishing kernel adds */
-      int fused = ramd_launch_forward_fused(ramd_stream, &e->sh, &e->b, r0, set->n, mode, text_i,
-                                            set->global_first, set->global_count, 0, d_dense, ld);
-      if (fused) {
-        ramd_launch_forward_finish(ramd_stream, &e->sh, &e->b, r0, set->n, fused, 1);
-        if (set->early_spec_classes > 0 && e->sp_adopted >= 0) {
-          /* the multi-head step: the next pass's noise from here on, beside the output layer and the loss */
-          noise_speculate_from(set, set->early_spec_classes);
-          set->early_spec_classes = -1; /* done */
-        }
-        ramd_launch_forward_finish(ramd_stream, &e->sh, &e->b, r0, set->n, fused, 2);
-        e->b.noise_spec_use = 0;
-        set_streams_dev_wrote(set);
-        if (outputs) {
-          ramd_d2h(outputs, e->b.out + (size_t)r0 * e->sh.O, (size_t)set->n * e->sh.O * sizeof(float));
-          ramd_dsync();
-        }
-        return 0;
-      }
-    }
-    ramd_launch_assemble(ramd_stream, &e->sh, &e->b, r0, set->n, mode, d_dense, ld, text_i,
-                         set->global_first, set->global_count, advance);
-  }
-  int fwd_ks = 0;
-  if (hidden_only) {
-    fwd_ks = ramd_launch_forward_hidden(ramd_stream, &e->sh, &e->b, r0, set->n, noise, 1);
-  } else {
-    ramd_launch_forward(ramd_stream, &e->sh, &e->b, r0, set->n, noise);
-  }
+  /* (when advancing, the ring index the device stores is the host's, which has just stepped) */
+  const RamdFwdCall call = {.row0 = r0, .nrows = set->n, .mode = mode, .dense = d_dense, .ld = ld, .text_i = text_i,
+                            .global_first = set->global_first, .global_count = set->global_count, .advance = advance,
+                            .noise = noise, .fwd_only = set->fwd_only, .want = want};
+  const RamdHandover left = ramd_launch_forward(ramd_stream, &e->sh, &e->b, &call, early_speculate, set);
   e->b.noise_spec_use = 0;
   set_streams_dev_wrote(set);
   if (outputs) {
     ramd_d2h(outputs, e->b.out + (size_t)r0 * e->sh.O, (size_t)set->n * e->sh.O * sizeof(float));
     ramd_dsync();
   }
-  return fwd_ks;
+  return left;
 }
 
 void rnn_amd_set_opinion(RnnAmdSet *set, const float *inputs, int ld_inputs, float *outputs) {
@@ -377,7 +337,7 @@ void rnn_amd_set_opinion(RnnAmdSet *set, const float *inputs, int ld_inputs, flo
     int w = e->sh.bI ? e->sh.b_in : e->sh.input_size;
     /* (queued: leaves with the ring indices in set_forward's flush) */
     ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), w * sizeof(float), set->n, set->fwd_only);
-    set_forward(set, RAMD_IN_DENSE, e->d_dense, w, 0, outputs, 0, 0);
+    set_forward(set, RAMD_IN_DENSE, e->d_dense, w, 0, outputs, 0, RAMD_FWD_WHOLE);
     if (e->sh.bI) {
       /* the layer's one input buffer, shared by every clone, as the per-net loop would leave it:
        * the last stream's inputs (recur-nn.c:88-94) */
@@ -386,14 +346,14 @@ void rnn_amd_set_opinion(RnnAmdSet *set, const float *inputs, int ld_inputs, flo
       memcpy(bl->inputs + 1, inputs + (size_t)(set->n - 1) * ld_inputs, sizeof(float) * bl->input_size);
     }
   } else {
-    set_forward(set, RAMD_IN_KEEP, NULL, 0, 0, outputs, 0, 0);
+    set_forward(set, RAMD_IN_KEEP, NULL, 0, 0, outputs, 0, RAMD_FWD_WHOLE);
   }
 }
 
 void rnn_amd_set_one_hot_opinion(RnnAmdSet *set, const int *hot, float *outputs) {
   RamdEngine *e = set->eng;
   ramd_upload(e->b.hot + set_state_row0(set), hot, set->n * sizeof(int));
-  set_forward(set, RAMD_IN_ONE_HOT, NULL, 0, 0, outputs, 0, 0);
+  set_forward(set, RAMD_IN_ONE_HOT, NULL, 0, 0, outputs, 0, RAMD_FWD_WHOLE);
 }
 
 void rnn_amd_set_put_o_error(RnnAmdSet *set, const float *o_error, int ld) {
@@ -691,8 +651,8 @@ static void multi_step_deltas(RnnAmdSet *set, const int *hot, const int *next, c
     mclass_note(e, target_class, set->n, n_classes);
   }
   ramd_upload(e->b.target + set->row0, next, set->n * sizeof(int));
-  set->early_spec_classes = set->fwd_only ? 0 : n_classes; /* (set_forward's fused branch takes it up) */
-  set_forward(set, RAMD_IN_ONE_HOT, NULL, 0, 0, NULL, 1, 0);
+  set->early_spec_classes = set->fwd_only ? 0 : n_classes; /* (early_speculate takes it up where the pass has its seam) */
+  set_forward(set, RAMD_IN_ONE_HOT, NULL, 0, 0, NULL, 1, RAMD_FWD_WHOLE);
   int early = set->early_spec_classes < 0;
   set->early_spec_classes = 0;
   if (!early && e->sp_adopted >= 0 && !set->fwd_only) {
@@ -731,7 +691,7 @@ void rnn_amd_set_multi_text_loss(RnnAmdSet *set, int i, const int *target_class,
   ramd_set_need_training(set, "rnn_amd_set_multi_text_loss");
   check_text_pos(e, i, 0, "rnn_amd_set_multi_text_loss");
   int n_classes = multi_heads(e, alphabet_len);
-  set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 0); /* advance + one-hot opinion + b.target */
+  set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_WHOLE); /* advance + one-hot opinion + b.target */
   multi_loss(set, target_class, alphabet_len, n_classes, leakage, 0);
 }
 
@@ -740,7 +700,7 @@ void rnn_amd_set_multi_text_loss(RnnAmdSet *set, int i, const int *target_class,
 void rnn_amd_set_text_opinion(RnnAmdSet *set, int i, int advance) {
   RamdEngine *e = set->eng;
   check_text_pos(e, i, 1, "rnn_amd_set_text_opinion");
-  set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, advance, 0);
+  set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, advance, RAMD_FWD_WHOLE);
 }
 
 /* rnnca's loss on the device (gstrnnca.c:701-714) after rnn_amd_set_opinion: sigmoid of the
@@ -795,8 +755,8 @@ void rnn_amd_set_opinion_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld
   /* inputs and targets leave together with the ring indices (set_forward's flush) */
   ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), e->sh.input_size * sizeof(float), set->n, 0);
   ramd_upload_rows_q(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n, 0);
-  int fwd_ks = set_forward(set, RAMD_IN_DENSE, e->d_dense, e->sh.input_size, 0, NULL, 0, 1);
-  if (!ramd_launch_dense_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, fwd_ks, (const float *)e->d_group, n, n, 0,
+  const RamdHandover left = set_forward(set, RAMD_IN_DENSE, e->d_dense, e->sh.input_size, 0, NULL, 0, RAMD_FWD_FOR_DENSE_TOP);
+  if (!ramd_launch_dense_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, left, (const float *)e->d_group, n, n, 0,
                              NULL, NULL, NULL, NULL)) {
     fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_sigmoid_mse: the top launch declined a shape it had accepted\n");
     abort();
@@ -852,8 +812,8 @@ void rnn_amd_set_opinion_grouped_softmax(RnnAmdSet *set, const float *inputs, in
     }
   }
   active_mask_to_dev(e, trained, set->n, 1); /* (for the delta call that follows: travels with the rest) */
-  int fwd_ks = set_forward(set, RAMD_IN_DENSE, e->d_dense, s->input_size, 0, NULL, 0, 1);
-  if (!ramd_launch_dense_top(ramd_stream, s, &e->b, set->row0, set->n, fwd_ks, NULL, 0, 0, n_groups, d, d + n_groups,
+  const RamdHandover left = set_forward(set, RAMD_IN_DENSE, e->d_dense, s->input_size, 0, NULL, 0, RAMD_FWD_FOR_DENSE_TOP);
+  if (!ramd_launch_dense_top(ramd_stream, s, &e->b, set->row0, set->n, left, NULL, 0, 0, n_groups, d, d + n_groups,
                              d + 2 * n_groups, dw)) {
     fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_grouped_softmax: the top launch declined a shape it had accepted\n");
     abort();
@@ -907,12 +867,12 @@ static void char_step_deltas(RnnAmdSet *set, int i, RamdPendingDelta *defer) {
   check_text_pos(e, i, 0, "rnn_amd_set_char_step");
   if (ramd_text_top_ok(&e->sh)) {
     /* advance + hidden layer, then output layer, loss and top backprop in one launch */
-    int fwd_ks = set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 1);
+    const RamdHandover left = set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_FOR_TEXT_TOP);
     noise_speculate(set); /* no draws between this pass's noise and the next one's */
-    ramd_launch_text_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, fwd_ks);
+    ramd_launch_text_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, left);
     set_calc_deltas(set, 0, NULL, NULL, RAMD_TOP_DONE, NULL, 0, defer);
   } else {
-    set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 0); /* advance + one-hot opinion */
+    set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_WHOLE); /* advance + one-hot opinion */
     noise_speculate(set);
     ramd_launch_softmax_error(ramd_stream, &e->sh, &e->b, set->row0, set->n);
     set_calc_deltas(set, 0, NULL, NULL, 0, NULL, 0, defer);
@@ -1056,11 +1016,11 @@ void rnn_amd_set_char_step_fused(RnnAmdSet *set, int i, unsigned batch_size) {
   const int batched = batch_size > 1;
   unsigned top_done = 0;
   if (ramd_text_top_ok(s)) { /* advance + hidden layer, then output layer, loss and top backprop in one launch */
-    int fwd_ks = set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 1);
-    ramd_launch_text_top(ramd_stream, s, &e->b, j, 1, fwd_ks);
+    const RamdHandover left = set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_FOR_TEXT_TOP);
+    ramd_launch_text_top(ramd_stream, s, &e->b, j, 1, left);
     top_done = RAMD_TOP_DONE;
   } else {
-    set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, 0); /* advance + one-hot opinion */
+    set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_WHOLE); /* advance + one-hot opinion */
     ramd_launch_softmax_error(ramd_stream, s, &e->b, j, 1);
   }
   int accumulate = batched;

@@ -71,7 +71,8 @@ static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, i
     ramd_launch_texts_step(ramd_stream, s, &e->b, r0, tb->d_text, tb->d_off, tb->d_skip, tb->d_acc, t == 0 ? hid0 : NULL,
                            alphabet_len ? alphabet_len : s->output_size, n_sums, t - 1, scored, t, a);
     if (a) {
-      ramd_launch_forward(ramd_stream, s, &e->b, r0, a, 0.0f);
+      const RamdFwdCall call = {.row0 = r0, .nrows = a, .rows_built = 1};
+      ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
     }
     scored = a;
   }

@@ -108,12 +108,15 @@ def test_text_step_with_adagrad_in_the_delta_gemms_epilogue(amd):
 
 @pytest.mark.parametrize("A,NC,H,S,D,leakage", [(128, 11, 256, 40, 6, 0.3), (24, 64, 512, 300, 5, 0.05),
                                                  (100, 3, 128, 7, 4, 0.9), (31, 20, 256, 64, 6, 0.2),
-                                                 (130, 3, 128, 7, 4, 0.9)])
+                                                 (130, 3, 128, 7, 4, 0.9), (64, 64, 512, 128, 4, 0.05),
+                                                 (64, 64, 2048, 128, 2, 0.05)])
 def test_multi_head_generation_with_other_head_shapes(amd, A, NC, H, S, D, leakage):
     """The per-head top-layer kernels at their limits: the widest head (128 symbols), the narrowest they take (24)
     with the most heads (64) and more than 256 streams (two passes of the stream lists), three heads that nearly
     every stream trains all of (leakage 0.9), 31-symbol heads (never aligned to a float4), 130-symbol heads (past the
-    128 that a wave holds in registers: the loss kernel's strided form)."""
+    128 that a wave holds in registers: the loss kernel's strided form).  The last two: the smallest sets whose output
+    layer is k_fwd_wide's nine-stage form (h_size 516; 128 streams x 4096 outputs = 2 x 64 tiles, fwd_plan.h) and its
+    33-stage form (h_size 2052)."""
     _multi_head_generation(amd, A, NC, H, S, D, leakage)
 
 
@@ -328,13 +331,14 @@ def test_dense_input_generation_with_other_shapes(amd, hidden, S, D, n_in, activ
     _rnnca_generation(amd, hidden, S, D, n_in=n_in, activation=activation)
 
 
-@pytest.mark.parametrize("hidden,S,D", [(2048, 512, 10), (64, 20, 4)])
+@pytest.mark.parametrize("hidden,S,D", [(2048, 512, 10), (64, 20, 4), (512, 2048, 2), (1024, 2048, 2)])
 def test_config4_rnnca_training_generation(amd, hidden, S, D):
     """rnnca's maybe_learn (gstrnnca.c:693-740) for every trainer at once: clear deltas, dense
     35-input opinion, sigmoid-slope MSE against the next frame's Y/Cb/Cr ON THE DEVICE,
     accumulating calc_deltas, weighted-momentum update with the soft start.  The reference's
     trainer never advances the ring (effective depth 1); the synthetic driver adds
-    rnn_bptt_advance so that depth 10 is exercised."""
+    rnn_bptt_advance so that depth 10 is exercised.  The sets of 2048: the fewest rows whose
+    hidden layer is k_fwd_wide, in its nine- and seventeen-stage forms (i_size 548 and 1060; fwd_plan.h)."""
     _rnnca_generation(amd, hidden, S, D)
 
 
