@@ -633,6 +633,31 @@ int rnn_amd_run_texts(RecurNN *net, const u8 *const *texts, const int *lens, con
  * charmodel-multi-predict.c:388-403): sums[k * n_heads + c] is head c's sum for text k. */
 int rnn_amd_run_texts_heads(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
                             int alphabet_len, double *sums); /* [n_texts][output_size / alphabet_len] */
+/* Many texts DRAWN from one net in one batched device run: the generative counterpart of rnn_amd_run_texts.  Row k of
+ * `out` is what this loop writes on a forward-only clone c_k of `net` whose hidden row starts as a copy of net's hidden
+ * row at the moment of the call and whose generator is init_rand64(seeds[k]) (recur-rng.h:33-43):
+ *     sym = first[k];
+ *     repeat up to max_len times: sym = the next symbol after feeding sym; write sym; stop after writing stop_point
+ * "the next symbol" being rnn_char_confabulate's (charmodel-predict.c:29-60): one forward pass on the one-hot of sym, the
+ * clamped softmax of head `head` of alphabet_len outputs, sharpened by `bias` (badmaths.h:71-156), and a draw from it with
+ * c_k's generator; with bias >= 100 the best output (the last of equal maxima) and no draw.  alphabet_len == 0: one head
+ * as wide as the output row.  stop_point < 0: no stop symbol.  out_lens[k] counts the symbols written, the stop symbol
+ * included; nothing is written behind them.  rng_out[k] (rng_out may be NULL) is c_k's generator afterwards.
+ * The draws are made on the device, from probabilities computed there: against a host computation of the same net they
+ * can differ where a draw falls within rounding of a boundary between two symbols, and from that symbol on the texts
+ * part -- each is a valid sample, and the same call gives the same bytes every time.
+ * `net` itself -- host and device copies, hidden row, generator, what it computes next -- is left exactly as it was.  The
+ * clones are state rows of the engine's own; the rows run side by side in waves of up to 256 with one device
+ * synchronisation per wave, and one more every 64 steps to end a wave whose every row has met its stop symbol.
+ * Returns 0; n_texts == 0 or max_len == 0 returns 0 at once (lengths zeroed, no device asked for).  Returns -1 when a row's
+ * draw failed (64 attempts without a pick: an output row whose softmax has no total, NaN for one) -- that row ends where
+ * it failed, the others are complete.  Returns -1 with a message on stderr and nothing computed, before anything needs a
+ * device: a net with a bottom layer (as rnn_amd_run_texts), n_texts < 0 or max_len < 0, a NULL first, seeds, out or
+ * out_lens with n_texts > 0, a first[k] outside [0, input_size), heads that do not divide the output row, a head out of
+ * range. */
+int rnn_amd_sample_texts(RecurNN *net, const int *first, const u64 *seeds, int n_texts, int max_len, float bias,
+                         int stop_point, int alphabet_len, int head, u8 *out /* [n_texts][max_len] */, int *out_lens,
+                         rand_ctx *rng_out /* [n_texts] or NULL */);
 /* Block until all queued device work of the library has finished. */
 void rnn_amd_synchronize(void);
 

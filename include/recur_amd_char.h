@@ -151,6 +151,15 @@ double rnn_char_cross_entropy(RecurNN *net, RnnCharAlphabet *alphabet, const u8 
 int rnn_amd_char_cross_entropy_texts(RecurNN *net, RnnCharAlphabet *alphabet, const u8 *const *texts, const int *lens,
                                      int n_texts, int ignore_first, const u8 *prefix_text, int prefix_len,
                                      double *entropy);
+/* rnn_char_confabulate's passage n_texts times over in one batched device run (rnn_amd_sample_texts, recur_amd.h): every
+ * passage starts from prev_char and the state `net` has, passage k draws with a generator seeded init_rand64(seeds[k]),
+ * and `net` -- state and generator -- is left as it was.  Up to char_len symbols each, ending after stop_point if that is
+ * not negative, turned into text in dest[k] (byte_len bytes each) under rnn_char_confabulate's room rule: byte_len -
+ * (utf8 ? 5 : 1) must be positive (else nothing is written but the NUL, bytes are 0, and 0 is returned), writing stops
+ * when that room is used up, the text is NUL-terminated; bytes[k] is its length.  There is no start_point: waiting for a
+ * symbol to turn up is what priming the net (rnn_char_prime) is for.  Returns what rnn_amd_sample_texts returns. */
+int rnn_amd_char_confabulate_texts(RecurNN *net, RnnCharAlphabet *a, const u64 *seeds, int n_texts, int char_len,
+                                   float bias, int prev_char, int stop_point, char **dest, int byte_len, int *bytes);
 
 /* ---- the multi-head text trainer (charmodel.h:132-152, 242-265;
  *      charmodel-multi-predict.c): py-recur-text.c's Net.train / Net.test backend ---- */

@@ -11,6 +11,7 @@ __device__ unsigned long long g_tt_stamps[16];
 #endif
 #include "k_top.h"
 #include "fwd_plan.h"
+#include "sample_rule.h"
 BND_DECL(g_bnd_top, ramd_bnd_top_stamps)
 #pragma clang fp contract(off)
 
@@ -729,6 +730,86 @@ __global__ __launch_bounds__(64 * TS_WAVES) void k_texts_step(View v, TextsStep 
                        text[p.t_feed], nullptr, red);
 }
 
+// The one launch between two forward passes of rnn_amd_sample_texts (sample_api.c): N texts drawn from one net side by
+// side, a state row each.  One workgroup of 256 threads per row (assemble_input_row's), two halves:
+//   draw (not in a wave's first launch, t == 0; not for a row that is done): wave 0 turns the row's slice of the output
+//     row, out[r][head * alen .. + alen), into the distribution in LDS (sample_rule.h, the wave as the team, lane-strided
+//     loops); lane 0 draws from it with the row's own generator -- p.rng, owned by the call, not b.rng -- stores symbol
+//     t - 1 of the row's text, the count and the generator.  The stop symbol ends the row (done 1), a draw that met the
+//     attempt cap fails it (done 2); its text and length are fixed from then on.  bias >= SAMPLE_GREEDY_BIAS: no draw, no
+//     generator.  Every word has one writer: no atomics.
+//   feed (t < max_len): the input row of the next forward pass -- assemble_input_row with the one-hot of the symbol just
+//     drawn, which reaches the workgroup through LDS behind a barrier; in the first launch the one-hot of first[j] on
+//     hid0, the hidden row of the net every text starts from (as k_texts_step).  A row that is done is not fed: its
+//     input row stays what it was and the forward passes that follow recompute what they computed.
+struct TextsSample {
+  const int *first;       /* [rows] the symbol in front of each text         */
+  DevRng *rng;            /* [rows] the rows' generators                      */
+  unsigned char *text;    /* [rows][max_len] the symbols drawn                */
+  int *len;               /* [rows] how many                                  */
+  int *done;              /* [rows] 0 running, 1 stopped, 2 failed            */
+  const float *hid0;      /* the hidden row of the first feed                 */
+  int row0;               /* state row of the wave's row 0 (forward-only)     */
+  int alen, head, max_len, t, stop_point;
+  float bias;
+};
+struct SampleWave { /* sample_rule.h's team: the 64 lanes of one wave */
+  int l;
+  __device__ __forceinline__ int lane() const { return l; }
+  __device__ __forceinline__ int stride() const { return 64; }
+  __device__ __forceinline__ void extremes(float &lo, float &hi) const { wave_minmax(lo, hi); }
+  __device__ __forceinline__ void fence() const { FenceOneWave{}(); }
+};
+struct SampleExp {
+  __device__ __forceinline__ float operator()(float x) const { return fast_expf_dev(x); }
+};
+struct SampleRand64 {
+  DevRng &g;
+  __device__ __forceinline__ unsigned long long operator()() { return dev_rand64(g); }
+};
+__global__ __launch_bounds__(256) void k_texts_sample(View v, TextsSample p) {
+  extern __shared__ float sdist[]; /* [alen] the row's distribution */
+  __shared__ float red[4];
+  __shared__ int hot_sh; /* the symbol to feed, or -1 */
+  const RamdShape &s = v.sh;
+  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (wave == 0) {
+    int hot = -1;
+    if (p.t == 0) {
+      hot = p.first[j];
+    } else if (p.done[j] == 0) { /* (the same word in every lane: the wave takes one side) */
+      const float *score = v.b.out + (size_t)r * s.O + (size_t)p.head * p.alen;
+      const bool greedy = p.bias >= SAMPLE_GREEDY_BIAS;
+      if (!greedy) sample_distribution(sdist, score, p.alen, p.bias, SampleExp{}, SampleWave{lane});
+      if (lane == 0) {
+        int pick;
+        if (greedy) {
+          pick = sample_greedy(score, p.alen);
+        } else {
+          DevRng g = p.rng[j];
+          SampleRand64 draw = {g};
+          pick = sample_draw(sdist, p.alen, draw);
+          p.rng[j] = g;
+        }
+        if (pick == SAMPLE_FAILED) {
+          p.done[j] = 2;
+        } else {
+          p.text[(size_t)j * p.max_len + (p.t - 1)] = (unsigned char)pick;
+          p.len[j] = p.t;
+          if (pick == p.stop_point) p.done[j] = 1;
+          else hot = pick;
+        }
+      }
+    }
+    if (lane == 0) hot_sh = p.t < p.max_len ? hot : -1;
+  }
+  __syncthreads();
+  const int hot = hot_sh;
+  if (hot >= 0) /* (the whole workgroup: assemble_input_row has barriers) */
+    assemble_input_row(s, input_row(v, r, 0), p.t == 0 ? p.hid0 : v.b.hidden + (size_t)r * s.H, RAMD_IN_ONE_HOT, hot,
+                       nullptr, red);
+}
+
 // rnnca's loss (gstrnnca.c:701-714, train_net): fast_sigmoid_array(answer, answer, n) IN
 // PLACE on the first n outputs (badmaths.h:33-44), then o_error[i] = a (1 - a) (target - a).
 // One thread per (stream, output); the rest of the error row stays as it was (zero).
@@ -847,6 +928,32 @@ extern "C" void ramd_launch_texts_step(ramd_stream_t st_, const RamdShape *sh, c
   if (shm > 64 * 1024) raise_lds_limit<k_texts_step>(160 * 1024 - 64);
   TextsStep p = {text, off, skip, acc, hid0, row0, alphabet_len, n_sums, t_score, a_score, t_feed, a_feed};
   RAMD_LAUNCH(k_texts_step, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
+}
+
+extern "C" void ramd_launch_texts_sample(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
+                                         const int *first, void *rng, unsigned char *text, int *len, int *done,
+                                         const float *hid0, int alphabet_len, int head, int max_len, int t, int stop_point,
+                                         float bias) {
+  if (rows < 1) return;
+  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
+    fprintf(stderr, "librecur_amd: ramd_launch_texts_sample: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
+    abort();
+  }
+  if (alphabet_len < 1 || head < 0 || (size_t)(head + 1) * alphabet_len > (size_t)sh->O || t < 0 || t > max_len) {
+    fprintf(stderr, "librecur_amd: ramd_launch_texts_sample: head %d of %d outputs in a row of %d, step %d of %d\n", head,
+            alphabet_len, sh->O, t, max_len);
+    abort();
+  }
+  hipStream_t st = (hipStream_t)st_;
+  View v = make_view(sh, b);
+  const size_t shm = (size_t)((alphabet_len + 3) & ~3) * sizeof(float);
+  if (shm > 160 * 1024 - 64) {
+    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", alphabet_len);
+    abort();
+  }
+  if (shm > 64 * 1024) raise_lds_limit<k_texts_sample>(160 * 1024 - 64);
+  TextsSample p = {first, (DevRng *)rng, text, len, done, hid0, row0, alphabet_len, head, max_len, t, stop_point, bias};
+  RAMD_LAUNCH(k_texts_sample, dim3(rows), dim3(256), shm, st, v, p);
 }
 
 extern "C" void ramd_launch_sigmoid_mse_error(ramd_stream_t st_, const RamdShape *sh,

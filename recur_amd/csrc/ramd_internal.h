@@ -250,6 +250,15 @@ void ramd_launch_texts_step(ramd_stream_t st, const RamdShape *sh, const RamdBuf
                             const unsigned char *text, const unsigned long long *off, const int *skip, double *acc,
                             const float *hid0, int alphabet_len, int n_sums, int t_score, int a_score, int t_feed,
                             int a_feed);
+/* the launch between two forward passes of rnn_amd_sample_texts, launch t = 0 .. max_len of a wave of `rows` texts on
+ * forward-only state rows row0 ...: for t > 0 draws symbol t - 1 of every row that is not done from head `head` of
+ * alphabet_len outputs of its output row (sample_rule.h: the biased clamped softmax, a draw with rng[row], or the best
+ * output when bias >= 100) into text[row][max_len], counts it in len[row] and sets done[row] (1: it was stop_point, 2: the
+ * draw failed); for t < max_len builds the input row of the next forward pass (the one-hot of that symbol on the row's
+ * hidden values; for t == 0 of first[row] on hid0's).  All pointers are device pointers; rng is [rows] rand_ctx. */
+void ramd_launch_texts_sample(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
+                              const int *first, void *rng, unsigned char *text, int *len, int *done, const float *hid0,
+                              int alphabet_len, int head, int max_len, int t, int stop_point, float bias);
 /* rnnca's loss (gstrnnca.c:701-714): sigmoid in place on the first n outputs, slope * (target -
  * a) into o_error; targets is a device array [nrows][ld] */
 void ramd_launch_sigmoid_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,

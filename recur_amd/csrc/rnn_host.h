@@ -216,6 +216,9 @@ void ramd_fused_net_update(RamdEngine *e, RecurNN *net, int row, unsigned batch_
 
 /* texts_api.c: the refusals of rnn_amd_run_texts / _heads (alphabet_len 0: no heads), which need no device: -1 with a
  * message on stderr, else 0 */
+/* the part of them that is about the net, shared with rnn_amd_sample_texts (sample_api.c): a bottom layer, heads that do
+ * not divide the output row */
+int ramd_texts_net_refused(const char *who, const RecurNN *net, int alphabet_len);
 int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const *texts, const int *lens, int n_texts,
                            int alphabet_len, const void *out);
 

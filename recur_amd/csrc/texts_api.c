@@ -8,12 +8,7 @@
 #include "rnn_host.h"
 #include "texts_plan.h"
 
-int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const *texts, const int *lens, int n_texts,
-                           int alphabet_len, const void *out) {
-  if (!net || n_texts < 0) {
-    fprintf(stderr, "librecur_amd: %s: %d texts\n", who, n_texts);
-    return -1;
-  }
+int ramd_texts_net_refused(const char *who, const RecurNN *net, int alphabet_len) {
   if (net->bottom_layer) {
     /* the layer has ONE input buffer for every clone (recur-nn-init.c:345-346; RamdBuffers.blast): "independent clones
      * of the net" is not a state the reference can be in */
@@ -23,6 +18,18 @@ int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const 
   }
   if (alphabet_len && (alphabet_len < 0 || net->output_size % alphabet_len != 0)) {
     fprintf(stderr, "librecur_amd: %s: %d outputs are not whole heads of %d\n", who, net->output_size, alphabet_len);
+    return -1;
+  }
+  return 0;
+}
+
+int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const *texts, const int *lens, int n_texts,
+                           int alphabet_len, const void *out) {
+  if (!net || n_texts < 0) {
+    fprintf(stderr, "librecur_amd: %s: %d texts\n", who, n_texts);
+    return -1;
+  }
+  if (ramd_texts_net_refused(who, net, alphabet_len)) {
     return -1;
   }
   if (n_texts > 0 && (!texts || !lens || !out)) {

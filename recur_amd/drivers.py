@@ -4,7 +4,8 @@
 tests also point it at the compiled reference) exactly the way the reference's own caller does (rnn_char_epoch,
 charmodel-predict.c:288-311).  ``AmdBatchedSet`` drives the additive batched entry points (include/recur_amd.h
 part 2): the whole set per call, text on the device.  ``run_texts`` scores a list of encoded texts against one net in
-one batched call (rnn_amd_run_texts / _heads).  ``synthetic_text_np`` is the seeded symbol stream of
+one batched call (rnn_amd_run_texts / _heads), ``sample_texts`` draws a batch of texts from one net in one batched call
+(rnn_amd_sample_texts).  ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
 """
@@ -72,6 +73,25 @@ def run_texts(lib, net, texts, skips=None, alphabet_len=0):
     if r != 0:
         raise ValueError("rnn_amd_run_texts refused the batch (see stderr)")
     return sums if alphabet_len else sums[:, 0]
+
+
+def sample_texts(lib, net, first, seeds, max_len, bias=0.0, stop=-1, alphabet_len=0, head=0):
+    """rnn_amd_sample_texts: len(first) texts of up to max_len symbols drawn from one net in one batched call, text k from
+    symbol first[k] with a generator seeded seeds[k].  Returns (the list of uint8 arrays, the generators afterwards as a
+    uint64 array [len(first)][4])."""
+    fst = np.ascontiguousarray(first, dtype=np.int32)
+    sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+    n = len(fst)
+    assert len(sd) == n
+    out = np.full((max(n, 1), max(max_len, 1)), 0xEE, np.uint8)
+    lens = np.full(max(n, 1), -1, np.int32)
+    rng = np.zeros((max(n, 1), 4), np.uint64)
+    r = lib.rnn_amd_sample_texts(net, rc.iptr(fst), sd.ctypes.data_as(C.POINTER(C.c_uint64)), n, max_len, bias, stop,
+                                 alphabet_len, head, rc.u8ptr(out), rc.iptr(lens), rng.ctypes.data_as(C.POINTER(rc.RandCtx)))
+    if r != 0:
+        raise ValueError("rnn_amd_sample_texts refused the batch or a draw failed (see stderr)")
+    assert all(np.all(out[k, lens[k]:max_len] == 0xEE) for k in range(n)), "symbols behind a text's length"
+    return [out[k, :lens[k]].copy() for k in range(n)], rng[:n]
 
 
 class ApiSet:

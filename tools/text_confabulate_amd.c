@@ -3,7 +3,11 @@
  * sample characters from its predictions.
  *
  *   text_confabulate_amd -f NET [-B bias] [-n chars] [-p prefix] [-u until_char]
- *                        [-w wait_for_char] [-r seed]
+ *                        [-w wait_for_char] [-r seed] [-N passages]
+ *
+ * -N n: n passages, one per line, each from the (primed) net's state with a generator of its own seeded seed, seed + 1,
+ * ..., all drawn in one batched device run (rnn_amd_char_confabulate_texts).  Without -N the one passage is drawn with the
+ * net's own generator, as ever.  -w has no batched form (priming is what brings a net to a starting point).
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -29,9 +33,9 @@ static void seed_rng(rand_ctx *x, u64 seed) {
 int main(int argc, char **argv) {
   const char *netfile = NULL, *prefix = NULL, *until = NULL, *wait_for = NULL;
   float bias = 0;
-  int chars = 72, opt;
+  int chars = 72, opt, passages = -1;
   long long seed = 2;
-  while ((opt = getopt(argc, argv, "f:B:n:p:u:w:r:")) != -1) {
+  while ((opt = getopt(argc, argv, "f:B:n:p:u:w:r:N:")) != -1) {
     switch (opt) {
     case 'f': netfile = optarg; break;
     case 'B': bias = atof(optarg); break;
@@ -40,8 +44,14 @@ int main(int argc, char **argv) {
     case 'u': until = optarg; break;
     case 'w': wait_for = optarg; break;
     case 'r': seed = atoll(optarg); break;
+    case 'N': passages = atoi(optarg); break;
     default: fprintf(stderr, "usage: %s -f NET [-B bias] [-n chars] [-p prefix]\n", argv[0]); return 2;
     }
+  }
+  if (passages >= 0 && wait_for) {
+    fprintf(stderr, "usage: %s -f NET -N passages [-B bias] [-n chars] [-p prefix] [-u until_char] [-r seed]: -w does not go "
+                    "with -N\n", argv[0]);
+    return 2;
   }
   RecurNN *net = netfile ? rnn_load_net(netfile) : NULL;
   if (!net || !net->metadata) {
@@ -63,6 +73,29 @@ int main(int argc, char **argv) {
   char *t = malloc(byte_len);
   int stop_point = until ? rnn_char_get_codepoint(alphabet, until) : -1;
   int start_point = wait_for ? rnn_char_get_codepoint(alphabet, wait_for) : -1;
+  if (passages >= 0) {
+    u64 *seeds = malloc(sizeof(u64) * (passages + 1));
+    char **lines = malloc(sizeof(char *) * (passages + 1));
+    int *bytes = malloc(sizeof(int) * (passages + 1));
+    for (int k = 0; k < passages; k++) {
+      seeds[k] = (u64)seed + (u64)k;
+      lines[k] = malloc(byte_len);
+    }
+    int r = rnn_amd_char_confabulate_texts(net, alphabet, seeds, passages, chars, bias, prev_char, stop_point, lines,
+                                           byte_len, bytes);
+    for (int k = 0; k < passages; k++) {
+      fputs(lines[k], stdout);
+      fputs("\n", stdout);
+      free(lines[k]);
+    }
+    free(seeds);
+    free(lines);
+    free(bytes);
+    free(t);
+    rnn_char_free_alphabet(alphabet);
+    rnn_delete_net(net);
+    return r ? 1 : 0;
+  }
   rnn_char_confabulate(net, t, chars, byte_len, alphabet, bias, &prev_char, start_point, stop_point);
   fputs(t, stdout);
   fputs("\n", stdout);
