@@ -122,9 +122,11 @@ static inline CalcPlan ramd_plan_calc_deltas(const RamdShape *sh, const RamdBuff
                   !(flags & (RAMD_NO_HO_DELTA | RAMD_IH_SCALE_IN_RATE));
   /* ---- the top layer's delta.  When k_delta_direct carries the update, delta and update ride in ITS first
    * microseconds (HoWork's preconditions: up to 256 streams, o_size <= 48, five rows of ho_delta per workgroup at most) */
-  /* (not where the chain launch has workgroups without chain work -- half of it or more, ramd_chain_steps: there the
-   * request costs the chain nothing, here it costs 2.4 us: the 48 loads per wave queue behind the ring's at the CU's
-   * 64 bytes per clock.  256 streams at hidden 1024: chain 107.6 -> 104.1 us, this launch 91.9 -> 94.3, generation 221.0 -> 219.9) */
+  /* (not where the chain launch has workgroups without chain work -- half of it or more, chain_plan.h: chain_segment's
+   * idle_only: there the request costs the chain nothing, here it costs 2.4 us: the 48 loads per wave queue behind the
+   * ring's at the CU's 64 bytes per clock.  256 streams at hidden 1024: chain 107.6 -> 104.1 us, this launch 91.9 -> 94.3,
+   * generation 221.0 -> 219.9.  They are two rules, not one: this one counts 32-stream row tiles whatever tiles the chain
+   * picks, so at hidden 1024 with 128 streams the two differ) */
   p.ho_in_delta = p.direct_fuse && defer->fuse_method == 0 && !ranges && !active && nrows >= 16 && nrows <= 256 &&
                   sh->O <= 48 && sh->O % 4 == 0 && sh->H <= 5 * dtiles && (nrows / 32) * (sh->hidden_size / 32) > 128 &&
                   env_int("RECUR_AMD_HO_IN_DELTA", 1);

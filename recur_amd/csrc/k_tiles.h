@@ -1,4 +1,4 @@
-// k_tiles.h -- the tile sizes that both the kernels and the launchers' planning (calc_plan.h, fwd_plan.h) read, and the split-K
+// k_tiles.h -- the tile sizes that both the kernels and the launchers' planning (calc_plan.h, chain_plan.h, fwd_plan.h) read, and the split-K
 // rule.  No HIP here: the host compiler alone can include it.
 #pragma once
 #include <stddef.h>

@@ -1,6 +1,7 @@
 // kernels_chain.hip -- the BPTT chain E_i = E_h . W_ih^T over the D steps (recur-nn.c:338-376): a launch per step
 // (k_chain_main, k_chain_wide) or all steps in one launch (k_chain_persist), and their launch logic.
 #include "k_common.h"
+#include "chain_plan.h"
 #ifdef PC_STAMPS /* development builds only: stamps of the chain's tail (tools/gpu_chain_stamps.py) */
 __device__ unsigned long long g_xc_stamps[32];
 #define XC_STAMP(i) do { if (blockIdx.x == 0 && threadIdx.x == ((i) == 10 ? 256 : 0)) g_xc_stamps[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
@@ -1232,72 +1233,57 @@ extern "C" unsigned ramd_chain_abort_word(void) {
   return g_chain_abort_host ? *(volatile unsigned *)g_chain_abort_host : 0u;
 }
 
-static bool chain_persist_ok(hipStream_t st, const RamdShape *sh, const RamdBuffers *b, int nrows) {
-  const int hs = sh->hidden_size;
-  if (b->uniform_idx < 0 || (hs != 1024 && hs != 512 && hs != 256) || nrows < 1 || nrows % 16 != 0 ||
-      sh->D > 60 || g_chain_broken || !env_int("RECUR_AMD_CHAIN_PERSIST", 1))
-    return false;
+// chain_plan.h decides; what follows launches what the plan says, each kernel family from one place.
+
+/* the one-launch chain is available: the probe (at the first call that asks) has validated the device and no launch has given up */
+static bool chain_available(hipStream_t st) {
   chain_validate(st);
-  return g_chain_validated;
+  return g_chain_validated && !g_chain_broken;
 }
 
-template <int ACT, int K>
-static void launch_chain_persist_k(hipStream_t st, const View *d_view, const RamdShape *sh,
-                                   const RamdBuffers *b, int row0, int nrows, unsigned seq, bool one, int nvalid,
-                                   int vlo, const HoWork &hw, const XcWork &xc) {
+/* one launch of k_chain_persist: its segment and what rides in it */
+struct PersistLaunch {
+  hipStream_t st;
+  const View *d_view;
+  int uniform_idx, D;
+  ChainSegment s;
+  unsigned seq;
+  HoWork hw;
+  XcWork xc;
+};
+
+template <int ACT, int K, bool ONE, bool PAD, bool XD> static void launch_persist(const PersistLaunch &c) {
   /* 2: seat from the CU's hardware number (robust beside other work); 1: from the workgroup number (on request, and
    * not beside this process's own side streams); 0: a ticket per workgroup */
   const int use_static = g_seat_table ? 2 : (g_xcd_static && !g_side_streams) ? 1 : 0;
   const unsigned tseq = use_static ? 0u : ++g_ticket_launches;
-  raise_lds_limit<k_chain_persist<ACT, K, false>>(pc_lds_bytes(K));
-  raise_lds_limit<k_chain_persist<ACT, K, true>>(pc_lds_bytes(K));
-  raise_lds_limit<k_chain_persist<ACT, K, true, true>>(pc_lds_bytes(K));
-  if constexpr (K >= 512) {
-    if (xc.on && xc.dense) { /* the tail for dense inputs */
-      raise_lds_limit<k_chain_persist<ACT, K, false, false, true>>(pc_lds_bytes(K));
-      raise_lds_limit<k_chain_persist<ACT, K, true, false, true>>(pc_lds_bytes(K));
-      raise_lds_limit<k_chain_persist<ACT, K, true, true, true>>(pc_lds_bytes(K));
-      if (one && (nvalid < nrows || vlo > 0))
-        RAMD_LAUNCH((k_chain_persist<ACT, K, true, true, true>), dim3(256), dim3(512), pc_lds_bytes(K), st, d_view,
-                    b->uniform_idx, row0, nrows, sh->D, seq, g_chain_sync, g_chain_abort_dev, nvalid, vlo, hw, xc, (int)use_static, tseq, g_seats);
-      else if (one)
-        RAMD_LAUNCH((k_chain_persist<ACT, K, true, false, true>), dim3(256), dim3(512), pc_lds_bytes(K), st, d_view,
-                    b->uniform_idx, row0, nrows, sh->D, seq, g_chain_sync, g_chain_abort_dev, nrows, 0, hw, xc, (int)use_static, tseq, g_seats);
-      else
-        RAMD_LAUNCH((k_chain_persist<ACT, K, false, false, true>), dim3(256), dim3(512), pc_lds_bytes(K), st, d_view,
-                    b->uniform_idx, row0, nrows, sh->D, seq, g_chain_sync, g_chain_abort_dev, nrows, 0, hw, xc, (int)use_static, tseq, g_seats);
-      return;
-    }
+  raise_lds_limit<k_chain_persist<ACT, K, ONE, PAD, XD>>(pc_lds_bytes(K));
+  RAMD_LAUNCH((k_chain_persist<ACT, K, ONE, PAD, XD>), dim3(256), dim3(512), pc_lds_bytes(K), c.st, c.d_view, c.uniform_idx,
+              c.s.row0, c.s.nrows, c.D, c.seq, g_chain_sync, g_chain_abort_dev, c.s.nvalid, c.s.vlo, c.hw, c.xc, use_static, tseq,
+              g_seats);
+}
+template <int ACT, int K, bool XD> static void launch_persist_tiles(const PersistLaunch &c) {
+  if (c.s.pad) launch_persist<ACT, K, true, true, XD>(c);
+  else if (c.s.one) launch_persist<ACT, K, true, false, XD>(c);
+  else launch_persist<ACT, K, false, false, XD>(c);
+}
+template <int ACT, int K> static void launch_persist_tail(const PersistLaunch &c) {
+  if constexpr (K >= 512) /* the tail for dense inputs */
+    if (c.xc.on && c.xc.dense) return launch_persist_tiles<ACT, K, true>(c);
+  launch_persist_tiles<ACT, K, false>(c);
+}
+template <int ACT> static void launch_persist_k(const PersistLaunch &c, int hidden_size) {
+  switch (hidden_size) {
+  case 1024: return launch_persist_tail<ACT, 1024>(c);
+  case 512: return launch_persist_tail<ACT, 512>(c);
+  default: return launch_persist_tail<ACT, 256>(c);
   }
-  if (one && (nvalid < nrows || vlo > 0))
-    RAMD_LAUNCH((k_chain_persist<ACT, K, true, true>), dim3(256), dim3(512), pc_lds_bytes(K), st, d_view,
-                b->uniform_idx, row0, nrows, sh->D, seq, g_chain_sync, g_chain_abort_dev, nvalid, vlo, hw, xc, (int)use_static, tseq, g_seats);
-  else if (one)
-    RAMD_LAUNCH((k_chain_persist<ACT, K, true>), dim3(256), dim3(512), pc_lds_bytes(K), st, d_view,
-                b->uniform_idx, row0, nrows, sh->D, seq, g_chain_sync, g_chain_abort_dev, nrows, 0, hw, xc, (int)use_static, tseq, g_seats);
-  else
-    RAMD_LAUNCH((k_chain_persist<ACT, K, false>), dim3(256), dim3(512), pc_lds_bytes(K), st, d_view,
-                b->uniform_idx, row0, nrows, sh->D, seq, g_chain_sync, g_chain_abort_dev, nrows, 0, hw, xc, (int)use_static, tseq, g_seats);
 }
-
-/* row tiles per launch: 8 XCDs x (32 seats / column tiles) */
-static int chain_persist_seats(const RamdShape *sh) {
-  const int nt = sh->hidden_size / 32; /* column tiles; the one-launch chain exists for 8, 16 and 32 of them */
-  return nt > 0 && nt <= 32 ? 8 * (32 / nt) : 0;
-}
-/* 16-stream row tiles (one sub-chain per workgroup) when they all still fit one launch: twice the
- * CUs for a small set; otherwise 32-stream tiles, which move more streams per microsecond */
-static bool chain_persist_one(const RamdShape *sh, int nrows) {
-  return nrows / 16 <= chain_persist_seats(sh) && (nrows % 32 != 0 || env_int("RECUR_AMD_CHAIN_ONE", 1));
-}
-static int chain_persist_rows(const RamdShape *sh, bool one) { return chain_persist_seats(sh) * (one ? 16 : 32); }
 
 /* `ho`: a pending request for the top layer's delta rides in this launch (and is marked done when the launch stands) */
-static bool launch_chain_persist(hipStream_t st, const View *d_view, const RamdShape *sh,
-                                 const RamdBuffers *b, int row0, int nrows, bool one, int nvalid, int vlo, HoWork *ho,
-                                 XcWork *xcp) {
-  HoWork hw = {};
-  XcWork xc = {};
+static bool launch_chain_persist(hipStream_t st, const View *d_view, const RamdShape *sh, const RamdBuffers *b,
+                                 const ChainSegment &s, HoWork *ho, XcWork *xcp) {
+  PersistLaunch c = {st, d_view, b->uniform_idx, sh->D, s, 0u, {}, {}};
   /* RECUR_AMD_CHAIN_CHECK=1 -- for a GPU that is shared, where a co-tenant may take CUs in mid-run: every chain
    * launch is followed by a synchronisation and a look at the abort word.  A launch that gave up is then not fatal:
    * the word is reset, the one-launch chain is switched off for the process and THIS call's chain runs again a
@@ -1308,14 +1294,11 @@ static bool launch_chain_persist(hipStream_t st, const View *d_view, const RamdS
    * gave up (tests). */
   const int test_giveup = env_int("RECUR_AMD_CHAIN_TEST_GIVEUP", 0);
   const bool checked = env_int("RECUR_AMD_CHAIN_CHECK", 0) || test_giveup > 1;
-  if (xcp && !checked) xc = *xcp;
-  if (xcp && !xc.on) xcp->on = 0; /* (the caller then runs the extras as a launch of their own) */
+  if (xcp && !checked) c.xc = *xcp;
+  if (xcp && !c.xc.on) xcp->on = 0; /* (the caller then runs the extras as a launch of their own) */
   if (ho && !ho->done) {
-    hw = *ho;
-    /* the launch's workgroups without chain work, if they are at least half of it, else all 256 */
-    const int busy = (nrows / (one ? 16 : 32)) * (sh->hidden_size / 32);
-    hw.idle_only = 256 - busy >= 128;
-    hw.workers = hw.idle_only ? 256 - busy : 256;
+    c.hw = *ho;
+    c.hw.workers = s.workers, c.hw.idle_only = s.idle_only;
   }
   if (g_chain_seq >= (1u << 25)) { /* flags are seq * 64 + step and compare as unsigned numbers: start over */
     HIP_CHECK(hipStreamSynchronize(st));
@@ -1323,18 +1306,11 @@ static bool launch_chain_persist(hipStream_t st, const View *d_view, const RamdS
     g_chain_seq = 0;
     g_ticket_launches = 0;
   }
-  const unsigned seq = ++g_chain_seq;
+  c.seq = ++g_chain_seq;
   int ev = timing_begin(st, T_CHAIN, 1);
-#define CHAIN_PERSIST(ACT)                                                                  \
-  do {                                                                                      \
-    if (sh->hidden_size == 1024) launch_chain_persist_k<ACT, 1024>(st, d_view, sh, b, row0, nrows, seq, one, nvalid, vlo, hw, xc); \
-    else if (sh->hidden_size == 512) launch_chain_persist_k<ACT, 512>(st, d_view, sh, b, row0, nrows, seq, one, nvalid, vlo, hw, xc); \
-    else launch_chain_persist_k<ACT, 256>(st, d_view, sh, b, row0, nrows, seq, one, nvalid, vlo, hw, xc);         \
-  } while (0)
-  if (sh->activation == 2) CHAIN_PERSIST(2);
-  else if (sh->activation == 5) CHAIN_PERSIST(5);
-  else CHAIN_PERSIST(1);
-#undef CHAIN_PERSIST
+  if (sh->activation == 2) launch_persist_k<2>(c, sh->hidden_size);
+  else if (sh->activation == 5) launch_persist_k<5>(c, sh->hidden_size);
+  else launch_persist_k<1>(c, sh->hidden_size);
   timing_end(st, ev);
   if (checked) {
     static int checked_launches = 0;
@@ -1352,8 +1328,49 @@ static bool launch_chain_persist(hipStream_t st, const View *d_view, const RamdS
       return false;
     }
   }
-  if (ho && hw.dst) ho->done = 1;
+  if (ho && c.hw.dst) ho->done = 1;
   return true;
+}
+
+/* the launch-per-step forms: D launches of one kernel over the call's rows */
+struct StepsLaunch {
+  hipStream_t st;
+  const View *d_view;
+  int uniform_idx, row0, nrows, D;
+  ChainSteps f;
+};
+template <int NS, int MT> static void launch_wide_steps(const StepsLaunch &c) {
+  const size_t shm = (size_t)W_STAGES * W_STAGE_FLOATS * sizeof(float);
+  raise_lds_limit<k_chain_wide<NS, MT>>((int)shm);
+  for (int t = 0; t < c.D; t++)
+    RAMD_LAUNCH((k_chain_wide<NS, MT>), dim3(c.f.blocks), dim3(512), shm, c.st, c.d_view, c.uniform_idx, c.row0, c.nrows, t,
+                c.f.tm, c.f.tn);
+}
+template <int NS> static void launch_wide_mt(const StepsLaunch &c) {
+  if (c.f.mt == 32) launch_wide_steps<NS, 32>(c);
+  else launch_wide_steps<NS, 64>(c);
+}
+template <bool UNI, int NS> static void launch_main_steps(const StepsLaunch &c) {
+  for (int t = 0; t < c.D; t++)
+    RAMD_LAUNCH((k_chain_main<UNI, NS>), dim3(c.f.blocks), dim3(512), 0, c.st, c.d_view, c.uniform_idx, c.row0, c.nrows, t,
+                c.f.tm, c.f.tn, c.f.nstages);
+}
+static void launch_chain_steps(const StepsLaunch &c) {
+  /* one event pair around the D launches: the per-launch average then carries
+   * 1/D of the event overhead instead of all of it */
+  int ev = timing_begin(c.st, T_CHAIN, c.D);
+  const int ns = c.f.ns;
+  if (c.f.form == CHAIN_WIDE) {
+    if (ns == 32) launch_wide_mt<32>(c);
+    else if (ns == 24) launch_wide_mt<24>(c);
+    else launch_wide_mt<16>(c);
+  } else if (!c.f.uniform) launch_main_steps<false, 0>(c);
+  else if (ns == 16) launch_main_steps<true, 16>(c);
+  else if (ns == 8) launch_main_steps<true, 8>(c);
+  else if (ns == 4) launch_main_steps<true, 4>(c);
+  else if (ns == 2) launch_main_steps<true, 2>(c);
+  else launch_main_steps<true, 0>(c);
+  timing_end(c.st, ev);
 }
 
 /* All D steps of the chain for streams [row0, row0 + nrows) (the part of rnn_bptt_calc_deltas between the
@@ -1361,108 +1378,17 @@ static bool launch_chain_persist(hipStream_t st, const View *d_view, const RamdS
  * step with 64 x 64 or 32 x 32 tiles.  Returns the partial sums of squares per (step, stream) it left. */
 int ramd_chain_steps(hipStream_t st, const View &v, const RamdShape *sh, const RamdBuffers *b, int row0,
                      int nrows, HoWork *ho, XcWork *xc) {
-  const int tn = (sh->hidden_size + CN - 1) / CN;
-  int tn_parts = tn; /* one per column tile of the chain kernel used */
-  int tm = (nrows + CM - 1) / CM;
-  int nstages = (sh->hidden_size + CK - 1) / CK; /* K = the hidden columns 1..hidden_size */
-  int blocks = ((tn + 7) / 8) * 8 * tm;
-  /* one event pair around the D launches: the per-launch average then carries
-   * 1/D of the event overhead instead of all of it */
   const View *d_view = device_view(st, v);
-  /* a set that is not whole 16-row tiles runs over the rows above it (Scap is a multiple of 16:
-   * they exist), which are multiplied along and never stored (PAD) -- a one-net trainer or a
-   * per-net call then takes the one-launch chain with a single tile instead of D launches */
-  int chain_rows = nrows;
-  if (nrows % 16 != 0 && row0 + ((nrows + 15) & ~15) <= sh->Scap) chain_rows = (nrows + 15) & ~15;
-  /* ... and a small set that does not start on a tile boundary (a per-net call on stream j):
-   * the tiles from the boundary below it, one launch */
-  const int span_base = row0 & ~15, span = ((row0 + nrows + 15) & ~15) - span_base;
-  const bool windowed = span_base != row0 && span_base + span <= sh->Scap && chain_persist_ok(st, sh, b, span) &&
-                        span / 16 <= chain_persist_seats(sh);
-  bool windowed_done = false;
-  if (windowed) {
-    windowed_done = launch_chain_persist(st, d_view, sh, b, span_base, span, true, row0 - span_base + nrows, row0 - span_base, ho, xc);
+  const bool available = chain_persist_wanted(sh, b, row0, nrows) && chain_available(st);
+  const ChainPlan p = ramd_plan_chain(sh, b, row0, nrows, available);
+  bool persist = p.seg_rows > 0;
+  ChainSegment s;
+  /* (RECUR_AMD_CHAIN_CHECK: a launch that gave up ends them; all of the call's rows go through the steps below) */
+  for (int r = 0; persist && chain_segment(p, r, &s); r += s.nrows) persist = launch_chain_persist(st, d_view, sh, b, s, ho, xc);
+  if (!persist) {
+    launch_chain_steps(StepsLaunch{st, d_view, b->uniform_idx, row0, nrows, sh->D, p.steps});
+    return p.steps.tn_parts;
   }
-  bool persist = windowed_done || chain_persist_ok(st, sh, b, chain_rows);
-  if (persist && !windowed_done) { /* as many row tiles per launch as there are seats; more streams: more launches */
-    /* (an odd number of 16-stream tiles beyond one launch: 32-stream tiles, the last 16 streams alone) */
-    for (int r = 0; r < chain_rows;) {
-      const int left = chain_rows - r, real_left = nrows - r;
-      bool one = chain_persist_one(sh, left);
-      int n = 0;
-      if (!one) { /* 32-stream tiles over whole, real tiles only */
-        n = real_left & ~31;
-        if (n > chain_persist_rows(sh, false)) n = chain_persist_rows(sh, false);
-        if (n == 0) one = true;
-      }
-      if (one) {
-        n = chain_persist_rows(sh, true);
-        if (n > left) n = left;
-      }
-      if (!launch_chain_persist(st, d_view, sh, b, row0 + r, n, one, real_left < n ? real_left : n, 0, ho, xc)) {
-        persist = false; /* (RECUR_AMD_CHAIN_CHECK: the launch gave up; all of the call's rows go through the steps below) */
-        break;
-      }
-      r += n;
-    }
-  }
-  if (persist) tn_parts = 0; /* the one-launch chain leaves no partial sums: the extras sum the rows themselves */
-  if (persist && xc && xc->on) xc->done = 1; /* every launch of the chain carried its rows' extras and control */
-  /* big sets of a wide net: 64 x 64 tiles (k_chain_wide), one partial sum per 64 columns */
-  const int wide_ns = sh->hidden_size / WK;
-  /* ... as 32 x 64 tiles where that fills more of the chip: fewer than 192 tiles of 64 streams, and streams a multiple of 32 */
-  const bool wide_half = !persist && b->uniform_idx >= 0 && nrows % 32 == 0 && sh->hidden_size % WN == 0 &&
-                         (nrows / WM) * (sh->hidden_size / WN) < 192 && (nrows / 32) * (sh->hidden_size / WN) >= 128 &&
-                         env_int("RECUR_AMD_CHAIN_WIDE_HALF", 1);
-  const bool wide = !persist && b->uniform_idx >= 0 && (nrows % WM == 0 || wide_half) && sh->hidden_size % WN == 0 &&
-                    (wide_ns == 16 || wide_ns == 24 || wide_ns == 32) &&
-                    ((nrows / WM) * (sh->hidden_size / WN) >= 128 || wide_half) && env_int("RECUR_AMD_CHAIN_WIDE", 1);
-  if (wide) {
-    const size_t shm = (size_t)W_STAGES * W_STAGE_FLOATS * sizeof(float);
-    raise_lds_limit<k_chain_wide<16>>((int)shm);
-    raise_lds_limit<k_chain_wide<24>>((int)shm);
-    raise_lds_limit<k_chain_wide<32>>((int)shm);
-    raise_lds_limit<k_chain_wide<16, 32>>((int)shm);
-    raise_lds_limit<k_chain_wide<24, 32>>((int)shm);
-    raise_lds_limit<k_chain_wide<32, 32>>((int)shm);
-    const int wtm = nrows / (wide_half ? 32 : WM), wtn = sh->hidden_size / WN;
-    const int wblocks = ((wtn + 7) / 8) * 8 * wtm;
-    tn_parts = wtn;
-    int evw = timing_begin(st, T_CHAIN, sh->D);
-    for (int t = 0; t < sh->D; t++) {
-      if (wide_half && wide_ns == 32)
-        RAMD_LAUNCH((k_chain_wide<32, 32>), dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, t, wtm, wtn);
-      else if (wide_half && wide_ns == 24)
-        RAMD_LAUNCH((k_chain_wide<24, 32>), dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, t, wtm, wtn);
-      else if (wide_half)
-        RAMD_LAUNCH((k_chain_wide<16, 32>), dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, t, wtm, wtn);
-      else if (wide_ns == 32)
-        RAMD_LAUNCH(k_chain_wide<32>, dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, t, wtm, wtn);
-      else if (wide_ns == 24)
-        RAMD_LAUNCH(k_chain_wide<24>, dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, t, wtm, wtn);
-      else
-        RAMD_LAUNCH(k_chain_wide<16>, dim3(wblocks), dim3(512), shm, st, d_view, b->uniform_idx, row0, nrows, t, wtm, wtn);
-    }
-    timing_end(st, evw);
-  }
-  int ev = (persist || wide) ? -1 : timing_begin(st, T_CHAIN, sh->D);
-  for (int t = 0; t < ((persist || wide) ? 0 : sh->D); t++) {
-#define CHAIN_NS(NS)                                                                               \
-RAMD_LAUNCH((k_chain_main<true, NS>), dim3(blocks), dim3(512), 0, st, d_view, b->uniform_idx, \
-                   row0, nrows, t, tm, tn, nstages)
-    const bool exact = sh->hidden_size % CK == 0;
-    if (b->uniform_idx >= 0 && exact && nstages == 8) CHAIN_NS(8);
-    else if (b->uniform_idx >= 0 && exact && nstages == 4) CHAIN_NS(4);
-    else if (b->uniform_idx >= 0 && exact && nstages == 2) CHAIN_NS(2);
-    else if (b->uniform_idx >= 0 && exact && nstages == 16) CHAIN_NS(16);
-    else if (b->uniform_idx >= 0)
-      RAMD_LAUNCH(k_chain_main<true>, dim3(blocks), dim3(512), 0, st, d_view, b->uniform_idx, row0,
-                         nrows, t, tm, tn, nstages);
-    else
-      RAMD_LAUNCH(k_chain_main<false>, dim3(blocks), dim3(512), 0, st, d_view, b->uniform_idx,
-                         row0, nrows, t, tm, tn, nstages);
-#undef CHAIN_NS
-  }
-  timing_end(st, ev);
-  return tn_parts;
+  if (xc && xc->on) xc->done = 1; /* every launch of the chain carried its rows' extras and control */
+  return 0; /* the one-launch chain leaves no partial sums: the extras sum the rows themselves */
 }

@@ -173,17 +173,22 @@ def test_hot_case_stepwise_on_the_direct_delta_path(amd):
     # (k_delta_direct's other forms: equal shares of K for a SIMD's two waves; the top layer's delta left in the chain launch)
     ("RECUR_AMD_DELTA_FAST_PCT=0", "test_full_size_generation_matches_oracle"),
     ("RECUR_AMD_HO_IN_DELTA=0", "test_full_size_generation_matches_oracle"),
+    # (the launch-per-step chain at hidden 1024, where only a switched-off one-launch chain leaves it the call:
+    # k_chain_wide<16, 32> and <16, 64>; test_chain_plan.py: test_where_the_one_launch_chain_does_not_take_the_call)
+    ("RECUR_AMD_CHAIN_PERSIST=0", "test_baseline_config_shapes_one_generation_matches_oracle -k per_step_wide_1024_256_3"),
+    ("RECUR_AMD_CHAIN_PERSIST=0", "test_baseline_config_shapes_one_generation_matches_oracle -k per_step_wide_1024_768_3"),
 ])
 def test_generations_with_the_direct_delta_gemm_switched_off(env, node):
     """k_delta_direct has k_delta_dma + the optimiser launch behind it (split-K planes summed by k_apply): the full-size
     generation and the hot regime at hidden 1024 once more with RECUR_AMD_DELTA_DIRECT=0, each in a process of its own
-    (the library reads its switches once per process)."""
+    (the library reads its switches once per process).  Likewise the one-launch chain and the launch per step behind it."""
     import os
     import subprocess
     import sys
     e = dict(os.environ, **dict(kv.split("=") for kv in env.split()))
+    node, *select = node.split()
     path = "%s::%s" % (os.path.abspath(__file__), node)
-    r = subprocess.run([sys.executable, "-m", "pytest", path, "-q", "-x", "-p", "no:cacheprovider"],
+    r = subprocess.run([sys.executable, "-m", "pytest", path, *select, "-q", "-x", "-p", "no:cacheprovider"],
                        capture_output=True, text=True, env=e, timeout=900, cwd=os.path.dirname(os.path.abspath(__file__)))
     assert r.returncode == 0 and "1 passed" in r.stdout, r.stdout[-3000:] + r.stderr[-2000:]
 
@@ -511,17 +516,20 @@ def test_empty_and_edge_inputs(amd):
     # so this one checks the non-accumulating batched form twice)
     ("dma_small", dict(input_size=42, hidden_size=128, output_size=42, S=32, D=6, learn_rate=1e-3, seed=34), 9),
     # the one-launch chain with 16-stream row tiles (one sub-chain per workgroup): an odd number of
-    # them, a single one, and hidden 256 where four tiles share an XCD
+    # them, a single one, and hidden 256 where four tiles share an XCD (which launches a shape gets is asserted in
+    # test_chain_plan.py: test_sets_of_whole_tiles_in_one_launch has 256 / 80 / 7)
     ("chain_one_1024_48", dict(input_size=42, hidden_size=1024, output_size=42, S=48, D=6, learn_rate=1e-5, seed=35), 8),
     ("chain_one_1024_16", dict(input_size=42, hidden_size=1024, output_size=42, S=16, D=4, learn_rate=1e-5, seed=36), 6),
     ("chain_one_256_80", dict(input_size=42, hidden_size=256, output_size=42, S=80, D=7, learn_rate=1e-4, seed=37), 9),
     # sets that are not whole 16-stream tiles run the one-launch chain over the unused rows above them
+    # (test_chain_plan.py: test_sets_that_are_not_whole_tiles_run_padded has 1024 / 1 / 5, 512 / 21 / 4 and 1024 / 250 / 3:
+    # seven 32-stream tiles, then two 16-stream tiles of which 26 rows are real)
     ("chain_padded_256_5", dict(input_size=42, hidden_size=256, output_size=42, S=5, D=6, learn_rate=1e-4, seed=39), 9),
     ("chain_padded_1024_1", dict(input_size=42, hidden_size=1024, output_size=42, S=1, D=5, learn_rate=1e-5, seed=40), 7),
     ("chain_padded_512_21", dict(input_size=42, hidden_size=512, output_size=42, S=21, D=4, learn_rate=1e-4, seed=41), 6),
-    # 250 streams at hidden 1024: seven 32-stream tiles, then two 16-stream tiles of which 26 rows are real
     ("chain_padded_1024_250", dict(input_size=42, hidden_size=1024, output_size=42, S=250, D=3, learn_rate=1e-5, seed=42), 4),
     # 17 tiles of 16 streams at hidden 1024: a launch of 32-stream tiles, then the last 16 streams alone
+    # (test_chain_plan.py: test_more_rows_than_one_launch_seats)
     ("chain_mixed_1024_272", dict(input_size=42, hidden_size=1024, output_size=42, S=272, D=3, learn_rate=1e-5, seed=38), 4),
 ])
 def test_fallback_and_boundary_shapes_match_oracle(amd, label, kw, steps):
@@ -692,6 +700,7 @@ def test_a_hundred_generations_at_full_size_track_the_compiled_reference(amd):
     # a GPU's share of 256 streams over 8 GPUs (BASELINE.json configs[3]'s sharding; `bench.py --scaling strong
     # --streams-global 32`; 64 = the share over 4 GPUs is configs[1]'s shape above): two 16-stream row tiles, three
     # quarters of the chain launch's workgroups idle, the extras + control in the tails of the others
+    # (test_chain_plan.py: test_sets_of_whole_tiles_in_one_launch)
     ("small_set_1024_32_20", dict(input_size=42, hidden_size=1024, output_size=42, S=32, D=20)),
     # (hidden 512: the direct weight-delta kernel with K split four ways over workgroups -- 8 x 8 tiles, 44 rest rows as
     # two pieces per workgroup -- and, 12 x 8 tiles, two ways)
@@ -700,18 +709,19 @@ def test_a_hundred_generations_at_full_size_track_the_compiled_reference(amd):
     ("configs4_rnnca_like_2048_512_10", dict(input_size=42, hidden_size=2048, output_size=42, S=512, D=10)),
     # hidden 2048 with fewer streams: the 64 x 64-tile chain step would leave half the chip idle (128 tiles), so
     # the step runs as 32 x 64 tiles with the K of a stage split over the wave pairs (k_chain_wide<NS, 32>);
-    # 96 streams: a multiple of 32 that is not one of 64
+    # 160 streams: a multiple of 32 that is not one of 64 (these two, configs4's 64 x 64 tiles above and hidden 1536
+    # below: test_chain_plan.py, test_wide_nets_a_launch_per_step)
     ("wide_half_tiles_2048_256_7", dict(input_size=42, hidden_size=2048, output_size=42, S=256, D=7)),
     ("wide_half_tiles_resqrt_2048_160_4", dict(input_size=42, hidden_size=2048, output_size=42, S=160, D=4,
                                                 activation=rc.RESQRT)),
-    # more than 8 row tiles: the one-launch chain once per 256 streams
+    # more than 8 row tiles: the one-launch chain once per 256 streams (test_chain_plan.py: test_more_rows_than_one_launch_seats)
     ("two_chain_launches_1024_512_20", dict(input_size=42, hidden_size=1024, output_size=42, S=512, D=20)),
     # fewer than 8 row tiles: XCDs without a row tile leave at once
     ("three_row_tiles_1024_96_12", dict(input_size=42, hidden_size=1024, output_size=42, S=96, D=12)),
     # the other activations' instances of the chain kernels: one sub-chain per workgroup with the
     # RESQRT derivative (hidden 512) and the RECLIP20 row rule (hidden 256), two sub-chains with
-    # RESQRT (hidden 256, 160 streams), and the 64 x 64-tile step with RESQRT (hidden 1536: a
-    # net the one-launch chain does not take)
+    # RESQRT (hidden 256, 640 streams: test_chain_plan.py, test_sets_of_whole_tiles_in_one_launch), and the
+    # 64 x 64-tile step with RESQRT (hidden 1536: a net the one-launch chain does not take)
     ("one_sub_chain_resqrt_512_64_8", dict(input_size=42, hidden_size=512, output_size=42, S=64, D=8,
                                            activation=rc.RESQRT)),
     ("one_sub_chain_reclip20_256_48_8", dict(input_size=42, hidden_size=256, output_size=42, S=48, D=8,
@@ -720,10 +730,18 @@ def test_a_hundred_generations_at_full_size_track_the_compiled_reference(amd):
                                              activation=rc.RESQRT)),
     ("wide_step_resqrt_1536_512_4", dict(input_size=42, hidden_size=1536, output_size=42, S=512, D=4,
                                          activation=rc.RESQRT)),
-    # far more streams than the north star: the one-launch chain in many windows, the delta GEMM over
+    # far more streams than the north star: the one-launch chain in many launches, the delta GEMM over
     # K = S * D = 24,576 and 6,144 rows (tools/gpu_large_sets.py goes on to 16,384 streams)
     ("many_streams_256_4096_6", dict(input_size=42, hidden_size=256, output_size=42, S=4096, D=6)),
     ("many_streams_1024_1536_4", dict(input_size=42, hidden_size=1024, output_size=42, S=1536, D=4)),
+    # the launch-per-step forms that nothing else selected, each at its smallest shape (test_chain_plan.py:
+    # test_wide_nets_a_launch_per_step): 24 stages in 32 x 64 tiles (k_chain_wide<24, 32>: 6 x 24 = 144 tiles of 32 streams,
+    # 72 of 64), and 16 stages in 32 x 64 and 64 x 64 tiles (the latter from 768 streams: 12 x 16 = 192 tiles) -- hidden
+    # 1024, which the one-launch chain takes here and leaves to them in
+    # test_generations_with_the_direct_delta_gemm_switched_off's process without it
+    ("wide_half_step_1536_192_3", dict(input_size=42, hidden_size=1536, output_size=42, S=192, D=3)),
+    ("per_step_wide_1024_256_3", dict(input_size=42, hidden_size=1024, output_size=42, S=256, D=3)),
+    ("per_step_wide_1024_768_3", dict(input_size=42, hidden_size=1024, output_size=42, S=768, D=3)),
 ])
 def test_baseline_config_shapes_one_generation_matches_oracle(amd, label, kw):
     """BASELINE.json's other configurations at their full hidden / stream / depth sizes:
