@@ -203,3 +203,47 @@ def test_one_net(harness):
     has(plan(harness, **dict(small, hidden=252)), hidden="small")  # H = 256, I = 296
     has(plan(harness, **dict(small, hidden=252, input=260)), hidden="gemm")  # I = 516 > 512
     has(plan(harness, **dict(small, output=65)), hidden="gemm")  # O = 68 > 64
+
+
+def test_the_batched_text_runs_shrinking_passes(harness):
+    """rnn_amd_run_texts and rnn_amd_sample_texts: built rows above Scap, no ring position, a row count that falls from
+    the wave's 256 to 1 as texts end.  The shapes are those of tests/test_gpu_texts_wide.py: if a predicate moves, this
+    says which form its nets no longer reach."""
+    def texts(i, h, o, rows):
+        return dict(input=i, hidden=h, output=o, streams=256, nrows=rows, mode=KEEP, rows_built=1, fwd_only=1, advance=0,
+                    uniform_idx=-1)
+
+    # A 42 / 1024 / 42: I = 1068, H = 1028, O = 44; nkt = 34, column tiles ceil(1028 / 64) = 17.  256 rows: 68 tiles, BENCH_KS.
+    # 192: 51 tiles, p = 1 up to k = 5 (255), 2 up to 10, 3 up to 15: k = 5: 6.8 + 2 + 0.75 = 9.55; k = 10: 2 * 3.4 + 2 + 1.5 =
+    # 10.3; k = 15: 3 * 2.267 + 2 + 2.25 = 11.05; k = 16 (p = 4): 4 * 2.125 + 2.67 + 2.4 = 13.57 -> 5
+    # 128 and 65: 34 tiles, p = 1 up to k = 7 (238), 2 up to 15: k = 7: 4.857 + 2 + 1.05 = 7.91; k = 15: 2 * 2.267 + 2 + 2.25 =
+    # 8.78; k = 16 (p = 3): 3 * 2.125 + 2 + 2.4 = 10.78 -> 7
+    # 64 and fewer: 17 tiles, p = 1 up to k = 15 (255): k = 14: 2.429 + 2 + 2.1 = 6.529; k = 15: 2.267 + 2 + 2.25 = 6.517;
+    # k = 16 (p = 2): 2 * 2.125 + 2 + 2.4 = 8.65 -> 15
+    for rows, ks in [(256, BENCH_KS), (192, 5), (128, 7), (65, 7), (64, 15), (63, 15), (17, 15), (1, 15)]:
+        has(plan(harness, **texts(42, 1024, 42, rows)), I=1068, H=1028, O=44, input="built", hidden="gemm", uniform=0, nkt=34,
+            ks=ks, noise="none", end="finalize", output="rows")
+    # B 73 / 99 / 3650 (the multi-head text net): I = 176, H = 100, O = 3652.  Hidden: nkt = 6, at most 4 x 2 tiles, p = 1:
+    # 6 / k + 2 + 0.15 k falls to k = 6 (3.9).  Output: o_nkt = 4, column tiles ceil(3652 / 64) = 58.  256 and 200 rows: 232
+    # tiles -> 1 (test_a_wide_output_layer_on_a_narrow_hidden_layer).  128: 116 tiles: k = 1: 4 + 2 + 0.15 = 6.15; k = 2 (232,
+    # p = 1): 2 + 2 + 0.3 = 4.3; k = 3 (p = 2): 2 * 1.333 + 2 + 0.45 = 5.12; k = 4 (p = 2): 2 + 2 + 0.6 = 4.6 -> 2.  64 and
+    # fewer: 58 tiles, p = 1 up to k = 4 (232): 4 / k + 2 + 0.15 k: k = 3: 3.78; k = 4: 3.6 -> 4
+    for rows, o_ks in [(256, 1), (200, 1), (128, 2), (64, 4), (63, 4), (5, 4), (1, 4)]:
+        has(plan(harness, **texts(73, 99, 3650, rows)), I=176, H=100, O=3652, input="built", hidden="gemm", nkt=6, ks=6,
+            end="finalize", output="gemm", o_nkt=4, o_ks=o_ks)
+    # C 128 / 512 / 4096: I = 644, H = 516 (9 stages of 64), O = 4096 (64 column tiles).  Output: 4, 3 and 2 row tiles x 64 >=
+    # 128 tiles, supertiles ceil(tm / 4) * 8 = 8 -> 256 workgroups.  Hidden: nkt = ceil(644 / 32) = 21, column tiles 9.
+    # 256 rows: 36 tiles, p = 1 up to k = 7 (252), 2 up to 14: k = 7: 3 + 2 + 1.05 = 6.05; k = 14: 2 * 1.5 + 2 + 2.1 = 7.1 -> 7
+    # 192: 27 tiles, p = 1 up to k = 9 (243), 2 up to 16: k = 9: 2.333 + 2 + 1.35 = 5.68; k = 16: 2 * 1.3125 + 2 + 2.4 = 7.03 -> 9
+    # 128: 18 tiles, p = 1 up to k = 14 (252): 21 / k + 0.15 k: k = 11: 3.559; k = 12: 3.55; k = 13: 3.565 -> 12
+    for rows, tm, ks in [(256, 4, 7), (192, 3, 9), (128, 2, 12)]:
+        has(plan(harness, **texts(128, 512, 4096, rows)), I=644, H=516, O=4096, input="built", hidden="gemm", nkt=21, ks=ks,
+            end="finalize", output="wide", o_ns=9, o_tm=tm, o_tn=64, o_blocks=256)
+    # 64 rows are 64 tiles, fewer than 128; 1 row is no multiple of 64.  o_nkt = ceil(516 / 32) = 17, 64 tiles: p = 1 up to
+    # k = 4 (256), 2 up to 8, 3 up to 12: k = 4: 4.25 + 2 + 0.6 = 6.85; k = 8: 2 * 2.125 + 2 + 1.2 = 7.45; k = 12: 3 * 1.417 + 2 +
+    # 1.8 = 8.05; k = 16 (p = 4): 4 * 1.0625 + 2.67 + 2.4 = 9.32 -> 4
+    for rows in (64, 1):
+        has(plan(harness, **texts(128, 512, 4096, rows)), input="built", hidden="gemm", nkt=21, output="gemm", o_nkt=17, o_ks=4)
+    # D 4 / 64 / 4: I = 72, H = 68, O = 4.  nkt = 3, at most 2 tiles, p = 1: 3 / k + 2 + 0.15 k falls to k = 3 (3.45)
+    has(plan(harness, **texts(4, 64, 4, 64)), I=72, H=68, O=4, input="built", hidden="gemm", nkt=3, ks=3, end="finalize", output="o4")
+    has(plan(harness, **texts(4, 64, 4, 63)), input="built", hidden="gemm", nkt=3, ks=3, end="finalize", output="rows")

@@ -6,7 +6,11 @@ its division.  The bar is the project's parity bar, |got - want| <= 1e-4 |want|;
 exactly 0.0 (the oracle is not asked then: its skip loop would read past the text, charmodel-predict.c:67-69).
 
 The nets are erewhon_case.KW-shaped, trained for 60 generations so that entropies are a few bits -- far from 0 and from the
--100 cap of capped_log2f.  Texts are slices of the erewhon text."""
+-100 cap of capped_log2f.  Texts are slices of the erewhon text.
+
+With 42, 73 or 3 x 14 outputs and 39 to 256 hidden values every forward pass of this module is planned output=rows
+(k_out_layer; fwd_plan.h).  The other output-layer forms on these rows -- the MFMA GEMM with k_sum_slabs, k_fwd_wide,
+k_out_layer_o4 --, more heads than k_texts_step has waves, and hidden 1024 are tests/test_gpu_texts_wide.py's."""
 import ctypes as C
 import os
 import subprocess
@@ -71,7 +75,7 @@ def oracle_like(lib, a, net, S):
     a.sync()
     n = a.net.contents
     o = sc.OracleSet(input_size=a.input_size, hidden_size=a.hidden_size, output_size=a.output_size, S=S, D=1,
-                     learn_rate=1e-3, seed=1)
+                     activation=n.activation, learn_rate=1e-3, seed=1)
     o.arrays()["ih_w"][:] = rc.view(n.ih_weights, a.I, a.H)
     o.arrays()["ho_w"][:] = rc.view(n.ho_weights, a.H, a.O)
     o.arrays()["hidden"][:] = hidden_row(lib, net)[None, :]

@@ -16,7 +16,9 @@ With bias >= 100 there is no draw: the device's pick must be a best output of th
 size), the strict pick is the last of equal maxima, and the generators are what they were seeded to.
 
 The nets are the `trained()` nets of test_gpu_run_texts.py (erewhon, 60 generations), shared with that module.  No test
-here feeds NaNs or otherwise aims at the draw's attempt cap: tests/test_sample_rule.py covers it on the CPU."""
+here feeds NaNs or otherwise aims at the draw's attempt cap: tests/test_sample_rule.py covers it on the CPU.  Their shapes
+keep every forward pass on output=rows (k_out_layer; fwd_plan.h) and the head at 2 of 3 at most: the other output-layer
+forms, a head far into a wide row and hidden 1024 are tests/test_gpu_texts_wide.py's."""
 import ctypes as C
 import os
 import subprocess
