@@ -658,6 +658,31 @@ int rnn_amd_run_texts_heads(RecurNN *net, const u8 *const *texts, const int *len
 int rnn_amd_sample_texts(RecurNN *net, const int *first, const u64 *seeds, int n_texts, int max_len, float bias,
                          int stop_point, int alphabet_len, int head, u8 *out /* [n_texts][max_len] */, int *out_lens,
                          rand_ctx *rng_out /* [n_texts] or NULL */);
+/* Many PROMPTS continued by one net in one batched device run: rnn_amd_sample_texts with a prompt per row in front of
+ * the draws.  Row k of `out` is what this loop writes on a forward-only clone c_k of `net` whose hidden row starts as a
+ * copy of net's hidden row at the moment of the call and whose generator is init_rand64(seeds[k]):
+ *     feed prompts[k][0 .. prompt_lens[k] - 2] as one-hot opinions: nothing is drawn, the generator is not touched
+ *         (rnn_char_prime's loop; rnn_amd_run_text with skip >= len - 1)
+ *     then exactly rnn_amd_sample_texts's loop with first = prompts[k][prompt_lens[k] - 1]: up to max_len symbols, each
+ *         drawn from head `head` of alphabet_len outputs, sharpened by `bias`, ending after it has written stop_point
+ * A stop symbol inside a prompt ends nothing.  Only the continuation is written to `out`, not the prompt; out_lens and
+ * rng_out mean what they mean for rnn_amd_sample_texts, and what is said there about draws within rounding of a boundary
+ * holds here.  `net` itself -- host and device copies, hidden row, generator -- is left exactly as it was.
+ * The rows run side by side, ordered by prompt_lens[k] + max_len, longest first, in waves of up to 256 (the layout of
+ * rnn_amd_run_texts): a row takes part in prompt_lens[k] + max_len - 1 forward passes, whose row count falls as the
+ * shorter rows end; one launch between two passes feeds a row its next prompt symbol or draws for it.  One device
+ * synchronisation per wave and one more every 64 steps, to end a wave whose every running row has met its stop symbol.
+ * With one-symbol prompts the call is rnn_amd_sample_texts(first[k] = prompts[k][0]), bit for bit.
+ * Not done: the prompt is not scored (rnn_amd_run_texts does that), every row starts from net's one hidden row, and no
+ * row's state is handed back.
+ * Returns 0; n_texts == 0 or max_len == 0 returns 0 at once (lengths zeroed, rng_out[k] as seeded, no device asked for).
+ * Returns -1 when a row's draw met the attempt cap, as rnn_amd_sample_texts does.  Returns -1 with a message on stderr and
+ * nothing computed, before anything needs a device: all that rnn_amd_sample_texts refuses; a NULL prompts or prompt_lens;
+ * a prompt_lens[k] < 1 or a NULL prompts[k]; a prompt symbol outside [0, input_size) at any position; a
+ * prompt_lens[k] + max_len that does not fit an int. */
+int rnn_amd_continue_texts(RecurNN *net, const u8 *const *prompts, const int *prompt_lens, const u64 *seeds, int n_texts,
+                           int max_len, float bias, int stop_point, int alphabet_len, int head,
+                           u8 *out /* [n_texts][max_len] */, int *out_lens, rand_ctx *rng_out /* [n_texts] or NULL */);
 /* Block until all queued device work of the library has finished. */
 void rnn_amd_synchronize(void);
 

@@ -160,6 +160,15 @@ int rnn_amd_char_cross_entropy_texts(RecurNN *net, RnnCharAlphabet *alphabet, co
  * symbol to turn up is what priming the net (rnn_char_prime) is for.  Returns what rnn_amd_sample_texts returns. */
 int rnn_amd_char_confabulate_texts(RecurNN *net, RnnCharAlphabet *a, const u64 *seeds, int n_texts, int char_len,
                                    float bias, int prev_char, int stop_point, char **dest, int byte_len, int *bytes);
+/* The same with a prompt per passage, in one batched device run (rnn_amd_continue_texts, recur_amd.h): prompts[k]
+ * (prompt_bytes[k] bytes of text) is encoded with rnn_char_alloc_encoded_text -- collapse, case and utf-8 as the alphabet says --, fed to
+ * passage k from the state `net` has, and its continuation of up to char_len symbols is drawn with a generator seeded
+ * init_rand64(seeds[k]) and turned into text in dest[k] under the room rule above.  Only the continuation is written,
+ * not the prompt.  `net` is left as it was.  A prompt that is NULL or encodes to no symbol is refused with its index on
+ * stderr: -1, nothing computed, every text empty and bytes zeroed.  Otherwise returns what rnn_amd_continue_texts returns. */
+int rnn_amd_char_continue_texts(RecurNN *net, RnnCharAlphabet *a, const char *const *prompts, const int *prompt_bytes,
+                                const u64 *seeds, int n_texts, int char_len, float bias, int stop_point, char **dest,
+                                int byte_len, int *bytes);
 
 /* ---- the multi-head text trainer (charmodel.h:132-152, 242-265;
  *      charmodel-multi-predict.c): py-recur-text.c's Net.train / Net.test backend ---- */

@@ -12,6 +12,7 @@ __device__ unsigned long long g_tt_stamps[16];
 #include "k_top.h"
 #include "fwd_plan.h"
 #include "sample_rule.h"
+#include "continue_rule.h"
 BND_DECL(g_bnd_top, ramd_bnd_top_stamps)
 #pragma clang fp contract(off)
 
@@ -767,6 +768,40 @@ struct SampleRand64 {
   DevRng &g;
   __device__ __forceinline__ unsigned long long operator()() { return dev_rand64(g); }
 };
+// The draw half of k_texts_sample and k_texts_continue, stated once: the whole of wave 0 calls it for a row that is not
+// done.  The wave turns the row's slice of the output row into the distribution in sdist (LDS, alen floats); lane 0 draws
+// from it with rng[j], stores the pick as symbol `idx` of the row's text, the count idx + 1 and the generator, and sets
+// done[j] (1: the pick was stop_point, 2: the draw met the attempt cap and nothing was stored).  Returns, in lane 0, the
+// pick if the row runs on, else -1; in the other lanes -1.
+__device__ __forceinline__ int texts_draw_and_store(const View &v, int r, int j, int lane, float *sdist, DevRng *rng,
+                                                    unsigned char *text, int *len, int *done, int alen, int head,
+                                                    int max_len, int idx, int stop_point, float bias) {
+  const float *score = v.b.out + (size_t)r * v.sh.O + (size_t)head * alen;
+  const bool greedy = bias >= SAMPLE_GREEDY_BIAS;
+  if (!greedy) sample_distribution(sdist, score, alen, bias, SampleExp{}, SampleWave{lane});
+  int hot = -1;
+  if (lane == 0) {
+    int pick;
+    if (greedy) {
+      pick = sample_greedy(score, alen);
+    } else {
+      DevRng g = rng[j];
+      SampleRand64 draw = {g};
+      pick = sample_draw(sdist, alen, draw);
+      rng[j] = g;
+    }
+    if (pick == SAMPLE_FAILED) {
+      done[j] = 2;
+    } else {
+      text[(size_t)j * max_len + idx] = (unsigned char)pick;
+      len[j] = idx + 1;
+      if (pick == stop_point) done[j] = 1;
+      else hot = pick;
+    }
+  }
+  return hot;
+}
+
 __global__ __launch_bounds__(256) void k_texts_sample(View v, TextsSample p) {
   extern __shared__ float sdist[]; /* [alen] the row's distribution */
   __shared__ float red[4];
@@ -778,28 +813,8 @@ __global__ __launch_bounds__(256) void k_texts_sample(View v, TextsSample p) {
     if (p.t == 0) {
       hot = p.first[j];
     } else if (p.done[j] == 0) { /* (the same word in every lane: the wave takes one side) */
-      const float *score = v.b.out + (size_t)r * s.O + (size_t)p.head * p.alen;
-      const bool greedy = p.bias >= SAMPLE_GREEDY_BIAS;
-      if (!greedy) sample_distribution(sdist, score, p.alen, p.bias, SampleExp{}, SampleWave{lane});
-      if (lane == 0) {
-        int pick;
-        if (greedy) {
-          pick = sample_greedy(score, p.alen);
-        } else {
-          DevRng g = p.rng[j];
-          SampleRand64 draw = {g};
-          pick = sample_draw(sdist, p.alen, draw);
-          p.rng[j] = g;
-        }
-        if (pick == SAMPLE_FAILED) {
-          p.done[j] = 2;
-        } else {
-          p.text[(size_t)j * p.max_len + (p.t - 1)] = (unsigned char)pick;
-          p.len[j] = p.t;
-          if (pick == p.stop_point) p.done[j] = 1;
-          else hot = pick;
-        }
-      }
+      hot = texts_draw_and_store(v, r, j, lane, sdist, p.rng, p.text, p.len, p.done, p.alen, p.head, p.max_len, p.t - 1,
+                                 p.stop_point, p.bias);
     }
     if (lane == 0) hot_sh = p.t < p.max_len ? hot : -1;
   }
@@ -807,6 +822,52 @@ __global__ __launch_bounds__(256) void k_texts_sample(View v, TextsSample p) {
   const int hot = hot_sh;
   if (hot >= 0) /* (the whole workgroup: assemble_input_row has barriers) */
     assemble_input_row(s, input_row(v, r, 0), p.t == 0 ? p.hid0 : v.b.hidden + (size_t)r * s.H, RAMD_IN_ONE_HOT, hot,
+                       nullptr, red);
+}
+
+// The one launch between two forward passes of rnn_amd_continue_texts (sample_api.c): N prompts continued by one net side
+// by side, a state row each, the rows ordered by prompt length + max_len, longest first (texts_plan.h), so that the rows
+// still running are a prefix.  One workgroup of 256 threads per row, as k_texts_sample; what launch t is for a row --
+// feeding prompt symbol t, drawing text index t - plen, or nothing -- is continue_rule.h's answer for the row's plen:
+//   prompt: the one-hot of the row's prompt symbol on the row's hidden values, at t == 0 on hid0's.  No draw, no generator.
+//   draw (a row that is not done): texts_draw_and_store, k_texts_sample's draw half; the pick is fed unless it was the
+//     text's last index, the stop symbol, or a failure.
+// The symbol reaches the workgroup through LDS behind a barrier.  A row that is done or idle is not fed.  Every word has
+// one writer: no atomics.
+struct TextsContinue {
+  const unsigned char *prompt;   /* the wave's prompts behind one another             */
+  const unsigned long long *off; /* [rows] where row j's prompt starts                */
+  const int *plen;               /* [rows] its length, at least 1                     */
+  DevRng *rng;                   /* [rows] the rows' generators                       */
+  unsigned char *text;           /* [rows][max_len] the symbols drawn                 */
+  int *len;                      /* [rows] how many                                   */
+  int *done;                     /* [rows] 0 running, 1 stopped, 2 failed             */
+  const float *hid0;             /* the hidden row of the first feed                  */
+  int row0;                      /* state row of the wave's row 0 (forward-only)      */
+  int alen, head, max_len, t, stop_point;
+  float bias;
+};
+__global__ __launch_bounds__(256) void k_texts_continue(View v, TextsContinue p) {
+  extern __shared__ float sdist[]; /* [alen] the row's distribution */
+  __shared__ float red[4];
+  __shared__ int hot_sh; /* the symbol to feed, or -1 */
+  const RamdShape &s = v.sh;
+  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const ContinueStep st = continue_step(p.plen[j], p.max_len, p.t); /* (the same in every thread) */
+  if (wave == 0) {
+    int hot = -1;
+    if (st.what == CONTINUE_PROMPT) {
+      hot = p.prompt[p.off[j] + st.index];
+    } else if (st.what == CONTINUE_DRAW && p.done[j] == 0) { /* (the same word in every lane: the wave takes one side) */
+      hot = texts_draw_and_store(v, r, j, lane, sdist, p.rng, p.text, p.len, p.done, p.alen, p.head, p.max_len, st.index,
+                                 p.stop_point, p.bias);
+    }
+    if (lane == 0) hot_sh = st.feeds ? hot : -1;
+  }
+  __syncthreads();
+  const int hot = hot_sh;
+  if (hot >= 0) /* (the whole workgroup: assemble_input_row has barriers) */
+    assemble_input_row(s, input_row(v, r, 0), st.on_hid0 ? p.hid0 : v.b.hidden + (size_t)r * s.H, RAMD_IN_ONE_HOT, hot,
                        nullptr, red);
 }
 
@@ -954,6 +1015,32 @@ extern "C" void ramd_launch_texts_sample(ramd_stream_t st_, const RamdShape *sh,
   if (shm > 64 * 1024) raise_lds_limit<k_texts_sample>(160 * 1024 - 64);
   TextsSample p = {first, (DevRng *)rng, text, len, done, hid0, row0, alphabet_len, head, max_len, t, stop_point, bias};
   RAMD_LAUNCH(k_texts_sample, dim3(rows), dim3(256), shm, st, v, p);
+}
+
+extern "C" void ramd_launch_texts_continue(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
+                                           const unsigned char *prompt, const unsigned long long *off, const int *plen,
+                                           void *rng, unsigned char *text, int *len, int *done, const float *hid0,
+                                           int alphabet_len, int head, int max_len, int t, int stop_point, float bias) {
+  if (rows < 1) return;
+  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
+    fprintf(stderr, "librecur_amd: ramd_launch_texts_continue: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
+    abort();
+  }
+  if (alphabet_len < 1 || head < 0 || (size_t)(head + 1) * alphabet_len > (size_t)sh->O || t < 0 || max_len < 1) {
+    fprintf(stderr, "librecur_amd: ramd_launch_texts_continue: head %d of %d outputs in a row of %d, step %d, texts of %d\n",
+            head, alphabet_len, sh->O, t, max_len);
+    abort();
+  }
+  hipStream_t st = (hipStream_t)st_;
+  View v = make_view(sh, b);
+  const size_t shm = (size_t)((alphabet_len + 3) & ~3) * sizeof(float);
+  if (shm > 160 * 1024 - 64) {
+    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", alphabet_len);
+    abort();
+  }
+  if (shm > 64 * 1024) raise_lds_limit<k_texts_continue>(160 * 1024 - 64);
+  TextsContinue p = {prompt, off, plen, (DevRng *)rng, text, len, done, hid0, row0, alphabet_len, head, max_len, t, stop_point, bias};
+  RAMD_LAUNCH(k_texts_continue, dim3(rows), dim3(256), shm, st, v, p);
 }
 
 extern "C" void ramd_launch_sigmoid_mse_error(ramd_stream_t st_, const RamdShape *sh,

@@ -259,6 +259,16 @@ void ramd_launch_texts_step(ramd_stream_t st, const RamdShape *sh, const RamdBuf
 void ramd_launch_texts_sample(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
                               const int *first, void *rng, unsigned char *text, int *len, int *done, const float *hid0,
                               int alphabet_len, int head, int max_len, int t, int stop_point, float bias);
+/* the launch between two forward passes of rnn_amd_continue_texts, launch t = 0 .. of a wave of `rows` prompts on
+ * forward-only state rows row0 ... (texts_plan.h's order for prompt length + max_len): what it does for a row is
+ * continue_rule.h's continue_step(plen[row], max_len, t) -- the input row of the next pass from prompt symbol t (the
+ * row's prompt starts at prompt[off[row]]; on hid0's hidden values at t == 0, else on the row's own), or the draw of text
+ * index t - plen[row] exactly as ramd_launch_texts_sample makes it (text, len, done, rng as there) and the input row from
+ * the pick, or nothing.  All pointers are device pointers. */
+void ramd_launch_texts_continue(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
+                                const unsigned char *prompt, const unsigned long long *off, const int *plen, void *rng,
+                                unsigned char *text, int *len, int *done, const float *hid0, int alphabet_len, int head,
+                                int max_len, int t, int stop_point, float bias);
 /* rnnca's loss (gstrnnca.c:701-714): sigmoid in place on the first n outputs, slope * (target -
  * a) into o_error; targets is a device array [nrows][ld] */
 void ramd_launch_sigmoid_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,

@@ -5,7 +5,7 @@ tests also point it at the compiled reference) exactly the way the reference's o
 charmodel-predict.c:288-311).  ``AmdBatchedSet`` drives the additive batched entry points (include/recur_amd.h
 part 2): the whole set per call, text on the device.  ``run_texts`` scores a list of encoded texts against one net in
 one batched call (rnn_amd_run_texts / _heads), ``sample_texts`` draws a batch of texts from one net in one batched call
-(rnn_amd_sample_texts).  ``synthetic_text_np`` is the seeded symbol stream of
+(rnn_amd_sample_texts), ``continue_texts`` continues a batch of prompts (rnn_amd_continue_texts).  ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
 """
@@ -90,6 +90,27 @@ def sample_texts(lib, net, first, seeds, max_len, bias=0.0, stop=-1, alphabet_le
                                  alphabet_len, head, rc.u8ptr(out), rc.iptr(lens), rng.ctypes.data_as(C.POINTER(rc.RandCtx)))
     if r != 0:
         raise ValueError("rnn_amd_sample_texts refused the batch or a draw failed (see stderr)")
+    assert all(np.all(out[k, lens[k]:max_len] == 0xEE) for k in range(n)), "symbols behind a text's length"
+    return [out[k, :lens[k]].copy() for k in range(n)], rng[:n]
+
+
+def continue_texts(lib, net, prompts, seeds, max_len, bias=0.0, stop=-1, alphabet_len=0, head=0):
+    """rnn_amd_continue_texts: the prompts (a list of numpy uint8 arrays) continued by up to max_len symbols each from one
+    net in one batched call, continuation k drawn with a generator seeded seeds[k].  Returns what sample_texts returns:
+    (the list of uint8 arrays -- the continuations, without their prompts --, the generators afterwards as a uint64
+    array [len(prompts)][4])."""
+    keep, ptrs, plens = text_pointers(prompts)
+    sd = np.ascontiguousarray(seeds, dtype=np.uint64)
+    n = len(keep)
+    assert len(sd) == n
+    out = np.full((max(n, 1), max(max_len, 1)), 0xEE, np.uint8)
+    lens = np.full(max(n, 1), -1, np.int32)
+    rng = np.zeros((max(n, 1), 4), np.uint64)
+    r = lib.rnn_amd_continue_texts(net, ptrs, rc.iptr(plens), sd.ctypes.data_as(C.POINTER(C.c_uint64)), n, max_len, bias,
+                                   stop, alphabet_len, head, rc.u8ptr(out), rc.iptr(lens),
+                                   rng.ctypes.data_as(C.POINTER(rc.RandCtx)))
+    if r != 0:
+        raise ValueError("rnn_amd_continue_texts refused the batch or a draw failed (see stderr)")
     assert all(np.all(out[k, lens[k]:max_len] == 0xEE) for k in range(n)), "symbols behind a text's length"
     return [out[k, :lens[k]].copy() for k in range(n)], rng[:n]
 

@@ -3,11 +3,15 @@
  * sample characters from its predictions.
  *
  *   text_confabulate_amd -f NET [-B bias] [-n chars] [-p prefix] [-u until_char]
- *                        [-w wait_for_char] [-r seed] [-N passages]
+ *                        [-w wait_for_char] [-r seed] [-N passages] [-P prompts_file]
  *
  * -N n: n passages, one per line, each from the (primed) net's state with a generator of its own seeded seed, seed + 1,
  * ..., all drawn in one batched device run (rnn_amd_char_confabulate_texts).  Without -N the one passage is drawn with the
  * net's own generator, as ever.  -w has no batched form (priming is what brings a net to a starting point).
+ * -P FILE: every non-empty line of FILE is a prompt, continued n times (-N n, default 1) from the (primed) net's state:
+ * lines x n rows in one batched device run (rnn_amd_char_continue_texts), row i -- the lines in order, a line's n
+ * continuations next to one another -- with a generator seeded seed + i.  One output line per row: the prompt, then its
+ * continuation.  -P does not go with -w either.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,12 +34,68 @@ static void seed_rng(rand_ctx *x, u64 seed) {
   }
 }
 
+/* -P: the non-empty lines of `file` n times over, continued in one call; one line per row on stdout */
+static int continue_prompts(RecurNN *net, RnnCharAlphabet *alphabet, const char *file, int n, long long seed, int chars,
+                            float bias, int stop_point, int byte_len) {
+  FILE *f = fopen(file, "r");
+  if (!f) {
+    fprintf(stderr, "cannot read the prompts in %s\n", file);
+    return 1;
+  }
+  char **prompts = NULL, *line = NULL;
+  size_t cap = 0, n_lines = 0;
+  ssize_t got;
+  while ((got = getline(&line, &cap, f)) >= 0) {
+    while (got > 0 && (line[got - 1] == '\n' || line[got - 1] == '\r')) {
+      line[--got] = 0;
+    }
+    if (got > 0) {
+      prompts = realloc(prompts, sizeof(char *) * (n_lines + 1));
+      prompts[n_lines++] = strdup(line);
+    }
+  }
+  free(line);
+  fclose(f);
+  const int rows = (int)n_lines * n;
+  const char **of_row = malloc(sizeof(char *) * (rows + 1));
+  int *prompt_bytes = malloc(sizeof(int) * (rows + 1));
+  u64 *seeds = malloc(sizeof(u64) * (rows + 1));
+  char **lines = malloc(sizeof(char *) * (rows + 1));
+  int *bytes = malloc(sizeof(int) * (rows + 1));
+  for (int i = 0; i < rows; i++) {
+    of_row[i] = prompts[i / n];
+    prompt_bytes[i] = (int)strlen(of_row[i]);
+    seeds[i] = (u64)seed + (u64)i;
+    lines[i] = malloc(byte_len);
+  }
+  int r = rnn_amd_char_continue_texts(net, alphabet, of_row, prompt_bytes, seeds, rows, chars, bias, stop_point, lines,
+                                      byte_len, bytes);
+  for (int i = 0; i < rows; i++) {
+    if (r == 0) {
+      fputs(of_row[i], stdout);
+      fputs(lines[i], stdout);
+      fputs("\n", stdout);
+    }
+    free(lines[i]);
+  }
+  for (size_t l = 0; l < n_lines; l++) {
+    free(prompts[l]);
+  }
+  free(prompts);
+  free(of_row);
+  free(prompt_bytes);
+  free(seeds);
+  free(lines);
+  free(bytes);
+  return r ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
-  const char *netfile = NULL, *prefix = NULL, *until = NULL, *wait_for = NULL;
+  const char *netfile = NULL, *prefix = NULL, *until = NULL, *wait_for = NULL, *prompts_file = NULL;
   float bias = 0;
   int chars = 72, opt, passages = -1;
   long long seed = 2;
-  while ((opt = getopt(argc, argv, "f:B:n:p:u:w:r:N:")) != -1) {
+  while ((opt = getopt(argc, argv, "f:B:n:p:u:w:r:N:P:")) != -1) {
     switch (opt) {
     case 'f': netfile = optarg; break;
     case 'B': bias = atof(optarg); break;
@@ -45,12 +105,13 @@ int main(int argc, char **argv) {
     case 'w': wait_for = optarg; break;
     case 'r': seed = atoll(optarg); break;
     case 'N': passages = atoi(optarg); break;
+    case 'P': prompts_file = optarg; break;
     default: fprintf(stderr, "usage: %s -f NET [-B bias] [-n chars] [-p prefix]\n", argv[0]); return 2;
     }
   }
-  if (passages >= 0 && wait_for) {
-    fprintf(stderr, "usage: %s -f NET -N passages [-B bias] [-n chars] [-p prefix] [-u until_char] [-r seed]: -w does not go "
-                    "with -N\n", argv[0]);
+  if ((passages >= 0 || prompts_file) && wait_for) {
+    fprintf(stderr, "usage: %s -f NET [-N passages] [-P prompts_file] [-B bias] [-n chars] [-p prefix] [-u until_char] "
+                    "[-r seed]: -w does not go with -N or -P\n", argv[0]);
     return 2;
   }
   RecurNN *net = netfile ? rnn_load_net(netfile) : NULL;
@@ -73,6 +134,13 @@ int main(int argc, char **argv) {
   char *t = malloc(byte_len);
   int stop_point = until ? rnn_char_get_codepoint(alphabet, until) : -1;
   int start_point = wait_for ? rnn_char_get_codepoint(alphabet, wait_for) : -1;
+  if (prompts_file) {
+    int r = continue_prompts(net, alphabet, prompts_file, passages >= 0 ? passages : 1, seed, chars, bias, stop_point, byte_len);
+    free(t);
+    rnn_char_free_alphabet(alphabet);
+    rnn_delete_net(net);
+    return r;
+  }
   if (passages >= 0) {
     u64 *seeds = malloc(sizeof(u64) * (passages + 1));
     char **lines = malloc(sizeof(char *) * (passages + 1));
