@@ -633,6 +633,31 @@ int rnn_amd_run_texts(RecurNN *net, const u8 *const *texts, const int *lens, con
  * charmodel-multi-predict.c:388-403): sums[k * n_heads + c] is head c's sum for text k. */
 int rnn_amd_run_texts_heads(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
                             int alphabet_len, double *sums); /* [n_texts][output_size / alphabet_len] */
+/* Many texts TRACED symbol by symbol in one batched device run: rnn_amd_run_texts(_heads) with every float it adds handed
+ * back instead of their sum.  With n_heads = alphabet_len ? output_size / alphabet_len : 1 and alen = alphabet_len ?
+ * alphabet_len : output_size, for every text k with lens[k] >= 2, every t in [0, lens[k] - 1) and every head c:
+ *     logp[k][t * n_heads + c]   the float rnn_amd_run_texts(_heads) adds into its double at step t: capped_log2f
+ *         (charmodel-helpers.h:11-13) of softmax(head c)[texts[k][t + 1]] after texts[k][0 .. t] were fed as one-hot
+ *         opinions; -100 for a symbol outside the head.  Added one after another in a double from skips[k] on they are
+ *         that call's sum, bit for bit.
+ *     guess[k][t * n_heads + c]  what softmax_best_guess (badmaths.h:113-141) returns for that head at that step: the
+ *         index of the largest likelihood after the division, the lowest index among equal ones.
+ * guess may be NULL (no guesses are taken); guess[k] and logp[k] of a text shorter than 2 symbols may be NULL, and nothing
+ * is written for such a text, nor behind the (lens[k] - 1) * n_heads entries of any other.  There is no skips: every step
+ * is traced and the caller ignores what it wants.
+ * Everything else is rnn_amd_run_texts's contract: each text runs on a forward-only clone that starts from net's hidden
+ * row at the moment of the call, the texts do not see one another, there is no noise and no generator is touched, `net`
+ * -- host and device copies -- is left exactly as it was; the rows go longest first, in waves of up to 256, with one
+ * device synchronisation per wave.
+ * Memory: a wave's trace stays on the device until the wave's one synchronisation and comes back in one copy -- 5 bytes
+ * per traced value (4 without guesses) on the device and as many in a host staging buffer, for the first wave (the 256
+ * longest texts) the sum of (lens[k] - 1) * n_heads of them.
+ * Returns 0; n_texts == 0, or no text of two symbols, returns 0 at once and asks for no device.  Returns -1 with a message
+ * on stderr and nothing computed, before anything needs a device: all that rnn_amd_run_texts_heads refuses, with
+ * alphabet_len == 0 allowed here; a NULL logp with n_texts > 0; a NULL logp[k], or with guess a NULL guess[k], for a text
+ * of 2 or more symbols; guess with alen > 256, whose indices do not fit a byte. */
+int rnn_amd_trace_texts(RecurNN *net, const u8 *const *texts, const int *lens, int n_texts, int alphabet_len,
+                        float *const *logp, u8 *const *guess);
 /* Many texts DRAWN from one net in one batched device run: the generative counterpart of rnn_amd_run_texts.  Row k of
  * `out` is what this loop writes on a forward-only clone c_k of `net` whose hidden row starts as a copy of net's hidden
  * row at the moment of the call and whose generator is init_rand64(seeds[k]) (recur-rng.h:33-43):

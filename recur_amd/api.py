@@ -251,6 +251,8 @@ AMD_API = {
     "rnn_amd_run_texts": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, c_int_p, C.c_int, C.POINTER(C.c_double)]),
     "rnn_amd_run_texts_heads": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, c_int_p, C.c_int, C.c_int,
                                           C.POINTER(C.c_double)]),
+    "rnn_amd_trace_texts": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, C.c_int, C.c_int, C.POINTER(c_float_p),
+                                      C.POINTER(c_u8_p)]),
     "rnn_amd_sample_texts": (C.c_int, [NetP, c_int_p, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                        C.c_int, c_u8_p, c_int_p, C.POINTER(RandCtx)]),
     "rnn_amd_continue_texts": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_float,

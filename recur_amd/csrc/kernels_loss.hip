@@ -705,6 +705,25 @@ struct TextsStep {
   int t_score, a_score, t_feed, a_feed;
 };
 constexpr int TS_WAVES = 4;
+// The score half of k_texts_step and k_texts_trace, stated once: one wave scores one head of alen outputs at src.  The wave
+// builds the shift and the exponentials into ex (LDS, alen floats); behind the fence lane 0 takes their sum in the
+// reference's order, the likelihood of `target` (a symbol outside the head has no probability: the cap) and returns
+// capped log2 of it; the other lanes return 0.  `sum` != nullptr: every lane takes the sum -- the same LDS reads,
+// broadcast -- and leaves it there for the caller's divisions.  The caller fences before the wave's next head rewrites ex.
+__device__ __forceinline__ float texts_score_head(const float *src, float *ex, int alen, int lane, int target, float *sum) {
+  const float adj = softmax_shift_of(src, alen, lane);
+  for (int i = lane; i < alen; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
+  FenceOneWave{}();
+  if (sum) {
+    *sum = ordered_sum(ex, alen);
+    return lane == 0 ? capped_log2f_dev(target < alen ? ex[target] / *sum : 0.0f) : 0.0f;
+  }
+  if (lane == 0) {
+    const float e = target < alen ? ex[target] / ordered_sum(ex, alen) : 0.0f;
+    return capped_log2f_dev(e);
+  }
+  return 0.0f;
+}
 __global__ __launch_bounds__(64 * TS_WAVES) void k_texts_step(View v, TextsStep p) {
   extern __shared__ float tex[]; /* [TS_WAVES][alen rounded up to 4] exponentials */
   __shared__ float red[4];
@@ -715,15 +734,61 @@ __global__ __launch_bounds__(64 * TS_WAVES) void k_texts_step(View v, TextsStep 
     const int target = text[p.t_score + 1];
     float *ex = tex + wave * ((p.alen + 3) & ~3);
     for (int c = wave; c < p.n_sums; c += TS_WAVES) {
-      const float *src = v.b.out + (size_t)r * s.O + (size_t)c * p.alen;
-      const float adj = softmax_shift_of(src, p.alen, lane);
-      for (int i = lane; i < p.alen; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
-      FenceOneWave{}();
-      if (lane == 0) { /* (a symbol outside the head has no probability: the cap) */
-        const float e = target < p.alen ? ex[target] / ordered_sum(ex, p.alen) : 0.0f;
-        p.acc[(size_t)j * p.n_sums + c] += (double)capped_log2f_dev(e);
-      }
+      const float l = texts_score_head(v.b.out + (size_t)r * s.O + (size_t)c * p.alen, ex, p.alen, lane, target, nullptr);
+      if (lane == 0) p.acc[(size_t)j * p.n_sums + c] += (double)l;
       FenceOneWave{}(); /* before this wave's next head rewrites ex */
+    }
+  }
+  if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
+    assemble_input_row(s, input_row(v, r, 0), p.hid0 ? p.hid0 : v.b.hidden + (size_t)r * s.H, RAMD_IN_ONE_HOT,
+                       text[p.t_feed], nullptr, red);
+}
+
+// The one launch between two forward passes of rnn_amd_trace_texts (texts_api.c): k_texts_step with the floats it adds
+// handed back one by one.  The feed half is k_texts_step's.  The score half scores every row at every step (there is no
+// skip) and, instead of adding into a double, lane 0 of the head's wave stores the float at trace[off_tr[j] + t_score *
+// n_sums + c]; with `guess` the wave also takes softmax_best_guess's pick (badmaths.h:113-141: the largest likelihood after
+// the division, the lowest index among equals) -- every lane offers ex[i] / sum for its outputs in ascending order, lanes
+// beyond alen offer nothing -- and lane 0 stores it as a byte at the same index.  Row j is scored at every t < len_j - 1,
+// so every traced entry is written exactly once, by one writer: no atomics and no memset of the trace.
+struct TextsTrace {
+  const unsigned char *text;        /* the wave's texts behind one another            */
+  const unsigned long long *off;    /* [rows] where row j's text starts               */
+  const unsigned long long *off_tr; /* [rows] where row j's trace starts, in entries  */
+  float *trace;                     /* the wave's log2 likelihoods                    */
+  unsigned char *guess;             /* the wave's best guesses, or nullptr            */
+  const float *hid0;                /* the hidden row of the first feed, or nullptr   */
+  int row0;                         /* state row of the wave's row 0 (forward-only)   */
+  int alen, n_sums;
+  int t_score, a_score, t_feed, a_feed;
+};
+__global__ __launch_bounds__(64 * TS_WAVES) void k_texts_trace(View v, TextsTrace p) {
+  extern __shared__ float tex[]; /* [TS_WAVES][alen rounded up to 4] exponentials */
+  __shared__ float red[4];
+  const RamdShape &s = v.sh;
+  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const unsigned char *text = p.text + p.off[j];
+  if (j < p.a_score) {
+    const int target = text[p.t_score + 1];
+    float *ex = tex + wave * ((p.alen + 3) & ~3);
+    const size_t at = p.off_tr[j] + (size_t)p.t_score * p.n_sums;
+    for (int c = wave; c < p.n_sums; c += TS_WAVES) {
+      const float *src = v.b.out + (size_t)r * s.O + (size_t)c * p.alen;
+      if (p.guess) {
+        float sum;
+        const float l = texts_score_head(src, ex, p.alen, lane, target, &sum);
+        BestGuess best;
+        for (int i = lane; i < p.alen; i += 64) best.offer(ex[i] / sum, i);
+        wave_best_guess(best);
+        if (lane == 0) {
+          p.trace[at + c] = l;
+          p.guess[at + c] = (unsigned char)best.i;
+        }
+      } else {
+        const float l = texts_score_head(src, ex, p.alen, lane, target, nullptr);
+        if (lane == 0) p.trace[at + c] = l;
+      }
+      FenceOneWave{}(); /* before this wave's next head rewrites ex (the guess's reads of it have returned) */
     }
   }
   if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
@@ -989,6 +1054,34 @@ extern "C" void ramd_launch_texts_step(ramd_stream_t st_, const RamdShape *sh, c
   if (shm > 64 * 1024) raise_lds_limit<k_texts_step>(160 * 1024 - 64);
   TextsStep p = {text, off, skip, acc, hid0, row0, alphabet_len, n_sums, t_score, a_score, t_feed, a_feed};
   RAMD_LAUNCH(k_texts_step, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
+}
+
+extern "C" void ramd_launch_texts_trace(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
+                                        const unsigned char *text, const unsigned long long *off,
+                                        const unsigned long long *off_tr, float *trace, unsigned char *guess,
+                                        const float *hid0, int alphabet_len, int n_sums, int t_score, int a_score,
+                                        int t_feed, int a_feed) {
+  const int rows = a_score > a_feed ? a_score : a_feed;
+  if (rows < 1) return;
+  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
+    fprintf(stderr, "librecur_amd: ramd_launch_texts_trace: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
+    abort();
+  }
+  if (alphabet_len < 1 || n_sums < 1 || (size_t)n_sums * alphabet_len > (size_t)sh->O || (a_score > 0 && t_score < 0)) {
+    fprintf(stderr, "librecur_amd: ramd_launch_texts_trace: %d heads of %d outputs in a row of %d, step %d\n", n_sums,
+            alphabet_len, sh->O, t_score);
+    abort();
+  }
+  hipStream_t st = (hipStream_t)st_;
+  View v = make_view(sh, b);
+  const size_t shm = (size_t)TS_WAVES * ((alphabet_len + 3) & ~3) * sizeof(float);
+  if (shm > 160 * 1024 - 64) {
+    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", alphabet_len);
+    abort();
+  }
+  if (shm > 64 * 1024) raise_lds_limit<k_texts_trace>(160 * 1024 - 64);
+  TextsTrace p = {text, off, off_tr, trace, guess, hid0, row0, alphabet_len, n_sums, t_score, a_score, t_feed, a_feed};
+  RAMD_LAUNCH(k_texts_trace, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
 }
 
 extern "C" void ramd_launch_texts_sample(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,

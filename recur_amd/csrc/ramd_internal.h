@@ -250,6 +250,15 @@ void ramd_launch_texts_step(ramd_stream_t st, const RamdShape *sh, const RamdBuf
                             const unsigned char *text, const unsigned long long *off, const int *skip, double *acc,
                             const float *hid0, int alphabet_len, int n_sums, int t_score, int a_score, int t_feed,
                             int a_feed);
+/* the launch between two forward passes of rnn_amd_trace_texts: ramd_launch_texts_step without skip and without sums --
+ * the float it would add for row `row`, step t_score, head c is stored at trace[off_tr[row] + t_score * n_sums + c], and
+ * with guess != NULL the head's best guess (softmax_best_guess: the largest likelihood, the lowest index among equals) as
+ * a byte at the same index of guess.  Every entry has one writer and is written once; nothing else of either array is
+ * touched. */
+void ramd_launch_texts_trace(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
+                             const unsigned char *text, const unsigned long long *off, const unsigned long long *off_tr,
+                             float *trace, unsigned char *guess, const float *hid0, int alphabet_len, int n_sums,
+                             int t_score, int a_score, int t_feed, int a_feed);
 /* the launch between two forward passes of rnn_amd_sample_texts, launch t = 0 .. max_len of a wave of `rows` texts on
  * forward-only state rows row0 ...: for t > 0 draws symbol t - 1 of every row that is not done from head `head` of
  * alphabet_len outputs of its output row (sample_rule.h: the biased clamped softmax, a draw with rng[row], or the best

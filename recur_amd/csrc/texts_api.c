@@ -1,5 +1,6 @@
 /* texts_api.c -- many texts against one net in one batched device run (gnu11 C): rnn_amd_run_texts and
- * rnn_amd_run_texts_heads, the set form of rnn_amd_run_text / _heads (net_api.c).  Where those feed one net a symbol per
+ * rnn_amd_run_texts_heads, the set form of rnn_amd_run_text / _heads (net_api.c), and rnn_amd_trace_texts, which hands
+ * back per symbol what those add up (k_texts_trace in k_texts_step's place).  Where those feed one net a symbol per
  * launch sequence, these give every text a forward-only state row of the engine's own and run the rows together: which
  * text gets which row, in how many waves and with how many rows at each step is texts_plan.h's business; between two
  * forward passes of the rows there is one launch (k_texts_step, kernels_loss.hip) that scores the step just computed and
@@ -45,20 +46,33 @@ int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const 
   return 0;
 }
 
+/* what a call wants back: the sums form (sums != NULL: one double per text and head), or the trace form (every float the
+ * sums form would add, in logp, and -- unless NULL -- the best guess next to each) */
+typedef struct TextsWanted {
+  double *sums;
+  float *const *logp;
+  u8 *const *guess;
+} TextsWanted;
+
 /* one wave of the plan on the state rows from r0 on; the d_* arrays have room for the plan's first (largest) wave, the
- * h_* ones are the pinned-or-not host sides of them and stay untouched until the wave's synchronisation */
+ * h_* ones are the pinned-or-not host sides of them and stay untouched until the wave's synchronisation.  The sums form
+ * uses skip and acc; the trace form off_tr and trace: a wave's floats, then -- with guesses -- its bytes, in ONE buffer
+ * so that one copy brings both back, row j's entries from off_tr[j] on in either */
 typedef struct TextsBuffers {
   u8 *h_text, *d_text;
   unsigned long long *h_off, *d_off;
   int *d_skip;
   double *h_acc, *d_acc;
+  unsigned long long *h_off_tr, *d_off_tr;
+  u8 *h_trace, *d_trace;
 } TextsBuffers;
 
 static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, int w, const u8 *const *texts, int r0,
-                     int alphabet_len, int n_sums, const TextsBuffers *tb, double *sums) {
+                     int alphabet_len, int n_sums, const TextsBuffers *tb, const TextsWanted *want) {
   const RamdShape *s = &e->sh;
   const TextsWave *wave = &plan->waves[w];
   const int n = wave->nrows;
+  const int alen = alphabet_len ? alphabet_len : s->output_size;
   size_t at = 0;
   for (int j = 0; j < n; j++) {
     const int len = plan->len[wave->row0 + j];
@@ -68,36 +82,79 @@ static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, i
   }
   ramd_h2d(tb->d_text, tb->h_text, at);
   ramd_h2d(tb->d_off, tb->h_off, (size_t)n * sizeof(unsigned long long));
-  ramd_h2d(tb->d_skip, plan->skip + wave->row0, (size_t)n * sizeof(int));
-  HIP_OK(hipMemsetAsync(tb->d_acc, 0, (size_t)n * n_sums * sizeof(double), ramd_stream));
+  size_t traced = 0; /* the wave's traced values */
+  u8 *d_guess = NULL;
+  if (want->sums) {
+    ramd_h2d(tb->d_skip, plan->skip + wave->row0, (size_t)n * sizeof(int));
+    HIP_OK(hipMemsetAsync(tb->d_acc, 0, (size_t)n * n_sums * sizeof(double), ramd_stream));
+  } else {
+    traced = texts_plan_trace_offsets(plan, w, n_sums, tb->h_off_tr);
+    ramd_h2d(tb->d_off_tr, tb->h_off_tr, (size_t)n * sizeof(unsigned long long));
+    d_guess = want->guess ? tb->d_trace + traced * sizeof(float) : NULL;
+  }
   /* every row starts from the net's hidden row: the first launch builds the input rows from it */
   const float *hid0 = e->b.hidden + (size_t)ramd_state_row(e, ramd_priv(net)) * s->H;
   int scored = 0; /* a(t - 1): the rows whose step t - 1 waits to be scored */
   for (int t = 0; t <= wave->steps; t++) {
     const int a = t < wave->steps ? texts_plan_active(plan, w, t) : 0;
-    ramd_launch_texts_step(ramd_stream, s, &e->b, r0, tb->d_text, tb->d_off, tb->d_skip, tb->d_acc, t == 0 ? hid0 : NULL,
-                           alphabet_len ? alphabet_len : s->output_size, n_sums, t - 1, scored, t, a);
+    if (want->sums) {
+      ramd_launch_texts_step(ramd_stream, s, &e->b, r0, tb->d_text, tb->d_off, tb->d_skip, tb->d_acc, t == 0 ? hid0 : NULL,
+                             alen, n_sums, t - 1, scored, t, a);
+    } else {
+      ramd_launch_texts_trace(ramd_stream, s, &e->b, r0, tb->d_text, tb->d_off, tb->d_off_tr, (float *)tb->d_trace, d_guess,
+                              t == 0 ? hid0 : NULL, alen, n_sums, t - 1, scored, t, a);
+    }
     if (a) {
       const RamdFwdCall call = {.row0 = r0, .nrows = a, .rows_built = 1};
       ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
     }
     scored = a;
   }
-  ramd_d2h(tb->h_acc, tb->d_acc, (size_t)n * n_sums * sizeof(double));
+  if (want->sums) {
+    ramd_d2h(tb->h_acc, tb->d_acc, (size_t)n * n_sums * sizeof(double));
+  } else {
+    ramd_d2h(tb->h_trace, tb->d_trace, traced * (sizeof(float) + (want->guess ? 1 : 0)));
+  }
   ramd_dsync(); /* the wave's one synchronisation */
   for (int j = 0; j < n; j++) {
-    memcpy(sums + (size_t)plan->order[wave->row0 + j] * n_sums, tb->h_acc + (size_t)j * n_sums, (size_t)n_sums * sizeof(double));
+    const int k = plan->order[wave->row0 + j];
+    if (want->sums) {
+      memcpy(want->sums + (size_t)k * n_sums, tb->h_acc + (size_t)j * n_sums, (size_t)n_sums * sizeof(double));
+      continue;
+    }
+    const size_t count = (size_t)(plan->len[wave->row0 + j] - 1) * n_sums;
+    memcpy(want->logp[k], tb->h_trace + tb->h_off_tr[j] * sizeof(float), count * sizeof(float));
+    if (want->guess) {
+      memcpy(want->guess[k], tb->h_trace + traced * sizeof(float) + tb->h_off_tr[j], count);
+    }
   }
 }
 
 static int run_texts(const char *who, RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
-                     int alphabet_len, double *sums) {
-  if (ramd_run_texts_refused(who, net, texts, lens, n_texts, alphabet_len, sums)) {
+                     int alphabet_len, const TextsWanted *want) {
+  double *sums = want->sums;
+  float *const *logp = want->logp;
+  u8 *const *guess = want->guess;
+  if (ramd_run_texts_refused(who, net, texts, lens, n_texts, alphabet_len, sums ? (const void *)sums : (const void *)logp)) {
     return -1;
   }
   const int n_sums = alphabet_len ? net->output_size / alphabet_len : 1;
-  for (size_t q = 0; q < (size_t)n_texts * n_sums; q++) {
-    sums[q] = 0.0;
+  if (sums) {
+    for (size_t q = 0; q < (size_t)n_texts * n_sums; q++) {
+      sums[q] = 0.0;
+    }
+  } else {
+    if (guess && (alphabet_len ? alphabet_len : net->output_size) > 256) {
+      fprintf(stderr, "librecur_amd: %s: a guess among %d outputs does not fit a byte\n", who,
+              alphabet_len ? alphabet_len : net->output_size);
+      return -1;
+    }
+    for (int k = 0; k < n_texts; k++) {
+      if (lens[k] >= 2 && (!logp[k] || (guess && !guess[k]))) {
+        fprintf(stderr, "librecur_amd: %s: text %d has no array to be traced into\n", who, k);
+        return -1;
+      }
+    }
   }
   TextsPlan plan;
   if (texts_plan_make(&plan, lens, skips, n_texts, TEXTS_PLAN_WIDTH)) {
@@ -121,31 +178,44 @@ static int run_texts(const char *who, RecurNN *net, const u8 *const *texts, cons
   for (int j = 0; j < widest; j++) {
     bytes += (size_t)plan.len[j];
   }
-  TextsBuffers tb;
+  TextsBuffers tb = {0};
   tb.h_text = ramd_zalloc(bytes);
   tb.h_off = ramd_zalloc((size_t)widest * sizeof(unsigned long long));
-  tb.h_acc = ramd_zalloc((size_t)widest * n_sums * sizeof(double));
   tb.d_text = ramd_dev_alloc(bytes);
   tb.d_off = ramd_dev_alloc((size_t)widest * sizeof(unsigned long long));
-  tb.d_skip = ramd_dev_alloc((size_t)widest * sizeof(int));
-  tb.d_acc = ramd_dev_alloc((size_t)widest * n_sums * sizeof(double));
+  if (sums) {
+    tb.h_acc = ramd_zalloc((size_t)widest * n_sums * sizeof(double));
+    tb.d_skip = ramd_dev_alloc((size_t)widest * sizeof(int));
+    tb.d_acc = ramd_dev_alloc((size_t)widest * n_sums * sizeof(double));
+  } else { /* the first wave has the most rows and the longest texts: the largest trace */
+    tb.h_off_tr = ramd_zalloc((size_t)widest * sizeof(unsigned long long));
+    const size_t room = texts_plan_trace_offsets(&plan, 0, n_sums, tb.h_off_tr) * (sizeof(float) + (guess ? 1 : 0));
+    tb.h_trace = ramd_zalloc(room);
+    tb.d_off_tr = ramd_dev_alloc((size_t)widest * sizeof(unsigned long long));
+    tb.d_trace = ramd_dev_alloc(room);
+  }
   for (int w = 0; w < plan.n_waves; w++) {
-    run_wave(e, net, &plan, w, texts, r0, alphabet_len, n_sums, &tb, sums);
+    run_wave(e, net, &plan, w, texts, r0, alphabet_len, n_sums, &tb, want);
   }
   ramd_dev_free(tb.d_text);
   ramd_dev_free(tb.d_off);
   ramd_dev_free(tb.d_skip);
   ramd_dev_free(tb.d_acc);
+  ramd_dev_free(tb.d_off_tr);
+  ramd_dev_free(tb.d_trace);
   free(tb.h_text);
   free(tb.h_off);
   free(tb.h_acc);
+  free(tb.h_off_tr);
+  free(tb.h_trace);
   texts_plan_free(&plan);
   return 0;
 }
 
 int rnn_amd_run_texts(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
                       double *sums) {
-  return run_texts("rnn_amd_run_texts", net, texts, lens, skips, n_texts, 0, sums);
+  const TextsWanted want = {.sums = sums};
+  return run_texts("rnn_amd_run_texts", net, texts, lens, skips, n_texts, 0, &want);
 }
 
 int rnn_amd_run_texts_heads(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
@@ -154,5 +224,12 @@ int rnn_amd_run_texts_heads(RecurNN *net, const u8 *const *texts, const int *len
     fprintf(stderr, "librecur_amd: rnn_amd_run_texts_heads: heads of %d outputs\n", alphabet_len);
     return -1;
   }
-  return run_texts("rnn_amd_run_texts_heads", net, texts, lens, skips, n_texts, alphabet_len, sums);
+  const TextsWanted want = {.sums = sums};
+  return run_texts("rnn_amd_run_texts_heads", net, texts, lens, skips, n_texts, alphabet_len, &want);
+}
+
+int rnn_amd_trace_texts(RecurNN *net, const u8 *const *texts, const int *lens, int n_texts, int alphabet_len,
+                        float *const *logp, u8 *const *guess) {
+  const TextsWanted want = {.logp = logp, .guess = guess};
+  return run_texts("rnn_amd_trace_texts", net, texts, lens, NULL, n_texts, alphabet_len, &want);
 }

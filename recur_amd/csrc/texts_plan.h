@@ -110,4 +110,17 @@ static inline int texts_plan_active(const TextsPlan *p, int w, int t) {
   return lo;
 }
 
+/* where each row of wave w keeps its per-step values when every step of every row leaves per_step of them (the trace of
+ * rnn_amd_trace_texts): off[j], for the wave's nrows rows, is the prefix sum of (len - 1) * per_step in plan order.
+ * Returns the wave's total.  Lengths descend through the plan, so wave 0's total is the largest. */
+static inline unsigned long long texts_plan_trace_offsets(const TextsPlan *p, int w, int per_step, unsigned long long *off) {
+  const int *len = p->len + p->waves[w].row0;
+  unsigned long long at = 0;
+  for (int j = 0; j < p->waves[w].nrows; j++) {
+    off[j] = at;
+    at += (unsigned long long)(len[j] - 1) * (unsigned long long)per_step;
+  }
+  return at;
+}
+
 #endif

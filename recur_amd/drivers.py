@@ -5,7 +5,8 @@ tests also point it at the compiled reference) exactly the way the reference's o
 charmodel-predict.c:288-311).  ``AmdBatchedSet`` drives the additive batched entry points (include/recur_amd.h
 part 2): the whole set per call, text on the device.  ``run_texts`` scores a list of encoded texts against one net in
 one batched call (rnn_amd_run_texts / _heads), ``sample_texts`` draws a batch of texts from one net in one batched call
-(rnn_amd_sample_texts), ``continue_texts`` continues a batch of prompts (rnn_amd_continue_texts).  ``synthetic_text_np`` is the seeded symbol stream of
+(rnn_amd_sample_texts), ``continue_texts`` continues a batch of prompts (rnn_amd_continue_texts), ``trace_texts`` hands
+back the scorer's figures symbol by symbol (rnn_amd_trace_texts).  ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
 """
@@ -73,6 +74,32 @@ def run_texts(lib, net, texts, skips=None, alphabet_len=0):
     if r != 0:
         raise ValueError("rnn_amd_run_texts refused the batch (see stderr)")
     return sums if alphabet_len else sums[:, 0]
+
+
+TRACE_GUARD = 4  # guard entries behind every array trace_texts hands to the library
+
+
+def trace_texts(lib, net, texts, alphabet_len=0, guesses=True):
+    """rnn_amd_trace_texts for a list of numpy uint8 arrays: per text (logp [len - 1][heads] float32, guess [len - 1][heads]
+    uint8 or None), the log2 likelihood of every next symbol and the net's best guess at it, each text on its own from
+    the net's current hidden state.  A text shorter than 2 symbols gets empty arrays.  Every array is allocated with
+    guard entries behind it (NaN, 0xEE), which must come back untouched."""
+    keep, ptrs, lens = text_pointers(texts)
+    heads = net.contents.output_size // alphabet_len if alphabet_len else 1
+    n = len(keep)
+    counts = [max(len(t) - 1, 0) * heads for t in keep]
+    lp = [np.full(c + TRACE_GUARD, np.nan, np.float32) for c in counts]
+    gs = [np.full(c + TRACE_GUARD, 0xEE, np.uint8) for c in counts] if guesses else None
+    lpp = (rc.c_float_p * max(n, 1))(*[rc.fptr(a) for a in lp])
+    gsp = (rc.c_u8_p * max(n, 1))(*[rc.u8ptr(a) for a in gs]) if guesses else None
+    r = lib.rnn_amd_trace_texts(net, ptrs, rc.iptr(lens), n, alphabet_len, lpp, gsp)
+    if r != 0:
+        raise ValueError("rnn_amd_trace_texts refused the batch (see stderr)")
+    assert all(np.all(np.isnan(a[c:])) for a, c in zip(lp, counts)), "log2 likelihoods behind a text's trace"
+    assert all(not np.any(np.isnan(a[:c])) for a, c in zip(lp, counts)), "a traced step was not written"
+    assert not guesses or all(np.all(a[c:] == 0xEE) for a, c in zip(gs, counts)), "guesses behind a text's trace"
+    return [(lp[k][:counts[k]].reshape(-1, heads).copy(),
+             gs[k][:counts[k]].reshape(-1, heads).copy() if guesses else None) for k in range(n)]
 
 
 def sample_texts(lib, net, first, seeds, max_len, bias=0.0, stop=-1, alphabet_len=0, head=0):
