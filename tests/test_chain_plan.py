@@ -186,6 +186,8 @@ def test_where_the_one_launch_chain_does_not_take_the_call(harness):
     has(plan(harness, {"RECUR_AMD_CHAIN_PERSIST": "0"}, **call(1024, 512, 3)), form="wide", ns=16, mt=32, tm=16, tn=16, blocks=256)
     has(plan(harness, {"RECUR_AMD_CHAIN_PERSIST": "0"}, **call(1024, 768, 3)), form="wide", ns=16, mt=64, tm=12, tn=16, blocks=192)
     # streams at different ring positions: k_chain_main<false>, stages counted at run time
+    # (run on the GPU by test_gpu_staggered_rings.py: test_a_staggered_text_step_matches_the_oracle, whose shapes
+    # test_staggered_rings_cpu.py pins in the same way)
     p = plan(harness, **call(1024, 256, 20, uniform_idx=-1))
     has(p, wanted=0, form="main", uniform=0, ns=0, nstages=8, tm=8, tn=32, blocks=256, parts=32)
     segments(p)

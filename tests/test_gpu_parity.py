@@ -788,9 +788,14 @@ def test_text_step_shape_sweep(amd, label, kw):
     _one_generation_from_device_state(amd, kw)
 
 
-def _one_generation_from_device_state(amd, kw):
+def _one_generation_from_device_state(amd, kw, prepare=None, elem_floor=1e-2):
+    """(prepare: called with the device set right after it is made; elem_floor: replay.check's, for a regime whose
+    measured spread in the reference itself asks for the hot regime's floor; returns the two snapshots after the compared
+    generation and the number of attempts it took, for callers that go on to ask more of them)"""
     kw = dict(kw, learn_rate=1e-5, seed=3)
     g = sc.AmdBatchedSet(amd, **kw)
+    if prepare:
+        prepare(g)
     text = sc.synthetic_text(30000)
     n = kw["D"] + 3
     for i in range(n):
@@ -820,9 +825,10 @@ def _one_generation_from_device_state(amd, kw):
         raise AssertionError("no generation without a rounding-level mask flip in 4 attempts")
     assert g.stats().bptt_depth_sum == float(so["bptt_depth"].sum())
     replay.check(sg, so, RTOL, keys=["ih_delta", "ho_delta", "ih_w", "ho_w", "ih_m", "ho_m", "hidden",
-                                     "output", "o_error", "hist", "min_error_factor", "ih_scale"])
+                                     "output", "o_error", "hist", "min_error_factor", "ih_scale"], elem_floor=elem_floor)
     g.close()
     o.close()
+    return sg, so, attempt + 1
 
 
 def test_noise_generated_ahead_is_dropped_when_a_generator_moves(amd):

@@ -7,7 +7,9 @@ Context: VERDICT.md round 4, weak spot 2 ("an element 100x smaller than the arra
 A sum of K products carries ~sqrt(K) eps of ITS LARGEST partial sums as rounding, not of its own value: an element that
 cancelled down to 1e-3 of the array's largest differs by 1e-4 .. 1e-3 of itself between any two summation orders --
 including the reference's two builds.  The numbers printed here are what tests/replay.py's element-wise bar is set by.
-usage: python tools/ref_elementwise_self_difference.py"""
+usage: python tools/ref_elementwise_self_difference.py [H,S,D,lr,warm[,activation[,variance[,seed]]] ...]
+(without arguments: the shapes the bar was set by; with them: those shapes instead, e.g. 130,40,6,1e-5,9,5,0.1,3 for a
+RECLIP20 net with large initial weights, whose units reach the ceiling)"""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests"))
 import numpy as np
@@ -27,9 +29,13 @@ def elem(a, b, floor):
 print("%-18s %-9s %9s %9s | element-wise, floor 1e-1 %9s 1e-2 %9s 1e-3" % ("shape H/S/D", "array", "2-norm", "max elem", "", ""))
 # (the last two: the hot regime of the golden case hot_clamps and of the direct-delta-path test -- learn rate 0.08,
 # streams soft-clipped, chains ending early: the error grows through the chain's steps)
-for (H, S, D, lr, warm) in ((99, 4, 10, 1e-3, 14), (256, 16, 8, 1e-4, 10), (1024, 8, 20, 1e-5, 22), (39, 4, 12, 0.08, 2),
-                            (128, 32, 8, 0.08, 2)):
+SHAPES = ((99, 4, 10, 1e-3, 14), (256, 16, 8, 1e-4, 10), (1024, 8, 20, 1e-5, 22), (39, 4, 12, 0.08, 2), (128, 32, 8, 0.08, 2))
+if len(sys.argv) > 1:
+    SHAPES = [tuple(float(x) if "." in x or "e" in x else int(x) for x in arg.split(",")) for arg in sys.argv[1:]]
+for (H, S, D, lr, warm, *more) in SHAPES:
     kw = dict(input_size=42, hidden_size=H, output_size=42, S=S, D=D, learn_rate=lr, seed=11)
+    if more:  # activation, variance of the initial weights, seed
+        kw.update(zip(("activation", "variance", "seed"), more))
     if lr == 0.08:
         warm = 2
     a = sc.ApiSet(strict, softmax_best_guess=strict.ref_softmax_best_guess, **kw)
@@ -55,6 +61,6 @@ for (H, S, D, lr, warm) in ((99, 4, 10, 1e-3, 14), (256, 16, 8, 1e-4, 10), (1024
             rc.view(y.hidden_layer, a.H)[:] = rc.view(x.hidden_layer, a.H)
             y.bptt.contents.min_error_factor = x.bptt.contents.min_error_factor
     for k in KEYS:
-        print("%-18s %-9s %9.2e %9.2e | %30.2e %14.2e %14.2e" % ("%d/%d/%d" % (H, S, D), k, *worst[k]))
+        print("%-18s %-9s %9.2e %9.2e | %30.2e %14.2e %14.2e" % ("%d/%d/%d" % (H, S, D) + ("/a%d" % more[0] if more else ""), k, *worst[k]))
     a.close()
     b.close()
