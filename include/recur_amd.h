@@ -698,8 +698,8 @@ int rnn_amd_sample_texts(RecurNN *net, const int *first, const u64 *seeds, int n
  * shorter rows end; one launch between two passes feeds a row its next prompt symbol or draws for it.  One device
  * synchronisation per wave and one more every 64 steps, to end a wave whose every running row has met its stop symbol.
  * With one-symbol prompts the call is rnn_amd_sample_texts(first[k] = prompts[k][0]), bit for bit.
- * Not done: the prompt is not scored (rnn_amd_run_texts does that), every row starts from net's one hidden row, and no
- * row's state is handed back.
+ * The prompt is not scored, every row starts from net's one hidden row and no row's state is handed back: for those
+ * see rnn_amd_run_texts_from and rnn_amd_continue_texts_from below.
  * Returns 0; n_texts == 0 or max_len == 0 returns 0 at once (lengths zeroed, rng_out[k] as seeded, no device asked for).
  * Returns -1 when a row's draw met the attempt cap, as rnn_amd_sample_texts does.  Returns -1 with a message on stderr and
  * nothing computed, before anything needs a device: all that rnn_amd_sample_texts refuses; a NULL prompts or prompt_lens;
@@ -708,6 +708,60 @@ int rnn_amd_sample_texts(RecurNN *net, const int *first, const u64 *seeds, int n
 int rnn_amd_continue_texts(RecurNN *net, const u8 *const *prompts, const int *prompt_lens, const u64 *seeds, int n_texts,
                            int max_len, float bias, int stop_point, int alphabet_len, int head,
                            u8 *out /* [n_texts][max_len] */, int *out_lens, rand_ctx *rng_out /* [n_texts] or NULL */);
+/* The batched text calls with a STATE PER TEXT, taken from the caller and handed back: what lets them be composed -- a
+ * long text scored or traced in windows, a passage drawn in instalments, a prompt scored and then continued without
+ * feeding it twice -- as the reference composes rnn_char_prime, rnn_char_confabulate and more of either on one net that
+ * keeps its state.  Nothing new is owned or freed: states travel through host arrays of the caller's.
+ * A state is a row of net->h_size floats laid out as net->hidden_layer is.  Only its elements [1, hidden_size] carry
+ * information (the input row of a forward pass takes no other, recur-nn.c:104-112).  h_in and h_out are
+ * [n_texts][net->h_size], contiguous, in the caller's order.  Element 0 and the padding behind hidden_size are never read
+ * from h_in; what is written there in h_out is unspecified.  Values in h_in are not inspected.
+ *   h_in == NULL    every row starts from net's hidden row at the moment of the call, as in the calls above.  With h_in,
+ *                   h_out (and rng_in) all NULL each call IS its counterpart above, bit for bit: rnn_amd_run_texts_from
+ *                   with alphabet_len == 0 is rnn_amd_run_texts, with alphabet_len > 0 rnn_amd_run_texts_heads (sums
+ *                   [n_texts][n_heads]); rnn_amd_trace_texts_from is rnn_amd_trace_texts; rnn_amd_continue_texts_from is
+ *                   rnn_amd_continue_texts.
+ *   h_in != NULL    clone c_k starts from h_in[k] instead.  Nothing else of those contracts changes: the texts do not see
+ *                   one another, there is no noise, net's generator is untouched, and `net` -- host and device copies,
+ *                   hidden row, generator, what it computes next -- is left exactly as it was.
+ *   h_out != NULL   h_out[k] is c_k's hidden row after its last forward pass:
+ *                   run and trace: after texts[k][0 .. lens[k] - 2] were fed; a text with lens[k] < 2 feeds nothing and
+ *                     h_out[k] is its start state.
+ *                   continue: after prompts[k] and out[k][0 .. out_lens[k] - 2] were fed.  The last symbol written is
+ *                     never fed, whether it was the stop symbol or index max_len - 1.  (A row whose draw failed, return
+ *                     -1, ends on an output row without a total; its state is the one that output row came from, after
+ *                     every symbol written was fed, and is as little use.)
+ *                   With h_in == NULL the start state that a text without a forward pass gets back is net's hidden row,
+ *                   read without changing net's host or device copy.
+ *   RESUMING        the next call on a state begins with the row's last symbol: texts[k] + lens[k] - 1 is where the next
+ *                   window of a text starts (windows overlap by one symbol: a window of n symbols scores n - 1 steps),
+ *                   and {out[k][out_lens[k] - 1]} is the one-symbol prompt that continues a passage -- with rng_in =
+ *                   the rng_out of the call before, the instalments are the passage drawn in one call.
+ *   ALIASING        h_out may be the same array as h_in, for an update in place.  Any other overlap is undefined.
+ *   rng_in          (continue only) non-NULL: c_k's generator starts as rng_in[k], seeds is ignored and may be NULL.
+ *                   NULL: init_rand64(seeds[k]) as above.  Both NULL with n_texts > 0 is refused.  rng_out may be rng_in.
+ *   sums == NULL    allowed in rnn_amd_run_texts_from when h_out is not NULL: the texts are fed and nothing is scored,
+ *                   the batched rnn_char_prime.  Both NULL with n_texts > 0 is refused.
+ * Chunks and bits: two calls give the same bits where every forward pass runs in the same form (fwd_plan.h goes by the
+ * row count); texts of equal lengths cut at equal places do, ragged ones agree to rounding -- the bar, not the bits, as
+ * between any two calls with different row counts.  The same holds for a row that has met its stop symbol inside the
+ * running prefix of its wave: it is not fed again and the later passes recompute its hidden row from the same input row,
+ * so between calls whose other rows differ its h_out is equal to rounding, not to the bit.
+ * Cost: one host-to-device copy of a wave's states before its first launch and one back in front of the wave's one
+ * synchronisation, h_size floats per row each; no synchronisation is added.
+ * Returns as the counterparts do, and: n_texts == 0 returns 0 and touches nothing; max_len == 0 in continue zeroes the
+ * lengths, rng_out[k] is the start generator and h_out[k] the start state; where no text takes a row (every lens[k] < 2,
+ * or max_len == 0) and h_in is given, h_out is filled by the host alone and no device is asked for.  Returns -1 with a
+ * message on stderr and nothing computed, before anything needs a device: all that the counterpart refuses, and the two
+ * refusals above.  There is no _from form of rnn_amd_sample_texts: a one-symbol prompt is that call, bit for bit. */
+int rnn_amd_run_texts_from(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
+                           int alphabet_len, const float *h_in, float *h_out, double *sums);
+int rnn_amd_trace_texts_from(RecurNN *net, const u8 *const *texts, const int *lens, int n_texts, int alphabet_len,
+                             const float *h_in, float *h_out, float *const *logp, u8 *const *guess);
+int rnn_amd_continue_texts_from(RecurNN *net, const u8 *const *prompts, const int *prompt_lens, const u64 *seeds,
+                                const rand_ctx *rng_in, int n_texts, int max_len, float bias, int stop_point,
+                                int alphabet_len, int head, const float *h_in, float *h_out,
+                                u8 *out /* [n_texts][max_len] */, int *out_lens, rand_ctx *rng_out /* [n_texts] or NULL */);
 /* Block until all queued device work of the library has finished. */
 void rnn_amd_synchronize(void);
 

@@ -169,6 +169,20 @@ int rnn_amd_char_confabulate_texts(RecurNN *net, RnnCharAlphabet *a, const u64 *
 int rnn_amd_char_continue_texts(RecurNN *net, RnnCharAlphabet *a, const char *const *prompts, const int *prompt_bytes,
                                 const u64 *seeds, int n_texts, int char_len, float bias, int stop_point, char **dest,
                                 int byte_len, int *bytes);
+/* Prompts scored AND continued, each `repeats` times, with every prompt fed ONCE: one rnn_amd_run_texts_from (recur_amd.h)
+ * feeds the encoded prompts from the state `net` has and hands back each prompt's sum and state; the states, `repeats`
+ * copies of each, are where one rnn_amd_continue_texts_from goes on from each prompt's last symbol.  entropy[k] is what
+ * rnn_amd_char_cross_entropy_texts gives for prompt k with ignore_first 0 and no prefix (bits per symbol; a one-symbol
+ * prompt has nothing scored and gets that call's 0 / -0).  Passage k * repeats + i -- dest, bytes and seeds are
+ * [n_texts * repeats] -- continues prompt k with a generator seeded init_rand64(seeds[k * repeats + i]); only the
+ * continuation is written, under the room rule above.  With repeats 1 the passages are rnn_amd_char_continue_texts's, to
+ * the bit where the prompts encode to equal lengths and to rounding of a draw otherwise (recur_amd.h: the bar, not the
+ * bits).  `net` is left as it was.  Refused as rnn_amd_char_continue_texts refuses, and: repeats < 1, a NULL entropy.
+ * Otherwise returns what the two calls return. */
+int rnn_amd_char_score_and_continue_texts(RecurNN *net, RnnCharAlphabet *a, const char *const *prompts,
+                                          const int *prompt_bytes, const u64 *seeds, int n_texts, int repeats, int char_len,
+                                          float bias, int stop_point, char **dest /* [n_texts * repeats] */, int byte_len,
+                                          int *bytes, double *entropy /* [n_texts] */);
 
 /* ---- the multi-head text trainer (charmodel.h:132-152, 242-265;
  *      charmodel-multi-predict.c): py-recur-text.c's Net.train / Net.test backend ---- */

@@ -257,6 +257,13 @@ AMD_API = {
                                        C.c_int, c_u8_p, c_int_p, C.POINTER(RandCtx)]),
     "rnn_amd_continue_texts": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_float,
                                          C.c_int, C.c_int, C.c_int, c_u8_p, c_int_p, C.POINTER(RandCtx)]),
+    "rnn_amd_run_texts_from": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, c_int_p, C.c_int, C.c_int, c_float_p, c_float_p,
+                                         C.POINTER(C.c_double)]),
+    "rnn_amd_trace_texts_from": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, C.c_int, C.c_int, c_float_p, c_float_p,
+                                           C.POINTER(c_float_p), C.POINTER(c_u8_p)]),
+    "rnn_amd_continue_texts_from": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, C.POINTER(C.c_uint64), C.POINTER(RandCtx),
+                                              C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
+                                              c_u8_p, c_int_p, C.POINTER(RandCtx)]),
     "rnn_amd_synchronize": (None, []),
     "rnn_amd_dist_get_id": (C.c_int, [C.c_void_p]),
     "rnn_amd_dist_init": (C.c_int, [C.c_int, C.c_int, C.c_void_p]),
@@ -437,6 +444,9 @@ CHAR_API = {
                                                  C.c_int, C.POINTER(C.c_char_p), C.c_int, c_int_p]),
     "rnn_amd_char_continue_texts": (C.c_int, [NetP, AlphaP, C.POINTER(C.c_char_p), c_int_p, C.POINTER(C.c_uint64), C.c_int,
                                               C.c_int, C.c_float, C.c_int, C.POINTER(C.c_char_p), C.c_int, c_int_p]),
+    "rnn_amd_char_score_and_continue_texts": (C.c_int, [NetP, AlphaP, C.POINTER(C.c_char_p), c_int_p, C.POINTER(C.c_uint64),
+                                                        C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_char_p),
+                                                        C.c_int, c_int_p, C.POINTER(C.c_double)]),
     "rnn_char_uncollapse_text": (C.c_void_p, [AlphaP, c_u8_p, C.c_int, c_int_p]),
     "rnn_char_dump_collapsed_text": (None, [c_u8_p, C.c_int, C.c_char_p, C.c_char_p]),
     "rnn_char_construct_metadata": (C.c_void_p, [MetaP]),

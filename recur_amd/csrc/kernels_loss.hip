@@ -705,6 +705,13 @@ struct TextsStep {
   int t_score, a_score, t_feed, a_feed;
 };
 constexpr int TS_WAVES = 4;
+// Where the feed half of the four k_texts_* kernels takes state row r's hidden values from, stated once: from hid0 in a
+// wave's first feed (`first`) when the call has one -- the hidden row of the net, which every row then starts from --,
+// else from the row's own hidden row: what the forward pass before left there, or, with a null hid0 in the first feed,
+// the start state the host has put there (the _from calls, texts_api.c and sample_api.c).
+__device__ __forceinline__ const float *texts_feed_hidden(const View &v, int r, const float *hid0, bool first) {
+  return first && hid0 ? hid0 : v.b.hidden + (size_t)r * v.sh.H;
+}
 // The score half of k_texts_step and k_texts_trace, stated once: one wave scores one head of alen outputs at src.  The wave
 // builds the shift and the exponentials into ex (LDS, alen floats); behind the fence lane 0 takes their sum in the
 // reference's order, the likelihood of `target` (a symbol outside the head has no probability: the cap) and returns
@@ -740,8 +747,8 @@ __global__ __launch_bounds__(64 * TS_WAVES) void k_texts_step(View v, TextsStep 
     }
   }
   if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
-    assemble_input_row(s, input_row(v, r, 0), p.hid0 ? p.hid0 : v.b.hidden + (size_t)r * s.H, RAMD_IN_ONE_HOT,
-                       text[p.t_feed], nullptr, red);
+    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_ONE_HOT, text[p.t_feed],
+                       nullptr, red);
 }
 
 // The one launch between two forward passes of rnn_amd_trace_texts (texts_api.c): k_texts_step with the floats it adds
@@ -792,8 +799,8 @@ __global__ __launch_bounds__(64 * TS_WAVES) void k_texts_trace(View v, TextsTrac
     }
   }
   if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
-    assemble_input_row(s, input_row(v, r, 0), p.hid0 ? p.hid0 : v.b.hidden + (size_t)r * s.H, RAMD_IN_ONE_HOT,
-                       text[p.t_feed], nullptr, red);
+    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_ONE_HOT, text[p.t_feed],
+                       nullptr, red);
 }
 
 // The one launch between two forward passes of rnn_amd_sample_texts (sample_api.c): N texts drawn from one net side by
@@ -814,7 +821,7 @@ struct TextsSample {
   unsigned char *text;    /* [rows][max_len] the symbols drawn                */
   int *len;               /* [rows] how many                                  */
   int *done;              /* [rows] 0 running, 1 stopped, 2 failed            */
-  const float *hid0;      /* the hidden row of the first feed                 */
+  const float *hid0;      /* the hidden row of the first feed, or nullptr     */
   int row0;               /* state row of the wave's row 0 (forward-only)     */
   int alen, head, max_len, t, stop_point;
   float bias;
@@ -886,15 +893,15 @@ __global__ __launch_bounds__(256) void k_texts_sample(View v, TextsSample p) {
   __syncthreads();
   const int hot = hot_sh;
   if (hot >= 0) /* (the whole workgroup: assemble_input_row has barriers) */
-    assemble_input_row(s, input_row(v, r, 0), p.t == 0 ? p.hid0 : v.b.hidden + (size_t)r * s.H, RAMD_IN_ONE_HOT, hot,
-                       nullptr, red);
+    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, p.t == 0), RAMD_IN_ONE_HOT, hot, nullptr, red);
 }
 
 // The one launch between two forward passes of rnn_amd_continue_texts (sample_api.c): N prompts continued by one net side
 // by side, a state row each, the rows ordered by prompt length + max_len, longest first (texts_plan.h), so that the rows
 // still running are a prefix.  One workgroup of 256 threads per row, as k_texts_sample; what launch t is for a row --
 // feeding prompt symbol t, drawing text index t - plen, or nothing -- is continue_rule.h's answer for the row's plen:
-//   prompt: the one-hot of the row's prompt symbol on the row's hidden values, at t == 0 on hid0's.  No draw, no generator.
+//   prompt: the one-hot of the row's prompt symbol on the row's hidden values, at t == 0 on hid0's (texts_feed_hidden).  No
+//     draw, no generator.
 //   draw (a row that is not done): texts_draw_and_store, k_texts_sample's draw half; the pick is fed unless it was the
 //     text's last index, the stop symbol, or a failure.
 // The symbol reaches the workgroup through LDS behind a barrier.  A row that is done or idle is not fed.  Every word has
@@ -907,7 +914,7 @@ struct TextsContinue {
   unsigned char *text;           /* [rows][max_len] the symbols drawn                 */
   int *len;                      /* [rows] how many                                   */
   int *done;                     /* [rows] 0 running, 1 stopped, 2 failed             */
-  const float *hid0;             /* the hidden row of the first feed                  */
+  const float *hid0;             /* the hidden row of the first feed, or nullptr      */
   int row0;                      /* state row of the wave's row 0 (forward-only)      */
   int alen, head, max_len, t, stop_point;
   float bias;
@@ -932,8 +939,8 @@ __global__ __launch_bounds__(256) void k_texts_continue(View v, TextsContinue p)
   __syncthreads();
   const int hot = hot_sh;
   if (hot >= 0) /* (the whole workgroup: assemble_input_row has barriers) */
-    assemble_input_row(s, input_row(v, r, 0), st.on_hid0 ? p.hid0 : v.b.hidden + (size_t)r * s.H, RAMD_IN_ONE_HOT, hot,
-                       nullptr, red);
+    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, st.on_hid0), RAMD_IN_ONE_HOT, hot, nullptr,
+                       red);
 }
 
 // rnnca's loss (gstrnnca.c:701-714, train_net): fast_sigmoid_array(answer, answer, n) IN

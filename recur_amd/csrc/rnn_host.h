@@ -221,6 +221,11 @@ void ramd_fused_net_update(RamdEngine *e, RecurNN *net, int row, unsigned batch_
 int ramd_texts_net_refused(const char *who, const RecurNN *net, int alphabet_len);
 int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const *texts, const int *lens, int n_texts,
                            int alphabet_len, const void *out);
+/* net's hidden row as it stands, into row[h_size], with neither of net's copies changed; and, shared with
+ * rnn_amd_continue_texts_from (sample_api.c), h_out of the texts that take no row (lens[k] < 2; n_rows: how many take
+ * one): their start state, h_in[k] or -- h_in NULL -- that hidden row (texts_states.h).  Returns 0, or -1 out of memory */
+void ramd_texts_net_hidden_row(RecurNN *net, float *row);
+int ramd_texts_fill_rowless(RecurNN *net, const int *lens, int n_texts, int n_rows, const float *h_in, float *h_out);
 
 /* set_api.c */
 void ramd_set_need_training(const RnnAmdSet *set, const char *what);

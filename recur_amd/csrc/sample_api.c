@@ -8,11 +8,14 @@
  * and not written.
  * rnn_amd_continue_texts and rnn_amd_char_continue_texts are the same with a prompt per row in front of the draws: the
  * rows are laid out by prompt length + max_len (texts_plan.h, as rnn_amd_run_texts lays out its texts), and the launch
- * between two forward passes (k_texts_continue) feeds a row its prompt or draws for it, as continue_rule.h says. */
+ * between two forward passes (k_texts_continue) feeds a row its prompt or draws for it, as continue_rule.h says.
+ * rnn_amd_continue_texts_from is that call with every row's start state and generator from the caller's arrays and its
+ * final state handed back (texts_states.h: which state belongs to which row); rnn_amd_continue_texts is it with NULLs. */
 #define RAMD_HIP_HOST 1
 #include <limits.h>
 #include "char_host.h"
 #include "texts_plan.h"
+#include "texts_states.h"
 #include "continue_rule.h"
 
 #define SAMPLE_CHECK_EVERY 64 /* steps between two looks at the rows' done words */
@@ -53,8 +56,9 @@ static int sample_texts_refused(const char *who, const RecurNN *net, const int *
   return 0;
 }
 
+/* (seeds: the call's seeds, or where it takes the rows' generators from the caller, those) */
 static int continue_texts_refused(const char *who, const RecurNN *net, const u8 *const *prompts, const int *prompt_lens,
-                                  const u64 *seeds, int n_texts, int max_len, int alphabet_len, int head, const void *out,
+                                  const void *seeds, int n_texts, int max_len, int alphabet_len, int head, const void *out,
                                   const int *out_lens) {
   if (sample_call_refused(who, net, n_texts, max_len, alphabet_len, head, prompts && prompt_lens && seeds && out && out_lens)) {
     return -1;
@@ -207,13 +211,35 @@ typedef struct ContinueBuffers {
   u8 *h_prompt, *d_prompt;
   unsigned long long *h_off, *d_off;
   int *h_plen, *d_plen;
+  float *h_state; /* [rows][H] the wave's states on their way in and out, or NULL */
 } ContinueBuffers;
+
+/* where a call's rows start and what it hands back of them besides the text: start states and generators (NULL: the
+ * net's hidden row, init_rand64 of the seeds), final states and generators (NULL: not wanted) */
+typedef struct ContinueStates {
+  const float *h_in;
+  float *h_out;
+  const u64 *seeds;
+  const rand_ctx *rng_in;
+  rand_ctx *rng_out;
+} ContinueStates;
+
+/* row k's generator before its first draw */
+static rand_ctx start_generator(const ContinueStates *cs, int k) {
+  rand_ctx g;
+  if (cs->rng_in) {
+    g = cs->rng_in[k];
+  } else {
+    ramd_init_rand64(&g, cs->seeds[k]);
+  }
+  return g;
+}
 
 /* wave w of the plan (its len is prompt length + max_len) on the state rows from r0 on; returns the number of rows whose
  * draw failed */
 static int continue_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, int w, int r0, const u8 *const *prompts,
-                         const u64 *seeds, int max_len, float bias, int stop_point, int alen, int head,
-                         const ContinueBuffers *cb, u8 *out, int *out_lens, rand_ctx *rng_out) {
+                         const ContinueStates *cs, int max_len, float bias, int stop_point, int alen, int head,
+                         const ContinueBuffers *cb, u8 *out, int *out_lens) {
   const RamdShape *s = &e->sh;
   const SampleBuffers *sb = &cb->sb;
   const TextsWave *wave = &plan->waves[w];
@@ -225,7 +251,7 @@ static int continue_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *pla
     cb->h_plen[j] = plen;
     memcpy(cb->h_prompt + at, prompts[k], (size_t)plen);
     at += (size_t)plen;
-    ramd_init_rand64(&sb->h_rng[j], seeds[k]);
+    sb->h_rng[j] = start_generator(cs, k);
   }
   ramd_h2d(cb->d_prompt, cb->h_prompt, at);
   ramd_h2d(cb->d_off, cb->h_off, (size_t)n * sizeof(unsigned long long));
@@ -233,8 +259,16 @@ static int continue_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *pla
   ramd_h2d(sb->d_rng, sb->h_rng, (size_t)n * sizeof(rand_ctx));
   HIP_OK(hipMemsetAsync(sb->d_len, 0, (size_t)n * sizeof(int), ramd_stream));
   HIP_OK(hipMemsetAsync(sb->d_done, 0, (size_t)n * sizeof(int), ramd_stream));
-  /* every row starts from the net's hidden row: the first launch builds the input rows from it */
+  /* every row starts from the net's hidden row: the first launch builds the input rows from it.  Or from its own state:
+   * the wave's rows of h_in go into the state rows, which are contiguous, and the first launch reads them there as every
+   * later one does (a null hid0, k_texts_continue) */
   const float *hid0 = e->b.hidden + (size_t)ramd_state_row(e, ramd_priv(net)) * s->H;
+  float *states = e->b.hidden + (size_t)r0 * s->H;
+  if (cs->h_in) {
+    texts_states_pack(plan, w, cs->h_in, NULL, s->H, s->hidden_size, cb->h_state);
+    ramd_h2d(states, cb->h_state, (size_t)n * s->H * sizeof(float));
+    hid0 = NULL;
+  }
   const int lead = cb->h_plen[0]; /* the wave's longest row: its launches are the wave's */
   int rows = n;                   /* the rows launch t is for: those that were fed after launch t - 1 */
   for (int t = 0;; t++) {
@@ -267,7 +301,16 @@ static int continue_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *pla
   ramd_d2h(sb->h_len, sb->d_len, (size_t)n * sizeof(int));
   ramd_d2h(sb->h_done, sb->d_done, (size_t)n * sizeof(int));
   ramd_d2h(sb->h_rng, sb->d_rng, (size_t)n * sizeof(rand_ctx));
+  if (cs->h_out) {
+    /* every row has had a forward pass (launch 0 feeds them all), and its hidden row is the one after its last feed: a
+     * pass over a row that was not fed since recomputes that row from the same input row, and a look above ends the wave
+     * only where its launch fed no row (every row it could have fed is done) */
+    ramd_d2h(cb->h_state, states, (size_t)n * s->H * sizeof(float));
+  }
   ramd_dsync(); /* the wave's synchronisation */
+  if (cs->h_out) {
+    texts_states_unpack(plan, w, cb->h_state, s->H, cs->h_out);
+  }
   int failed = 0;
   for (int j = 0; j < n; j++) {
     const int k = plan->order[wave->row0 + j];
@@ -275,22 +318,36 @@ static int continue_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *pla
     memcpy(out + (size_t)k * max_len, sb->h_text + (size_t)j * max_len, (size_t)len);
     out_lens[k] = len;
     failed += sb->h_done[j] == 2;
-    if (rng_out) {
-      rng_out[k] = sb->h_rng[j];
+    if (cs->rng_out) {
+      cs->rng_out[k] = sb->h_rng[j];
     }
   }
   return failed;
 }
 
-int rnn_amd_continue_texts(RecurNN *net, const u8 *const *prompts, const int *prompt_lens, const u64 *seeds, int n_texts,
-                           int max_len, float bias, int stop_point, int alphabet_len, int head, u8 *out, int *out_lens,
-                           rand_ctx *rng_out) {
-  const char *who = "rnn_amd_continue_texts";
-  if (continue_texts_refused(who, net, prompts, prompt_lens, seeds, n_texts, max_len, alphabet_len, head, out, out_lens)) {
+static int continue_texts(const char *who, RecurNN *net, const u8 *const *prompts, const int *prompt_lens, int n_texts,
+                          int max_len, float bias, int stop_point, int alphabet_len, int head, const ContinueStates *cs,
+                          u8 *out, int *out_lens) {
+  if (continue_texts_refused(who, net, prompts, prompt_lens, cs->rng_in ? (const void *)cs->rng_in : (const void *)cs->seeds,
+                             n_texts, max_len, alphabet_len, head, out, out_lens)) {
     return -1;
   }
-  if (n_texts == 0 || max_len == 0) {
-    return nothing_to_draw(seeds, n_texts, out_lens, rng_out);
+  if (n_texts == 0) {
+    return 0;
+  }
+  if (max_len == 0) { /* nothing to draw: lengths zeroed, generators and states as they start, no device asked for... */
+    for (int k = 0; k < n_texts; k++) {
+      out_lens[k] = 0;
+      if (cs->rng_out) {
+        cs->rng_out[k] = start_generator(cs, k);
+      }
+    }
+    /* (... unless the start state is the net's hidden row and only the device has it.  No text takes a row) */
+    if (ramd_texts_fill_rowless(net, out_lens, n_texts, 0, cs->h_in, cs->h_out)) {
+      fprintf(stderr, "librecur_amd: %s: out of memory\n", who);
+      return -1;
+    }
+    return 0;
   }
   int *lens = ramd_zalloc((size_t)n_texts * sizeof(int)); /* what a row is planned by: the forward passes it takes, plus 1 */
   TextsPlan plan;
@@ -327,6 +384,7 @@ int rnn_amd_continue_texts(RecurNN *net, const u8 *const *prompts, const int *pr
   cb.h_prompt = ramd_zalloc(bytes);
   cb.h_off = ramd_zalloc((size_t)widest * sizeof(unsigned long long));
   cb.h_plen = ramd_zalloc((size_t)widest * sizeof(int));
+  cb.h_state = cs->h_in || cs->h_out ? ramd_zalloc((size_t)widest * e->sh.H * sizeof(float)) : NULL;
   cb.sb.d_len = ramd_dev_alloc((size_t)widest * sizeof(int));
   cb.sb.d_done = ramd_dev_alloc((size_t)widest * sizeof(int));
   cb.sb.d_rng = ramd_dev_alloc((size_t)widest * sizeof(rand_ctx));
@@ -336,8 +394,7 @@ int rnn_amd_continue_texts(RecurNN *net, const u8 *const *prompts, const int *pr
   cb.d_plen = ramd_dev_alloc((size_t)widest * sizeof(int));
   int failed = 0;
   for (int w = 0; w < plan.n_waves; w++) {
-    failed += continue_wave(e, net, &plan, w, r0, prompts, seeds, max_len, bias, stop_point, alen, head, &cb, out, out_lens,
-                            rng_out);
+    failed += continue_wave(e, net, &plan, w, r0, prompts, cs, max_len, bias, stop_point, alen, head, &cb, out, out_lens);
   }
   ramd_dev_free(cb.sb.d_len);
   ramd_dev_free(cb.sb.d_done);
@@ -353,6 +410,7 @@ int rnn_amd_continue_texts(RecurNN *net, const u8 *const *prompts, const int *pr
   free(cb.h_prompt);
   free(cb.h_off);
   free(cb.h_plen);
+  free(cb.h_state);
   texts_plan_free(&plan);
   if (failed) {
     fprintf(stderr, "librecur_amd: %s: %d of %d texts met the attempt cap of the draw (an output row without a total)\n",
@@ -360,6 +418,23 @@ int rnn_amd_continue_texts(RecurNN *net, const u8 *const *prompts, const int *pr
     return -1;
   }
   return 0;
+}
+
+int rnn_amd_continue_texts_from(RecurNN *net, const u8 *const *prompts, const int *prompt_lens, const u64 *seeds,
+                                const rand_ctx *rng_in, int n_texts, int max_len, float bias, int stop_point,
+                                int alphabet_len, int head, const float *h_in, float *h_out, u8 *out, int *out_lens,
+                                rand_ctx *rng_out) {
+  const ContinueStates cs = {.h_in = h_in, .h_out = h_out, .seeds = seeds, .rng_in = rng_in, .rng_out = rng_out};
+  return continue_texts("rnn_amd_continue_texts_from", net, prompts, prompt_lens, n_texts, max_len, bias, stop_point,
+                        alphabet_len, head, &cs, out, out_lens);
+}
+
+int rnn_amd_continue_texts(RecurNN *net, const u8 *const *prompts, const int *prompt_lens, const u64 *seeds, int n_texts,
+                           int max_len, float bias, int stop_point, int alphabet_len, int head, u8 *out, int *out_lens,
+                           rand_ctx *rng_out) {
+  const ContinueStates cs = {.seeds = seeds, .rng_out = rng_out};
+  return continue_texts("rnn_amd_continue_texts", net, prompts, prompt_lens, n_texts, max_len, bias, stop_point, alphabet_len,
+                        head, &cs, out, out_lens);
 }
 
 /* rnn_char_confabulate's room rule (char_sampling.c): byte_len - (utf8 ? 5 : 1) bytes for symbols -- one may need four,
@@ -462,6 +537,84 @@ int rnn_amd_char_continue_texts(RecurNN *net, RnnCharAlphabet *a, const char *co
                                  lens, NULL);
       symbols_to_texts(a, syms, char_len, lens, n_texts, room, dest, bytes);
     }
+  }
+  for (int k = 0; k < n_texts; k++) {
+    free(enc[k]);
+  }
+  free(enc);
+  free(plens);
+  free(lens);
+  free(syms);
+  return r;
+}
+
+/* Prompts scored AND continued, every prompt fed once: one rnn_amd_run_texts_from hands back each prompt's sum and the
+ * state behind its last symbol but one; the states, `repeats` times each, are where one rnn_amd_continue_texts_from goes
+ * on from the prompts' last symbols */
+int rnn_amd_char_score_and_continue_texts(RecurNN *net, RnnCharAlphabet *a, const char *const *prompts,
+                                          const int *prompt_bytes, const u64 *seeds, int n_texts, int repeats, int char_len,
+                                          float bias, int stop_point, char **dest, int byte_len, int *bytes,
+                                          double *entropy) {
+  const char *who = "rnn_amd_char_score_and_continue_texts";
+  if (!net || !a || n_texts < 0 || char_len < 0 || repeats < 1 || (n_texts > 0 && repeats > INT_MAX / n_texts) ||
+      (n_texts > 0 && (!prompts || !prompt_bytes || !seeds || !dest || !bytes || !entropy))) {
+    fprintf(stderr, "librecur_amd: %s: %d texts %d times of %d characters, or a NULL argument\n", who, n_texts, repeats,
+            char_len);
+    return -1;
+  }
+  if (n_texts == 0) {
+    return 0;
+  }
+  const int rows = n_texts * repeats;
+  const size_t H = (size_t)net->h_size;
+  u8 **enc = calloc((size_t)n_texts, sizeof(u8 *));
+  int *plens = calloc((size_t)n_texts, sizeof(int));
+  int *lens = calloc((size_t)rows, sizeof(int)); /* (a refused call writes none) */
+  u8 *syms = malloc((size_t)rows * RAMD_MAX(char_len, 1));
+  int r = 0;
+  for (int k = 0; k < n_texts && r == 0; k++) {
+    if (prompts[k] && prompt_bytes[k] >= 0) {
+      enc[k] = rnn_char_alloc_encoded_text(a, prompts[k], prompt_bytes[k], &plens[k], NULL, false);
+    }
+    if (plens[k] < 1) {
+      fprintf(stderr, "librecur_amd: %s: prompt %d encodes to no symbol\n", who, k);
+      r = -1;
+    }
+  }
+  const int room = r ? 0 : room_for_texts(a, rows, dest, byte_len, bytes);
+  if (r) { /* refused: nothing computed, every text empty */
+    for (int i = 0; i < rows; i++) {
+      if (byte_len > 0) {
+        dest[i][0] = 0;
+      }
+      bytes[i] = 0;
+    }
+  } else if (room > 0) {
+    float *state = malloc((size_t)n_texts * H * sizeof(float));
+    float *start = malloc((size_t)rows * H * sizeof(float));
+    u8 *last = malloc((size_t)rows);
+    const u8 **last_of = malloc((size_t)rows * sizeof(u8 *));
+    int *ones = malloc((size_t)rows * sizeof(int));
+    r = rnn_amd_run_texts_from(net, (const u8 *const *)enc, plens, NULL, n_texts, 0, NULL, state, entropy);
+    for (int k = 0; r == 0 && k < n_texts; k++) {
+      entropy[k] = entropy[k] / -(double)(plens[k] - 1); /* rnn_amd_char_cross_entropy_texts's expression, ignore_first 0 */
+      for (int i = k * repeats; i < (k + 1) * repeats; i++) {
+        memcpy(start + (size_t)i * H, state + (size_t)k * H, H * sizeof(float));
+        last[i] = enc[k][plens[k] - 1];
+        last_of[i] = last + i;
+        ones[i] = 1;
+      }
+    }
+    if (r == 0) {
+      r = rnn_amd_continue_texts_from(net, last_of, ones, seeds, NULL, rows, char_len, bias, stop_point, 0, 0, start, NULL,
+                                      syms, lens, NULL);
+    }
+    symbols_to_texts(a, syms, char_len, lens, rows, room, dest, bytes);
+    free(state);
+    free(start);
+    free(last);
+    free(last_of);
+    free(ones);
   }
   for (int k = 0; k < n_texts; k++) {
     free(enc[k]);

@@ -4,10 +4,15 @@
  * launch sequence, these give every text a forward-only state row of the engine's own and run the rows together: which
  * text gets which row, in how many waves and with how many rows at each step is texts_plan.h's business; between two
  * forward passes of the rows there is one launch (k_texts_step, kernels_loss.hip) that scores the step just computed and
- * builds the input rows of the next.  The net the caller passes is read -- its weights, its hidden row -- and not written. */
+ * builds the input rows of the next.  The net the caller passes is read -- its weights, its hidden row -- and not written.
+ * The public calls are the _from forms (rnn_amd_run_texts_from, rnn_amd_trace_texts_from): every text's start state from
+ * the caller's h_in and its final state into the caller's h_out, either of them NULL for "the net's hidden row" and "not
+ * wanted"; which state belongs to which row is texts_states.h's business.  The forms without states call them with NULLs. */
 #define RAMD_HIP_HOST 1
+#include <limits.h>
 #include "rnn_host.h"
 #include "texts_plan.h"
+#include "texts_states.h"
 
 int ramd_texts_net_refused(const char *who, const RecurNN *net, int alphabet_len) {
   if (net->bottom_layer) {
@@ -46,12 +51,49 @@ int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const 
   return 0;
 }
 
-/* what a call wants back: the sums form (sums != NULL: one double per text and head), or the trace form (every float the
- * sums form would add, in logp, and -- unless NULL -- the best guess next to each) */
+/* net's hidden row as it stands at this moment, into row[h_size], with neither of net's copies changed: the host's where
+ * that is current, else the device's, read and not adopted */
+void ramd_texts_net_hidden_row(RecurNN *net, float *row) {
+  const RamdPriv *p = ramd_priv(net);
+  RamdEngine *e = p->eng;
+  if (p->host_valid || !e || !e->dev_ready) {
+    memcpy(row, net->hidden_layer, (size_t)net->h_size * sizeof(float));
+    return;
+  }
+  ramd_d2h(row, e->b.hidden + (size_t)ramd_state_row(e, p) * e->sh.H, (size_t)e->sh.H * sizeof(float));
+  ramd_dsync();
+}
+
+/* h_out of the texts that take no row: their start state, by the host alone unless the net's hidden row is wanted (h_in
+ * NULL) and only the device has it.  Returns 0, or -1 out of memory */
+int ramd_texts_fill_rowless(RecurNN *net, const int *lens, int n_texts, int n_rows, const float *h_in, float *h_out) {
+  if (!h_out || n_rows == n_texts) {
+    return 0;
+  }
+  float *row = NULL;
+  if (!h_in) {
+    row = malloc((size_t)net->h_size * sizeof(float));
+    if (!row) {
+      return -1;
+    }
+    ramd_texts_net_hidden_row(net, row);
+  }
+  texts_states_fill_rowless(lens, n_texts, h_in, row, net->h_size, net->hidden_size, h_out);
+  free(row);
+  return 0;
+}
+
+/* what a call wants back: the sums form (one double per text and head in sums; NULL: the texts are fed and nothing is
+ * scored, rnn_char_prime's loop), or the trace form (every float the sums form would add, in logp, and -- unless NULL --
+ * the best guess next to each); and the states: every text's start state in h_in (NULL: the net's hidden row), its final
+ * state into h_out (NULL: not wanted) */
 typedef struct TextsWanted {
+  int trace;
   double *sums;
   float *const *logp;
   u8 *const *guess;
+  const float *h_in;
+  float *h_out;
 } TextsWanted;
 
 /* one wave of the plan on the state rows from r0 on; the d_* arrays have room for the plan's first (largest) wave, the
@@ -65,6 +107,7 @@ typedef struct TextsBuffers {
   double *h_acc, *d_acc;
   unsigned long long *h_off_tr, *d_off_tr;
   u8 *h_trace, *d_trace;
+  float *h_state; /* [rows][H] the wave's states on their way in and out, or NULL */
 } TextsBuffers;
 
 static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, int w, const u8 *const *texts, int r0,
@@ -84,7 +127,7 @@ static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, i
   ramd_h2d(tb->d_off, tb->h_off, (size_t)n * sizeof(unsigned long long));
   size_t traced = 0; /* the wave's traced values */
   u8 *d_guess = NULL;
-  if (want->sums) {
+  if (!want->trace) {
     ramd_h2d(tb->d_skip, plan->skip + wave->row0, (size_t)n * sizeof(int));
     HIP_OK(hipMemsetAsync(tb->d_acc, 0, (size_t)n * n_sums * sizeof(double), ramd_stream));
   } else {
@@ -92,12 +135,20 @@ static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, i
     ramd_h2d(tb->d_off_tr, tb->h_off_tr, (size_t)n * sizeof(unsigned long long));
     d_guess = want->guess ? tb->d_trace + traced * sizeof(float) : NULL;
   }
-  /* every row starts from the net's hidden row: the first launch builds the input rows from it */
+  /* every row starts from the net's hidden row: the first launch builds the input rows from it.  Or from its own state:
+   * the wave's rows of h_in go into the state rows, which are contiguous, and the first launch reads them there as every
+   * later one does */
   const float *hid0 = e->b.hidden + (size_t)ramd_state_row(e, ramd_priv(net)) * s->H;
+  float *states = e->b.hidden + (size_t)r0 * s->H;
+  if (want->h_in) {
+    texts_states_pack(plan, w, want->h_in, NULL, s->H, s->hidden_size, tb->h_state);
+    ramd_h2d(states, tb->h_state, (size_t)n * s->H * sizeof(float));
+    hid0 = NULL;
+  }
   int scored = 0; /* a(t - 1): the rows whose step t - 1 waits to be scored */
   for (int t = 0; t <= wave->steps; t++) {
     const int a = t < wave->steps ? texts_plan_active(plan, w, t) : 0;
-    if (want->sums) {
+    if (!want->trace) {
       ramd_launch_texts_step(ramd_stream, s, &e->b, r0, tb->d_text, tb->d_off, tb->d_skip, tb->d_acc, t == 0 ? hid0 : NULL,
                              alen, n_sums, t - 1, scored, t, a);
     } else {
@@ -112,11 +163,17 @@ static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, i
   }
   if (want->sums) {
     ramd_d2h(tb->h_acc, tb->d_acc, (size_t)n * n_sums * sizeof(double));
-  } else {
+  } else if (want->trace) {
     ramd_d2h(tb->h_trace, tb->d_trace, traced * (sizeof(float) + (want->guess ? 1 : 0)));
   }
+  if (want->h_out) { /* a row's last forward pass was its last writer: the passes after it had fewer rows */
+    ramd_d2h(tb->h_state, states, (size_t)n * s->H * sizeof(float));
+  }
   ramd_dsync(); /* the wave's one synchronisation */
-  for (int j = 0; j < n; j++) {
+  if (want->h_out) {
+    texts_states_unpack(plan, w, tb->h_state, s->H, want->h_out);
+  }
+  for (int j = 0; j < n && (want->sums || want->trace); j++) {
     const int k = plan->order[wave->row0 + j];
     if (want->sums) {
       memcpy(want->sums + (size_t)k * n_sums, tb->h_acc + (size_t)j * n_sums, (size_t)n_sums * sizeof(double));
@@ -135,12 +192,14 @@ static int run_texts(const char *who, RecurNN *net, const u8 *const *texts, cons
   double *sums = want->sums;
   float *const *logp = want->logp;
   u8 *const *guess = want->guess;
-  if (ramd_run_texts_refused(who, net, texts, lens, n_texts, alphabet_len, sums ? (const void *)sums : (const void *)logp)) {
+  /* (the sums form may leave out its sums where it hands back states: the texts are fed and nothing is scored) */
+  const void *result = want->trace ? (const void *)logp : sums ? (const void *)sums : (const void *)want->h_out;
+  if (ramd_run_texts_refused(who, net, texts, lens, n_texts, alphabet_len, result)) {
     return -1;
   }
   const int n_sums = alphabet_len ? net->output_size / alphabet_len : 1;
-  if (sums) {
-    for (size_t q = 0; q < (size_t)n_texts * n_sums; q++) {
+  if (!want->trace) {
+    for (size_t q = 0; sums && q < (size_t)n_texts * n_sums; q++) {
       sums[q] = 0.0;
     }
   } else {
@@ -161,8 +220,18 @@ static int run_texts(const char *who, RecurNN *net, const u8 *const *texts, cons
     fprintf(stderr, "librecur_amd: %s: out of memory planning %d texts\n", who, n_texts);
     return -1;
   }
+  if (ramd_texts_fill_rowless(net, lens, n_texts, plan.n_rows, want->h_in, want->h_out)) {
+    fprintf(stderr, "librecur_amd: %s: out of memory\n", who);
+    texts_plan_free(&plan);
+    return -1;
+  }
   if (plan.n_rows == 0) { /* nothing to score: no device is asked for */
     return 0;
+  }
+  if (!want->trace && !sums) {
+    for (int r = 0; r < plan.n_rows; r++) {
+      plan.skip[r] = INT_MAX; /* fed, never scored */
+    }
   }
   RamdEngine *e = ramd_engine_of(net);
   const int widest = plan.waves[0].nrows;
@@ -183,7 +252,10 @@ static int run_texts(const char *who, RecurNN *net, const u8 *const *texts, cons
   tb.h_off = ramd_zalloc((size_t)widest * sizeof(unsigned long long));
   tb.d_text = ramd_dev_alloc(bytes);
   tb.d_off = ramd_dev_alloc((size_t)widest * sizeof(unsigned long long));
-  if (sums) {
+  if (want->h_in || want->h_out) {
+    tb.h_state = ramd_zalloc((size_t)widest * e->sh.H * sizeof(float));
+  }
+  if (!want->trace) {
     tb.h_acc = ramd_zalloc((size_t)widest * n_sums * sizeof(double));
     tb.d_skip = ramd_dev_alloc((size_t)widest * sizeof(int));
     tb.d_acc = ramd_dev_alloc((size_t)widest * n_sums * sizeof(double));
@@ -208,8 +280,15 @@ static int run_texts(const char *who, RecurNN *net, const u8 *const *texts, cons
   free(tb.h_acc);
   free(tb.h_off_tr);
   free(tb.h_trace);
+  free(tb.h_state);
   texts_plan_free(&plan);
   return 0;
+}
+
+int rnn_amd_run_texts_from(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
+                           int alphabet_len, const float *h_in, float *h_out, double *sums) {
+  const TextsWanted want = {.sums = sums, .h_in = h_in, .h_out = h_out};
+  return run_texts("rnn_amd_run_texts_from", net, texts, lens, skips, n_texts, alphabet_len, &want);
 }
 
 int rnn_amd_run_texts(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips, int n_texts,
@@ -228,8 +307,14 @@ int rnn_amd_run_texts_heads(RecurNN *net, const u8 *const *texts, const int *len
   return run_texts("rnn_amd_run_texts_heads", net, texts, lens, skips, n_texts, alphabet_len, &want);
 }
 
+int rnn_amd_trace_texts_from(RecurNN *net, const u8 *const *texts, const int *lens, int n_texts, int alphabet_len,
+                             const float *h_in, float *h_out, float *const *logp, u8 *const *guess) {
+  const TextsWanted want = {.trace = 1, .logp = logp, .guess = guess, .h_in = h_in, .h_out = h_out};
+  return run_texts("rnn_amd_trace_texts_from", net, texts, lens, NULL, n_texts, alphabet_len, &want);
+}
+
 int rnn_amd_trace_texts(RecurNN *net, const u8 *const *texts, const int *lens, int n_texts, int alphabet_len,
                         float *const *logp, u8 *const *guess) {
-  const TextsWanted want = {.logp = logp, .guess = guess};
+  const TextsWanted want = {.trace = 1, .logp = logp, .guess = guess};
   return run_texts("rnn_amd_trace_texts", net, texts, lens, NULL, n_texts, alphabet_len, &want);
 }

@@ -6,7 +6,9 @@ charmodel-predict.c:288-311).  ``AmdBatchedSet`` drives the additive batched ent
 part 2): the whole set per call, text on the device.  ``run_texts`` scores a list of encoded texts against one net in
 one batched call (rnn_amd_run_texts / _heads), ``sample_texts`` draws a batch of texts from one net in one batched call
 (rnn_amd_sample_texts), ``continue_texts`` continues a batch of prompts (rnn_amd_continue_texts), ``trace_texts`` hands
-back the scorer's figures symbol by symbol (rnn_amd_trace_texts).  ``synthetic_text_np`` is the seeded symbol stream of
+back the scorer's figures symbol by symbol (rnn_amd_trace_texts); ``run_texts_from``, ``trace_texts_from`` and
+``continue_texts_from`` are those with a start state per text and the final states handed back, as numpy arrays
+[n][h_size] (the rnn_amd_*_texts_from calls).  ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
 """
@@ -140,6 +142,91 @@ def continue_texts(lib, net, prompts, seeds, max_len, bias=0.0, stop=-1, alphabe
         raise ValueError("rnn_amd_continue_texts refused the batch or a draw failed (see stderr)")
     assert all(np.all(out[k, lens[k]:max_len] == 0xEE) for k in range(n)), "symbols behind a text's length"
     return [out[k, :lens[k]].copy() for k in range(n)], rng[:n]
+
+
+def _states(net, n, h_in, want_out, in_place):
+    """(h_in array or None, h_out array or None, their pointers) for the _from drivers: states are [n][h_size] float32"""
+    H = net.contents.h_size
+    hin = None
+    if h_in is not None:
+        hin = h_in if in_place else np.ascontiguousarray(h_in, dtype=np.float32)
+        assert hin.dtype == np.float32 and hin.flags.c_contiguous and hin.shape == (n, H), "states are [n][h_size] float32"
+    if in_place:
+        assert hin is not None, "an update in place needs h_in"
+        hout = hin
+    else:
+        hout = np.full((max(n, 1), H), np.nan, np.float32) if want_out else None
+    return hin, hout, None if hin is None else rc.fptr(hin), None if hout is None else rc.fptr(hout)
+
+
+def run_texts_from(lib, net, texts, skips=None, alphabet_len=0, h_in=None, want_out=True, in_place=False, sums=True):
+    """rnn_amd_run_texts_from: run_texts with a start state per text (h_in [n][h_size] float32, None: the net's hidden
+    row) and the texts' final states handed back.  Returns (sums as run_texts returns them, or None with sums=False: the
+    texts are fed and nothing is scored; h_out [n][h_size] float32, or None with want_out=False).  in_place: h_out IS the
+    caller's h_in array, updated where it lies."""
+    keep, ptrs, lens = text_pointers(texts)
+    n = len(keep)
+    sk = None if skips is None else np.ascontiguousarray(skips, dtype=np.int32)
+    assert sk is None or len(sk) == n
+    heads = net.contents.output_size // alphabet_len if alphabet_len else 1
+    got = np.full((n, heads), np.nan) if sums else None
+    hin, hout, hip, hop = _states(net, n, h_in, want_out, in_place)
+    r = lib.rnn_amd_run_texts_from(net, ptrs, rc.iptr(lens), None if sk is None else rc.iptr(sk), n, alphabet_len, hip, hop,
+                                   got.ctypes.data_as(C.POINTER(C.c_double)) if sums else None)
+    if r != 0:
+        raise ValueError("rnn_amd_run_texts_from refused the batch (see stderr)")
+    if got is not None and not alphabet_len:
+        got = got[:, 0]
+    return got, None if hout is None else hout[:n]
+
+
+def trace_texts_from(lib, net, texts, alphabet_len=0, guesses=True, h_in=None, want_out=True, in_place=False):
+    """rnn_amd_trace_texts_from: trace_texts with a start state per text and the final states handed back.  Returns (what
+    trace_texts returns, h_out [n][h_size] float32 or None)."""
+    keep, ptrs, lens = text_pointers(texts)
+    heads = net.contents.output_size // alphabet_len if alphabet_len else 1
+    n = len(keep)
+    counts = [max(len(t) - 1, 0) * heads for t in keep]
+    lp = [np.full(c + TRACE_GUARD, np.nan, np.float32) for c in counts]
+    gs = [np.full(c + TRACE_GUARD, 0xEE, np.uint8) for c in counts] if guesses else None
+    lpp = (rc.c_float_p * max(n, 1))(*[rc.fptr(a) for a in lp])
+    gsp = (rc.c_u8_p * max(n, 1))(*[rc.u8ptr(a) for a in gs]) if guesses else None
+    hin, hout, hip, hop = _states(net, n, h_in, want_out, in_place)
+    r = lib.rnn_amd_trace_texts_from(net, ptrs, rc.iptr(lens), n, alphabet_len, hip, hop, lpp, gsp)
+    if r != 0:
+        raise ValueError("rnn_amd_trace_texts_from refused the batch (see stderr)")
+    assert all(np.all(np.isnan(a[c:])) for a, c in zip(lp, counts)), "log2 likelihoods behind a text's trace"
+    assert all(not np.any(np.isnan(a[:c])) for a, c in zip(lp, counts)), "a traced step was not written"
+    assert not guesses or all(np.all(a[c:] == 0xEE) for a, c in zip(gs, counts)), "guesses behind a text's trace"
+    return [(lp[k][:counts[k]].reshape(-1, heads).copy(),
+             gs[k][:counts[k]].reshape(-1, heads).copy() if guesses else None) for k in range(n)], \
+        None if hout is None else hout[:n]
+
+
+def continue_texts_from(lib, net, prompts, seeds, max_len, bias=0.0, stop=-1, alphabet_len=0, head=0, h_in=None, rng_in=None,
+                        want_out=True, in_place=False):
+    """rnn_amd_continue_texts_from: continue_texts with a start state per prompt (h_in) and, with rng_in (a uint64 array
+    [n][4] as the drivers return generators; seeds may then be None), a start generator per prompt; the final states are
+    handed back.  Returns (the continuations, the generators afterwards, h_out [n][h_size] float32 or None)."""
+    keep, ptrs, plens = text_pointers(prompts)
+    n = len(keep)
+    sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+    gi = None if rng_in is None else np.ascontiguousarray(rng_in, dtype=np.uint64)
+    assert sd is None or len(sd) == n
+    assert gi is None or gi.shape == (n, 4)
+    out = np.full((max(n, 1), max(max_len, 1)), 0xEE, np.uint8)
+    lens = np.full(max(n, 1), -1, np.int32)
+    rng = np.zeros((max(n, 1), 4), np.uint64)
+    hin, hout, hip, hop = _states(net, n, h_in, want_out, in_place)
+    r = lib.rnn_amd_continue_texts_from(net, ptrs, rc.iptr(plens),
+                                        None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                        None if gi is None else gi.ctypes.data_as(C.POINTER(rc.RandCtx)), n, max_len, bias,
+                                        stop, alphabet_len, head, hip, hop, rc.u8ptr(out), rc.iptr(lens),
+                                        rng.ctypes.data_as(C.POINTER(rc.RandCtx)))
+    if r != 0:
+        raise ValueError("rnn_amd_continue_texts_from refused the batch or a draw failed (see stderr)")
+    assert all(np.all(out[k, lens[k]:max_len] == 0xEE) for k in range(n)), "symbols behind a text's length"
+    return [out[k, :lens[k]].copy() for k in range(n)], rng[:n], None if hout is None else hout[:n]
 
 
 class ApiSet:

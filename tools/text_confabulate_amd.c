@@ -3,7 +3,7 @@
  * sample characters from its predictions.
  *
  *   text_confabulate_amd -f NET [-B bias] [-n chars] [-p prefix] [-u until_char]
- *                        [-w wait_for_char] [-r seed] [-N passages] [-P prompts_file]
+ *                        [-w wait_for_char] [-r seed] [-N passages] [-P prompts_file [-e]]
  *
  * -N n: n passages, one per line, each from the (primed) net's state with a generator of its own seeded seed, seed + 1,
  * ..., all drawn in one batched device run (rnn_amd_char_confabulate_texts).  Without -N the one passage is drawn with the
@@ -12,6 +12,9 @@
  * lines x n rows in one batched device run (rnn_amd_char_continue_texts), row i -- the lines in order, a line's n
  * continuations next to one another -- with a generator seeded seed + i.  One output line per row: the prompt, then its
  * continuation.  -P does not go with -w either.
+ * -P FILE -e: the same lines, each also scored: every prompt is fed once, scored on its way, and continued n times from the
+ * state behind it (rnn_amd_char_score_and_continue_texts).  Every output line is prefixed by its prompt's bits per symbol
+ * and a tab.
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -36,7 +39,7 @@ static void seed_rng(rand_ctx *x, u64 seed) {
 
 /* -P: the non-empty lines of `file` n times over, continued in one call; one line per row on stdout */
 static int continue_prompts(RecurNN *net, RnnCharAlphabet *alphabet, const char *file, int n, long long seed, int chars,
-                            float bias, int stop_point, int byte_len) {
+                            float bias, int stop_point, int byte_len, int scored) {
   FILE *f = fopen(file, "r");
   if (!f) {
     fprintf(stderr, "cannot read the prompts in %s\n", file);
@@ -68,10 +71,24 @@ static int continue_prompts(RecurNN *net, RnnCharAlphabet *alphabet, const char 
     seeds[i] = (u64)seed + (u64)i;
     lines[i] = malloc(byte_len);
   }
-  int r = rnn_amd_char_continue_texts(net, alphabet, of_row, prompt_bytes, seeds, rows, chars, bias, stop_point, lines,
-                                      byte_len, bytes);
+  double *entropy = calloc(n_lines + 1, sizeof(double));
+  int r;
+  if (scored) { /* a prompt per line, not per row: each is fed once */
+    for (size_t l = 0; l < n_lines; l++) {
+      prompt_bytes[l] = (int)strlen(prompts[l]);
+    }
+    r = n < 1 ? 0 : rnn_amd_char_score_and_continue_texts(net, alphabet, (const char *const *)prompts, prompt_bytes, seeds,
+                                                          (int)n_lines, n, chars, bias, stop_point, lines, byte_len, bytes,
+                                                          entropy);
+  } else {
+    r = rnn_amd_char_continue_texts(net, alphabet, of_row, prompt_bytes, seeds, rows, chars, bias, stop_point, lines,
+                                    byte_len, bytes);
+  }
   for (int i = 0; i < rows; i++) {
     if (r == 0) {
+      if (scored) {
+        printf("%.6f\t", entropy[i / n]);
+      }
       fputs(of_row[i], stdout);
       fputs(lines[i], stdout);
       fputs("\n", stdout);
@@ -87,15 +104,16 @@ static int continue_prompts(RecurNN *net, RnnCharAlphabet *alphabet, const char 
   free(seeds);
   free(lines);
   free(bytes);
+  free(entropy);
   return r ? 1 : 0;
 }
 
 int main(int argc, char **argv) {
   const char *netfile = NULL, *prefix = NULL, *until = NULL, *wait_for = NULL, *prompts_file = NULL;
   float bias = 0;
-  int chars = 72, opt, passages = -1;
+  int chars = 72, opt, passages = -1, scored = 0;
   long long seed = 2;
-  while ((opt = getopt(argc, argv, "f:B:n:p:u:w:r:N:P:")) != -1) {
+  while ((opt = getopt(argc, argv, "f:B:n:p:u:w:r:N:P:e")) != -1) {
     switch (opt) {
     case 'f': netfile = optarg; break;
     case 'B': bias = atof(optarg); break;
@@ -106,6 +124,7 @@ int main(int argc, char **argv) {
     case 'r': seed = atoll(optarg); break;
     case 'N': passages = atoi(optarg); break;
     case 'P': prompts_file = optarg; break;
+    case 'e': scored = 1; break;
     default: fprintf(stderr, "usage: %s -f NET [-B bias] [-n chars] [-p prefix]\n", argv[0]); return 2;
     }
   }
@@ -135,7 +154,8 @@ int main(int argc, char **argv) {
   int stop_point = until ? rnn_char_get_codepoint(alphabet, until) : -1;
   int start_point = wait_for ? rnn_char_get_codepoint(alphabet, wait_for) : -1;
   if (prompts_file) {
-    int r = continue_prompts(net, alphabet, prompts_file, passages >= 0 ? passages : 1, seed, chars, bias, stop_point, byte_len);
+    int r = continue_prompts(net, alphabet, prompts_file, passages >= 0 ? passages : 1, seed, chars, bias, stop_point, byte_len,
+                             scored);
     free(t);
     rnn_char_free_alphabet(alphabet);
     rnn_delete_net(net);
