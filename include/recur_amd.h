@@ -762,6 +762,46 @@ int rnn_amd_continue_texts_from(RecurNN *net, const u8 *const *prompts, const in
                                 const rand_ctx *rng_in, int n_texts, int max_len, float bias, int stop_point,
                                 int alphabet_len, int head, const float *h_in, float *h_out,
                                 u8 *out /* [n_texts][max_len] */, int *out_lens, rand_ctx *rng_out /* [n_texts] or NULL */);
+/* Many DENSE FEATURE SEQUENCES against one net in one batched device run: using a trained classifier, as the batched
+ * text calls use a trained character model.  Sequence k is n_frames[k] rows of net->input_size floats at inputs[k], row
+ * stride ld_inputs floats.  What is written for it is what this loop writes on a forward-only clone c_k of `net`
+ * (emit_opinions' loop body, gstclassify.c:2259-2292, for one channel):
+ *     for every frame t: answer = rnn_opinion(c_k, inputs[k] + t * ld_inputs, 0);
+ *         for every class group g: winners[k][t * n_groups + g] =
+ *             softmax_best_guess(error + group_offset[g], answer + group_offset[g], group_size[g]);
+ *         answers[k][t * output_size + i] = -error[i] for a column i inside a group, answer[i] for any other
+ * that is: a column inside a group gets its softmax probability within the group (badmaths.h:71-111: the shift,
+ * fast_expf, the sum in index order, the division -- the number gstclassify publishes), a column in no group the raw
+ * output (rnn_amd_classify_parse_classes counts the commas of the class string in its offsets, so such columns exist),
+ * and with n_groups == 0 every column is rnn_opinion's answer: the plain forward run of rnnca and parrot.  A winner is the
+ * index within its group of the largest probability after the division, the lowest index among equals.
+ * answers[k] is [n_frames[k]][net->output_size], winners[k] is [n_frames[k]][n_groups] bytes; winners may be NULL (none
+ * are taken).  answers[k], winners[k] and inputs[k] of a sequence without a frame may be NULL; nothing is written for it,
+ * nor behind the entries of any other.  Every entry is written exactly once.
+ * States are the _from text calls': c_k starts from net's hidden row at the moment of the call (h_in NULL) or from h_in[k],
+ * a row of net->h_size floats laid out as net->hidden_layer whose elements [1, hidden_size] carry the state; h_out[k]
+ * (h_out may be NULL) is c_k's hidden row after its last frame, for a sequence without a frame its start state; h_out may
+ * be h_in.  A recording cut into pieces run by successive calls joined through h_out -> h_in is the recording run in one
+ * call (to the bit where the passes run with the same row counts, else to rounding, as said above for the texts).
+ * There is no noise and no generator is touched; `net` -- host and device copies, hidden row, what it computes next --
+ * is left exactly as it was.
+ * The rows go longest first in waves of up to 256 (the layout of rnn_amd_run_texts: n frames are a text of n + 1
+ * symbols).  A frame costs 4 * input_size bytes, so a wave is STAGED IN SEGMENTS of at most segment_frames frames: per
+ * segment one upload of the frames of the rows that still run, the launches, one copy back of the segment's answers and
+ * one of its winners, one device synchronisation.  The staging buffers -- on the device and as many bytes on the host --
+ * hold one segment: the sum over the first wave's rows of min(n_frames, segment_frames), times 4 * input_size bytes of
+ * frames, 4 * output_size of answers and n_groups of winners.  segment_frames <= 0: the default, the largest count for
+ * which 256 rows' frames stay within 2 MiB (2 MiB / (1024 * input_size), at least 1; 64 frames at 32 features).  The
+ * segment size changes no bit of the result.
+ * Returns 0; where no sequence has a frame it returns 0 at once (h_out filled by the host) and asks for no device.  Returns
+ * -1 with a message on stderr and nothing computed, before anything needs a device: a NULL net; n_seqs, n_groups or an
+ * n_frames[k] below 0; a net with a bottom layer (as rnn_amd_run_texts); a group with no class, one that leaves the
+ * output row or overlaps another; ld_inputs < net->input_size; a NULL inputs, n_frames or answers with n_seqs > 0, a
+ * NULL group_offset or group_size with n_groups > 0, a NULL inputs[k], answers[k] or (with winners) winners[k] for a
+ * sequence with a frame; winners with n_groups == 0 or with a group of more than 256 classes. */
+int rnn_amd_run_sequences(RecurNN *net, const float *const *inputs, const int *n_frames, int n_seqs, int ld_inputs,
+                          int n_groups, const int *group_offset, const int *group_size, const float *h_in, float *h_out,
+                          int segment_frames, float *const *answers, u8 *const *winners);
 /* Block until all queued device work of the library has finished. */
 void rnn_amd_synchronize(void);
 

@@ -261,6 +261,8 @@ AMD_API = {
                                          C.POINTER(C.c_double)]),
     "rnn_amd_trace_texts_from": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, C.c_int, C.c_int, c_float_p, c_float_p,
                                            C.POINTER(c_float_p), C.POINTER(c_u8_p)]),
+    "rnn_amd_run_sequences": (C.c_int, [NetP, C.POINTER(c_float_p), c_int_p, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p,
+                                        c_float_p, c_float_p, C.c_int, C.POINTER(c_float_p), C.POINTER(c_u8_p)]),
     "rnn_amd_continue_texts_from": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, C.POINTER(C.c_uint64), C.POINTER(RandCtx),
                                               C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
                                               c_u8_p, c_int_p, C.POINTER(RandCtx)]),

@@ -803,6 +803,71 @@ __global__ __launch_bounds__(64 * TS_WAVES) void k_texts_trace(View v, TextsTrac
                        nullptr, red);
 }
 
+// The one launch between two forward passes of rnn_amd_run_sequences (seqs_api.c): a wave of dense feature sequences on
+// forward-only state rows, one workgroup of 256 threads per row, the rows' frames of the current segment staged behind
+// one another (seqs_plan.h: row j's frame i at in[(off[j] + i) * input_size], its answers at ans[(off[j] + i) *
+// output_size], its winners at win[(off[j] + i) * n_groups]; t_score and t_feed count within the segment).  Two halves:
+//   score frame t_score, rows [0, a_score): emit_opinions' loop body (gstclassify.c:2273-2280) on the output row the
+//     forward pass just left.  A wave per class group, the groups shared out over the waves, lane-strided so that a group
+//     may be wider than the wave: softmax of out[goff[g] .. + gsize[g]) (badmaths.h:71-111: the shift, fast_expf, the sum in
+//     the reference's order), every lane stores ex[i] / sum for its classes -- what softmax_best_guess stores, negated
+//     back -- and offers it to the best guess (badmaths.h:113-141: the largest after the division, the lowest index among
+//     equals), which lane 0 stores as a byte when winners are wanted.  The columns in no group (gap[n_gap], in ascending
+//     order; with no groups every column) are copied raw by the whole workgroup.  Every entry has one writer and is
+//     written once: no atomics and no memset.
+//   feed frame t_feed, rows [0, a_feed): the input row of the next forward pass -- assemble_input_row with the staged
+//     frame as the dense row, the emergency soft clip included; the hidden values as the text kernels take them
+//     (texts_feed_hidden).
+// a_score == 0: the first launch of a segment, which only feeds; a_feed == 0: its last, which only scores.
+struct SeqsStep {
+  const float *in;               /* the segment's staged frames                    */
+  float *ans;                    /* the segment's answers                          */
+  unsigned char *win;            /* the segment's winners, or nullptr              */
+  const unsigned long long *off; /* [rows] where row j's frames start, in frames   */
+  const int *goff, *gsize;       /* [n_groups] the class groups                    */
+  const int *gap;                /* [n_gap] the columns in no group                */
+  const float *hid0;             /* the hidden row of the first feed, or nullptr   */
+  int row0;                      /* state row of the wave's row 0 (forward-only)   */
+  int n_groups, n_gap, stride;   /* stride: a wave's floats of LDS                 */
+  int t_score, a_score, t_feed, a_feed;
+};
+__global__ __launch_bounds__(64 * TS_WAVES) void k_seqs_step(View v, SeqsStep p) {
+  extern __shared__ float tex[]; /* [TS_WAVES][stride] exponentials */
+  __shared__ float red[4];
+  const RamdShape &s = v.sh;
+  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const size_t at = (size_t)p.off[j];
+  if (j < p.a_score) {
+    const float *out = v.b.out + (size_t)r * s.O;
+    const size_t slot = at + (size_t)p.t_score;
+    float *dst = p.ans + slot * (size_t)s.output_size;
+    for (int c = threadIdx.x; c < p.n_gap; c += 64 * TS_WAVES) dst[p.gap[c]] = out[p.gap[c]];
+    float *ex = tex + wave * p.stride;
+    for (int g = wave; g < p.n_groups; g += TS_WAVES) {
+      const int o = p.goff[g], n = p.gsize[g];
+      const float *src = out + o;
+      const float adj = softmax_shift_of(src, n, lane);
+      for (int i = lane; i < n; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
+      FenceOneWave{}();
+      const float sum = ordered_sum(ex, n);
+      BestGuess best;
+      for (int i = lane; i < n; i += 64) { /* (consecutive lanes, consecutive floats) */
+        const float e = ex[i] / sum;
+        dst[o + i] = e;
+        best.offer(e, i);
+      }
+      if (p.win) {
+        wave_best_guess(best);
+        if (lane == 0) p.win[slot * (size_t)p.n_groups + g] = (unsigned char)best.i;
+      }
+      FenceOneWave{}(); /* before this wave's next group rewrites ex */
+    }
+  }
+  if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
+    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_DENSE, 0,
+                       p.in + (at + (size_t)p.t_feed) * (size_t)s.input_size, red);
+}
+
 // The one launch between two forward passes of rnn_amd_sample_texts (sample_api.c): N texts drawn from one net side by
 // side, a state row each.  One workgroup of 256 threads per row (assemble_input_row's), two halves:
 //   draw (not in a wave's first launch, t == 0; not for a row that is done): wave 0 turns the row's slice of the output
@@ -1089,6 +1154,36 @@ extern "C" void ramd_launch_texts_trace(ramd_stream_t st_, const RamdShape *sh, 
   if (shm > 64 * 1024) raise_lds_limit<k_texts_trace>(160 * 1024 - 64);
   TextsTrace p = {text, off, off_tr, trace, guess, hid0, row0, alphabet_len, n_sums, t_score, a_score, t_feed, a_feed};
   RAMD_LAUNCH(k_texts_trace, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
+}
+
+extern "C" void ramd_launch_seqs_step(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
+                                      const float *in, const unsigned long long *off, float *ans, unsigned char *win,
+                                      int n_groups, int largest, const int *goff, const int *gsize, const int *gap,
+                                      int n_gap, const float *hid0, int t_score, int a_score, int t_feed, int a_feed) {
+  const int rows = a_score > a_feed ? a_score : a_feed;
+  if (rows < 1) return;
+  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
+    fprintf(stderr, "librecur_amd: ramd_launch_seqs_step: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
+    abort();
+  }
+  if (n_groups < 0 || n_gap < 0 || largest < 0 || largest > sh->output_size || n_gap > sh->output_size ||
+      (n_groups > 0 && (!goff || !gsize || largest < 1)) || (n_gap > 0 && !gap) || (win && n_groups < 1) ||
+      (a_score > 0 && (t_score < 0 || !ans)) || (a_feed > 0 && (t_feed < 0 || !in)) || !off) {
+    fprintf(stderr, "librecur_amd: ramd_launch_seqs_step: %d groups of up to %d and %d other columns in a row of %d, "
+                    "steps %d and %d\n", n_groups, largest, n_gap, sh->output_size, t_score, t_feed);
+    abort();
+  }
+  hipStream_t st = (hipStream_t)st_;
+  View v = make_view(sh, b);
+  const int stride = (largest + 3) & ~3;
+  const size_t shm = (size_t)TS_WAVES * stride * sizeof(float);
+  if (shm > 160 * 1024 - 64) {
+    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", largest);
+    abort();
+  }
+  if (shm > 64 * 1024) raise_lds_limit<k_seqs_step>(160 * 1024 - 64);
+  SeqsStep p = {in, ans, win, off, goff, gsize, gap, hid0, row0, n_groups, n_gap, stride, t_score, a_score, t_feed, a_feed};
+  RAMD_LAUNCH(k_seqs_step, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
 }
 
 extern "C" void ramd_launch_texts_sample(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,

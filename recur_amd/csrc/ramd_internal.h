@@ -259,6 +259,19 @@ void ramd_launch_texts_trace(ramd_stream_t st, const RamdShape *sh, const RamdBu
                              const unsigned char *text, const unsigned long long *off, const unsigned long long *off_tr,
                              float *trace, unsigned char *guess, const float *hid0, int alphabet_len, int n_sums,
                              int t_score, int a_score, int t_feed, int a_feed);
+/* the launch between two forward passes of rnn_amd_run_sequences, for a wave of dense sequences on forward-only state
+ * rows row0 ... and one segment of their frames (seqs_plan.h; off[row] is where the row's frames start in the segment's
+ * staging buffers, in frames; t_score and t_feed count within the segment): for the wave's first a_score rows the
+ * answers of frame t_score into ans[(off[row] + t_score) * output_size ...] -- the softmax probability within its group
+ * for a column of one of the n_groups class groups (goff, gsize; `largest` the largest size), the raw output for the
+ * n_gap columns listed in gap -- and, with win != NULL, softmax_best_guess's pick per group as a byte at
+ * win[(off[row] + t_score) * n_groups + group]; for its first a_feed rows the input row of the next forward pass from the
+ * staged frame in[(off[row] + t_feed) * input_size ...] on the row's hidden values, or on hid0's when that is not NULL.
+ * All pointers are device pointers.  a_score or a_feed may be 0.  Every entry has one writer and is written once. */
+void ramd_launch_seqs_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, const float *in,
+                           const unsigned long long *off, float *ans, unsigned char *win, int n_groups, int largest,
+                           const int *goff, const int *gsize, const int *gap, int n_gap, const float *hid0, int t_score,
+                           int a_score, int t_feed, int a_feed);
 /* the launch between two forward passes of rnn_amd_sample_texts, launch t = 0 .. max_len of a wave of `rows` texts on
  * forward-only state rows row0 ...: for t > 0 draws symbol t - 1 of every row that is not done from head `head` of
  * alphabet_len outputs of its output row (sample_rule.h: the biased clamped softmax, a draw with rng[row], or the best

@@ -8,7 +8,9 @@ one batched call (rnn_amd_run_texts / _heads), ``sample_texts`` draws a batch of
 (rnn_amd_sample_texts), ``continue_texts`` continues a batch of prompts (rnn_amd_continue_texts), ``trace_texts`` hands
 back the scorer's figures symbol by symbol (rnn_amd_trace_texts); ``run_texts_from``, ``trace_texts_from`` and
 ``continue_texts_from`` are those with a start state per text and the final states handed back, as numpy arrays
-[n][h_size] (the rnn_amd_*_texts_from calls).  ``synthetic_text_np`` is the seeded symbol stream of
+[n][h_size] (the rnn_amd_*_texts_from calls); ``run_sequences`` runs a list of dense feature sequences against one net in
+one batched call (rnn_amd_run_sequences): per frame the class groups' probabilities and winners, with states in and out
+in the same form.  ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
 """
@@ -227,6 +229,40 @@ def continue_texts_from(lib, net, prompts, seeds, max_len, bias=0.0, stop=-1, al
         raise ValueError("rnn_amd_continue_texts_from refused the batch or a draw failed (see stderr)")
     assert all(np.all(out[k, lens[k]:max_len] == 0xEE) for k in range(n)), "symbols behind a text's length"
     return [out[k, :lens[k]].copy() for k in range(n)], rng[:n], None if hout is None else hout[:n]
+
+
+def run_sequences(lib, net, seqs, groups=None, h_in=None, want_out=True, in_place=False, segment_frames=0, winners=True):
+    """rnn_amd_run_sequences for a list of float32 arrays [frames][input_size] (a sequence may have no frame): per
+    sequence (answers [frames][output_size] float32, winners [frames][n_groups] uint8 or None) and h_out [n][h_size]
+    float32 (None with want_out=False).  groups: a list of (offset, size) class groups, None or empty for the raw outputs
+    (no winners then).  h_in, want_out, in_place as in the _from text drivers.  Every array is allocated with guard
+    entries behind it (NaN, 0xEE), which must come back untouched, and every entry in front of them must be written."""
+    n = len(seqs)
+    isz, osz = net.contents.input_size, net.contents.output_size
+    keep = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1, isz) for s in seqs]
+    frames = np.array([len(s) for s in keep], np.int32)
+    groups = list(groups or [])
+    ng = len(groups)
+    winners = winners and ng > 0
+    goff = np.array([g[0] for g in groups], np.int32)
+    gsize = np.array([g[1] for g in groups], np.int32)
+    ans = [np.full(int(f) * osz + TRACE_GUARD, np.nan, np.float32) for f in frames]
+    win = [np.full(int(f) * ng + TRACE_GUARD, 0xEE, np.uint8) for f in frames] if winners else None
+    inp = (rc.c_float_p * max(n, 1))(*[rc.fptr(s) if len(s) else None for s in keep])
+    ansp = (rc.c_float_p * max(n, 1))(*[rc.fptr(a) for a in ans])
+    winp = (rc.c_u8_p * max(n, 1))(*[rc.u8ptr(a) for a in win]) if winners else None
+    hin, hout, hip, hop = _states(net, n, h_in, want_out, in_place)
+    r = lib.rnn_amd_run_sequences(net, inp, rc.iptr(frames), n, isz, ng, rc.iptr(goff) if ng else None,
+                                  rc.iptr(gsize) if ng else None, hip, hop, segment_frames, ansp, winp)
+    if r != 0:
+        raise ValueError("rnn_amd_run_sequences refused the batch (see stderr)")
+    counts = [int(f) * osz for f in frames]
+    assert all(np.all(np.isnan(a[c:])) for a, c in zip(ans, counts)), "answers behind a sequence's last frame"
+    assert all(not np.any(np.isnan(a[:c])) for a, c in zip(ans, counts)), "an answer was not written"
+    assert not winners or all(np.all(a[int(f) * ng:] == 0xEE) for a, f in zip(win, frames)), "winners behind a sequence's last frame"
+    return [(ans[k][:counts[k]].reshape(-1, osz).copy(),
+             win[k][:int(frames[k]) * ng].reshape(-1, ng).copy() if winners else None) for k in range(n)], \
+        None if hout is None else hout[:n]
 
 
 class ApiSet:
