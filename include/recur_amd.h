@@ -802,6 +802,54 @@ int rnn_amd_continue_texts_from(RecurNN *net, const u8 *const *prompts, const in
 int rnn_amd_run_sequences(RecurNN *net, const float *const *inputs, const int *n_frames, int n_seqs, int ld_inputs,
                           int n_groups, const int *group_offset, const int *group_size, const float *h_in, float *h_out,
                           int segment_frames, float *const *answers, u8 *const *winners);
+/* RNNCA'S AUTOMATON played on the device, many frames in one run: the batched form of fill_frame (gstrnnca.c:805-831).
+ * The grid is width * height cells, cell (cx, cy) at index cy * width + cx; a frame is three planes of that many bytes
+ * (Y, Cb, Cr).  Every cell is a forward-only clone of `net`.  frames[t] is what fill_frame leaves in play_frame after its
+ * (t + 1)-th call, frame -1 being `seed`:
+ *     for every cell: fill_net_inputs from frame t - 1 -- the luma of the cell's len_y neighbours at offsets_y, (Cb, Cr) of
+ *         its len_c neighbours at offsets_c, each byte times (1.0f / 255.0f), then the position cx * 1.0f / width,
+ *         cy * 1.0f / height and with len_pos == 3 a third input (gstrnnca.c:689, evaluated in double); a neighbour beyond
+ *         the grid is the clamped one (edges != 0) or the one a SINGLE wrap reaches (edges == 0);
+ *         answer = rnn_opinion(clone, inputs, 0); fast_sigmoid_array(answer, answer, 3)
+ *     for every cell: the bytes of frame t = the truncations of answer[0 .. 2] * 255.9f
+ * (a scaled value outside [0, 256), which C leaves undefined, stores 0 if it is NaN or negative and 255 otherwise).
+ * rnn_amd_automaton_parse_offsets expands an offset pattern such as the default "Y00120111C0111" as setup_inputs does
+ * (gstrnnca.c:375-439; the default gives 17 Y and 8 C offsets: 17 + 2 * 8 + 2 = 35 inputs) into arrays of max_pairs
+ * (dx, dy) pairs each; unknown characters are skipped.  It returns 0, or -1 with a line on stderr when a list does not
+ * fit (nothing is written behind the arrays) or an argument is NULL.
+ * check_for_stasis (gstrnnca.c:764-802) draws from the caller's generator and may rewrite the frame: it stays with the
+ * caller, between calls, on frames[last] before it becomes the next call's seed.
+ * States are the _from text calls': cell k starts from net's hidden row at the moment of the call (h_in NULL) or from
+ * h_in[k], a row of net->h_size floats laid out as net->hidden_layer whose elements [1, hidden_size] carry the state;
+ * h_out[k] (h_out may be NULL, or h_in) is the cell's hidden row after the last frame.  A run cut into two calls, joined
+ * by frames[last] as the next seed and h_out -> h_in, is the uncut run, bit for bit.  The states move in one copy each way.
+ * There is no noise and no generator is touched; `net` -- host and device copies, hidden row, what it computes next --
+ * is left exactly as it was.
+ * All width * height rows run in lock step (there are no waves: a cell reads its neighbours), between two forward passes
+ * one launch paints the frame and builds the next input rows, and the host is not visited per frame: the frames stay on
+ * the device and come back in one copy with one synchronisation per SEGMENT of at most segment_frames frames
+ * (segment_frames <= 0: the default, the largest count whose bytes stay within 16 MiB, at least 1; 404 frames of
+ * 144 x 96).  The device buffer holds one segment.  The segment size changes no bit.
+ * Returns 0; n_frames == 0 returns 0 at once, asks for no device and with h_in given copies the states to h_out on the
+ * host.  Returns -1 with a line on stderr and nothing computed, before anything needs a device: a NULL net, ca or seed, or
+ * NULL frames with n_frames > 0; n_frames < 0; width or height < 1 or a product beyond int; len_y or len_c < 0 or a NULL
+ * list with a positive length; len_pos other than 2 or 3; net->input_size != len_y + 2 * len_c + len_pos;
+ * net->output_size < 3; a net with a bottom layer (as rnn_amd_run_texts); with edges == 0 an offset with |dx| >= width or
+ * |dy| >= height, which the reference's single wrap would take out of the plane. */
+typedef struct RnnAmdAutomaton {
+  int width, height;
+  const int *offsets_y; /* (dx, dy) pairs */
+  int len_y;
+  const int *offsets_c;
+  int len_c;
+  int len_pos; /* 2 or 3 */
+  int edges;   /* non-zero: clamp; 0: wrap once */
+} RnnAmdAutomaton;
+int rnn_amd_automaton_parse_offsets(const char *pattern, int *offsets_y, int *len_y, int *offsets_c, int *len_c,
+                                    int max_pairs);
+int rnn_amd_run_automaton(RecurNN *net, const RnnAmdAutomaton *ca, const u8 *seed /* [3][height * width] */, int n_frames,
+                          const float *h_in, float *h_out /* [height * width][h_size] */, int segment_frames,
+                          u8 *frames /* [n_frames][3][height * width] */);
 /* Block until all queued device work of the library has finished. */
 void rnn_amd_synchronize(void);
 

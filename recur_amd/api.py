@@ -139,6 +139,12 @@ class AmdStats(C.Structure):
 
 NetP = C.POINTER(RecurNN)
 
+
+class Automaton(C.Structure):  # RnnAmdAutomaton (include/recur_amd.h)
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("offsets_y", c_int_p), ("len_y", C.c_int),
+                ("offsets_c", c_int_p), ("len_c", C.c_int), ("len_pos", C.c_int), ("edges", C.c_int)]
+
+
 # flags / enums (include/recur_amd.h)
 FLAG_OWN_BPTT = 1
 FLAG_OWN_WEIGHTS = 2
@@ -263,6 +269,8 @@ AMD_API = {
                                            C.POINTER(c_float_p), C.POINTER(c_u8_p)]),
     "rnn_amd_run_sequences": (C.c_int, [NetP, C.POINTER(c_float_p), c_int_p, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p,
                                         c_float_p, c_float_p, C.c_int, C.POINTER(c_float_p), C.POINTER(c_u8_p)]),
+    "rnn_amd_automaton_parse_offsets": (C.c_int, [C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, C.c_int]),
+    "rnn_amd_run_automaton": (C.c_int, [NetP, C.POINTER(Automaton), c_u8_p, C.c_int, c_float_p, c_float_p, C.c_int, c_u8_p]),
     "rnn_amd_continue_texts_from": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, C.POINTER(C.c_uint64), C.POINTER(RandCtx),
                                               C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
                                               c_u8_p, c_int_p, C.POINTER(RandCtx)]),

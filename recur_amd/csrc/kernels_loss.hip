@@ -13,6 +13,7 @@ __device__ unsigned long long g_tt_stamps[16];
 #include "fwd_plan.h"
 #include "sample_rule.h"
 #include "continue_rule.h"
+#include "automaton_rule.h"
 BND_DECL(g_bnd_top, ramd_bnd_top_stamps)
 #pragma clang fp contract(off)
 
@@ -868,6 +869,68 @@ __global__ __launch_bounds__(64 * TS_WAVES) void k_seqs_step(View v, SeqsStep p)
                        p.in + (at + (size_t)p.t_feed) * (size_t)s.input_size, red);
 }
 
+// The one launch between two forward passes of rnn_amd_run_automaton (automaton_api.c): rnnca's fill_frame
+// (gstrnnca.c:805-831) with a forward-only state row per cell, all width * height of them in lock step.  One workgroup of
+// 256 threads per cell (assemble_input_row's), the rule from automaton_rule.h, two halves:
+//   paint (paint != nullptr; not in a call's first launch): the cell's three outputs, which the forward pass just left in
+//     its out row, through the level rule into the cell's byte of the three planes of the frame at `paint`.  Three threads,
+//     a byte each: one writer per byte, no atomics and no memset.
+//   feed (feed != 0; not in a call's last launch): the cell's dense input row into LDS -- the levels of its neighbours in
+//     the frame before, the position -- and assemble_input_row with it, the emergency soft clip included; the hidden values
+//     as the text kernels take them (texts_feed_hidden).
+// A cell's feed needs its neighbours' levels of the very frame this launch paints, and those bytes are other workgroups'
+// writes of this launch: reading them back would be a race.  So the feed half does not read the frame: it reads the
+// neighbours' OUT rows, which no workgroup of this launch writes, and applies the same level function -- at most
+// len_y + 2 * len_c small evaluations per cell, and the same byte as the one painted because the rule is stated once.
+// Only a call's first launch (seed != nullptr) gathers bytes: the seed frame's, which no launch writes.
+struct AutomatonStep {
+  AutomatonRule g;            /* the grid; the offset lists are device arrays            */
+  const unsigned char *seed;  /* [3][cells] the frame the first feed gathers from, or nullptr: from the out rows */
+  unsigned char *paint;       /* [3][cells] the frame to paint, or nullptr                */
+  const float *hid0;          /* the hidden row of the first feed, or nullptr             */
+  int row0;                   /* state row of cell 0 (forward-only)                       */
+  int feed;
+};
+struct AutomatonExp {
+  __device__ __forceinline__ float operator()(float x) const { return fast_expf_dev(x); }
+};
+struct AutomatonSeedLevels { /* the frame before is bytes in memory */
+  const unsigned char *frame;
+  int cells;
+  __device__ __forceinline__ unsigned char operator()(int plane, int cell) const {
+    return frame[(size_t)plane * cells + cell];
+  }
+};
+struct AutomatonOutLevels { /* the frame before is what the cells' out rows paint */
+  const float *out; /* cell 0's out row */
+  int O;
+  __device__ __forceinline__ unsigned char operator()(int plane, int cell) const {
+    return automaton_level(out[(size_t)cell * O + plane], AutomatonExp{});
+  }
+};
+__global__ __launch_bounds__(256) void k_automaton_step(View v, AutomatonStep p) {
+  extern __shared__ float cell_in[]; /* [input_size] the cell's dense input row */
+  __shared__ float red[4];
+  const RamdShape &s = v.sh;
+  const int j = blockIdx.x, r = p.row0 + j;
+  const int cells = p.g.width * p.g.height;
+  const float *out0 = v.b.out + (size_t)p.row0 * s.O;
+  if (p.paint && threadIdx.x < 3)
+    p.paint[(size_t)threadIdx.x * cells + j] = automaton_level(out0[(size_t)j * s.O + threadIdx.x], AutomatonExp{});
+  if (p.feed) { /* (the whole workgroup: barriers) */
+    const int cx = j % p.g.width, cy = j / p.g.width;
+    if (p.seed) {
+      const AutomatonSeedLevels level = {p.seed, cells};
+      for (int i = threadIdx.x; i < s.input_size; i += 256) cell_in[i] = automaton_input(p.g, cx, cy, i, level);
+    } else {
+      const AutomatonOutLevels level = {out0, s.O};
+      for (int i = threadIdx.x; i < s.input_size; i += 256) cell_in[i] = automaton_input(p.g, cx, cy, i, level);
+    }
+    __syncthreads();
+    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_DENSE, 0, cell_in, red);
+  }
+}
+
 // The one launch between two forward passes of rnn_amd_sample_texts (sample_api.c): N texts drawn from one net side by
 // side, a state row each.  One workgroup of 256 threads per row (assemble_input_row's), two halves:
 //   draw (not in a wave's first launch, t == 0; not for a row that is done): wave 0 turns the row's slice of the output
@@ -1184,6 +1247,34 @@ extern "C" void ramd_launch_seqs_step(ramd_stream_t st_, const RamdShape *sh, co
   if (shm > 64 * 1024) raise_lds_limit<k_seqs_step>(160 * 1024 - 64);
   SeqsStep p = {in, ans, win, off, goff, gsize, gap, hid0, row0, n_groups, n_gap, stride, t_score, a_score, t_feed, a_feed};
   RAMD_LAUNCH(k_seqs_step, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
+}
+
+extern "C" void ramd_launch_automaton_step(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
+                                           const AutomatonRule *grid, const unsigned char *seed, unsigned char *paint,
+                                           const float *hid0, int feed) {
+  const long long cells = (long long)grid->width * grid->height;
+  if (!paint && !feed) return;
+  if (grid->width < 1 || grid->height < 1 || row0 < sh->Scap || row0 + cells > sh->Scap + sh->Fcap) {
+    /* (the kernel writes forward-only input rows and reads every cell's out row) */
+    fprintf(stderr, "librecur_amd: ramd_launch_automaton_step: rows %d .. %lld are not forward-only state rows\n", row0,
+            row0 + cells);
+    abort();
+  }
+  if (grid->len_y < 0 || grid->len_c < 0 || (grid->len_y > 0 && !grid->offsets_y) || (grid->len_c > 0 && !grid->offsets_c) ||
+      automaton_input_size(grid) != sh->input_size || sh->output_size < 3) {
+    fprintf(stderr, "librecur_amd: ramd_launch_automaton_step: %d + 2 * %d + %d inputs for a net of %d, %d outputs\n",
+            grid->len_y, grid->len_c, grid->len_pos, sh->input_size, sh->output_size);
+    abort();
+  }
+  hipStream_t st = (hipStream_t)st_;
+  View v = make_view(sh, b);
+  const size_t shm = (size_t)((sh->input_size + 3) & ~3) * sizeof(float);
+  if (shm > 64 * 1024) {
+    fprintf(stderr, "librecur_amd: a cell's %d inputs do not fit the LDS\n", sh->input_size);
+    abort();
+  }
+  AutomatonStep p = {*grid, seed, paint, hid0, row0, feed};
+  RAMD_LAUNCH(k_automaton_step, dim3((unsigned)cells), dim3(256), shm, st, v, p);
 }
 
 extern "C" void ramd_launch_texts_sample(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,

@@ -272,6 +272,17 @@ void ramd_launch_seqs_step(ramd_stream_t st, const RamdShape *sh, const RamdBuff
                            const unsigned long long *off, float *ans, unsigned char *win, int n_groups, int largest,
                            const int *goff, const int *gsize, const int *gap, int n_gap, const float *hid0, int t_score,
                            int a_score, int t_feed, int a_feed);
+/* the launch between two forward passes of rnn_amd_run_automaton, for the width * height cells of `grid`
+ * (automaton_rule.h; its offset lists are device arrays, and with edges == 0 the caller has refused offsets the single
+ * wrap does not bring back) on forward-only state rows row0 ..., cell c on row row0 + c: with paint != NULL the three
+ * levels of every cell's outputs as bytes into the planes of the frame paint[3][cells]; with feed != 0 the input row of
+ * every cell's next forward pass, from the levels of its neighbours -- gathered from the bytes of seed[3][cells], or with
+ * a NULL seed made from the neighbours' out rows, which is the frame this launch paints -- on the row's hidden values, or
+ * on hid0's when that is not NULL.  All pointers are device pointers.  Every byte has one writer. */
+struct AutomatonRule;
+void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
+                                const struct AutomatonRule *grid, const unsigned char *seed, unsigned char *paint,
+                                const float *hid0, int feed);
 /* the launch between two forward passes of rnn_amd_sample_texts, launch t = 0 .. max_len of a wave of `rows` texts on
  * forward-only state rows row0 ...: for t > 0 draws symbol t - 1 of every row that is not done from head `head` of
  * alphabet_len outputs of its output row (sample_rule.h: the biased clamped softmax, a draw with rng[row], or the best

@@ -10,7 +10,9 @@ back the scorer's figures symbol by symbol (rnn_amd_trace_texts); ``run_texts_fr
 ``continue_texts_from`` are those with a start state per text and the final states handed back, as numpy arrays
 [n][h_size] (the rnn_amd_*_texts_from calls); ``run_sequences`` runs a list of dense feature sequences against one net in
 one batched call (rnn_amd_run_sequences): per frame the class groups' probabilities and winners, with states in and out
-in the same form.  ``synthetic_text_np`` is the seeded symbol stream of
+in the same form; ``run_automaton`` plays rnnca's automaton from a seed frame on an ``AutomatonGeometry`` in one call
+(rnn_amd_run_automaton): the frames as uint8 [n][3][height][width] and the cells' states, and ``parse_offsets`` expands an
+offset pattern (rnn_amd_automaton_parse_offsets).  ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
 """
@@ -263,6 +265,64 @@ def run_sequences(lib, net, seqs, groups=None, h_in=None, want_out=True, in_plac
     return [(ans[k][:counts[k]].reshape(-1, osz).copy(),
              win[k][:int(frames[k]) * ng].reshape(-1, ng).copy() if winners else None) for k in range(n)], \
         None if hout is None else hout[:n]
+
+
+def parse_offsets(lib, pattern, max_pairs=512):
+    """rnn_amd_automaton_parse_offsets: (the Y offsets, the C offsets) of an rnnca offset pattern such as
+    "Y00120111C0111", as int32 arrays [n][2] of (dx, dy).  The arrays are allocated with guard entries behind them, which
+    must come back untouched."""
+    oy = np.full(2 * max_pairs + TRACE_GUARD, -77, np.int32)
+    oc = np.full(2 * max_pairs + TRACE_GUARD, -77, np.int32)
+    ny, nc = C.c_int(-1), C.c_int(-1)
+    r = lib.rnn_amd_automaton_parse_offsets(pattern.encode() if isinstance(pattern, str) else pattern, rc.iptr(oy),
+                                            C.byref(ny), rc.iptr(oc), C.byref(nc), max_pairs)
+    assert np.all(oy[2 * max_pairs:] == -77) and np.all(oc[2 * max_pairs:] == -77), "offsets behind an array's room"
+    if r != 0:
+        raise ValueError("rnn_amd_automaton_parse_offsets refused the pattern (see stderr)")
+    assert np.all(oy[2 * ny.value:] == -77) and np.all(oc[2 * nc.value:] == -77), "offsets behind a list's length"
+    return oy[:2 * ny.value].reshape(-1, 2).copy(), oc[:2 * nc.value].reshape(-1, 2).copy()
+
+
+class AutomatonGeometry:
+    """an RnnAmdAutomaton and the arrays it points at: a width x height grid, the (dx, dy) offset lists [n][2], two or
+    three position inputs, clamped (edges != 0) or once-wrapped edges"""
+
+    def __init__(self, width, height, offsets_y, offsets_c, len_pos=2, edges=1):
+        self.width, self.height, self.len_pos, self.edges = width, height, len_pos, edges
+        self.offsets_y = np.ascontiguousarray(offsets_y, dtype=np.int32).reshape(-1, 2)
+        self.offsets_c = np.ascontiguousarray(offsets_c, dtype=np.int32).reshape(-1, 2)
+        self.input_size = len(self.offsets_y) + 2 * len(self.offsets_c) + len_pos
+        self.struct = rc.Automaton(width, height, rc.iptr(self.offsets_y) if len(self.offsets_y) else None,
+                                   len(self.offsets_y), rc.iptr(self.offsets_c) if len(self.offsets_c) else None,
+                                   len(self.offsets_c), len_pos, edges)
+
+
+def run_automaton(lib, net, geometry, seed, n_frames, h_in=None, want_out=True, in_place=False, segment_frames=0, fill=0xEE):
+    """rnn_amd_run_automaton: n_frames frames of rnnca's automaton on the grid of `geometry` (an AutomatonGeometry) from
+    the seed frame (uint8 [3][height][width]), every cell a forward-only clone of net.  Returns (frames uint8
+    [n_frames][3][height][width], h_out [cells][h_size] float32 or None with want_out=False).  h_in (None: the net's
+    hidden row), want_out and in_place as in the _from text drivers.  Every array is allocated with guard bytes behind it
+    (`fill`, NaN), which must come back untouched, and every state in front of them must be written; that every byte of
+    the frames is written shows in two calls with different `fill` giving the same frames."""
+    g = geometry
+    cells, H = g.width * g.height, net.contents.h_size
+    sd = np.ascontiguousarray(seed, dtype=np.uint8)
+    assert sd.size == 3 * cells, "a seed frame is [3][height][width] bytes"
+    count = n_frames * 3 * cells
+    frames = np.full(count + TRACE_GUARD, fill, np.uint8)
+    hin, hout, hip, _ = _states(net, cells, h_in, False, in_place)
+    if want_out and not in_place:
+        hout = np.full((cells + 1, H), np.nan, np.float32)   # (a guard row behind the states)
+    r = lib.rnn_amd_run_automaton(net, C.byref(g.struct), rc.u8ptr(sd), n_frames, hip, None if hout is None else rc.fptr(hout),
+                                  segment_frames, rc.u8ptr(frames))
+    if r != 0:
+        raise ValueError("rnn_amd_run_automaton refused the call (see stderr)")
+    assert np.all(frames[count:] == fill), "bytes behind the last frame"
+    if hout is not None and not in_place:
+        assert np.all(np.isnan(hout[cells])), "floats behind the last state"
+        hout = hout[:cells]
+        assert not np.any(np.isnan(hout[:, 1:1 + net.contents.hidden_size])), "a state was not written"
+    return frames[:count].reshape(n_frames, 3, g.height, g.width).copy(), hout
 
 
 class ApiSet:
