@@ -104,31 +104,25 @@ int rnn_amd_run_automaton(RecurNN *net, const RnnAmdAutomaton *ca, const u8 *see
   }
   size_t F = segment_frames > 0 ? (size_t)segment_frames : RAMD_MAX(AUTOMATON_SEGMENT_BYTES / frame_bytes, 1);
   F = RAMD_MIN(F, (size_t)n_frames);
-  RamdEngine *e = ramd_engine_of(net);
-  if (e->scratch_fwd < cells) {
-    e->scratch_fwd = cells; /* the image grows once (every net's state survives: ramd_engine_ensure_device) */
-  }
-  ramd_engine_ensure_device(e);
-  ramd_engine_need_dev(e, RNN_AMD_WEIGHTS);
-  ramd_stream_need_dev(e, net);
-  ramd_set_uniform_idx(e, e->n_streams, 0); /* forward-only rows: no ring position */
+  RamdRows rows;
+  ramd_rows_open(&rows, net, cells);
+  RamdEngine *e = rows.e;
   const RamdShape *s = &e->sh;
-  const int r0 = s->Scap + e->n_fwd; /* the engine's scratch rows lie behind the clones' */
-  /* every cell starts from the net's hidden row, or from its own state */
-  const float *hid0 = e->b.hidden + (size_t)ramd_state_row(e, ramd_priv(net)) * s->H;
-  float *states = e->b.hidden + (size_t)r0 * s->H;
+  const int r0 = rows.r0;
+  /* every cell starts from the net's hidden row, or from its own state: all rows are live and lie in the caller's order */
+  const float *hid0 = rows.hid0;
   if (h_in) {
-    ramd_h2d(states, h_in, (size_t)cells * s->H * sizeof(float));
+    ramd_h2d(rows.states, h_in, (size_t)cells * s->H * sizeof(float));
     hid0 = NULL;
   }
   const size_t n_off = 2 * ((size_t)ca->len_y + (size_t)ca->len_c);
-  int *d_off = ramd_dev_alloc((n_off ? n_off : 1) * sizeof(int));
+  int *d_off = ramd_rows_dev(&rows, (n_off ? n_off : 1) * sizeof(int));
   ramd_h2d(d_off, ca->offsets_y, 2 * (size_t)ca->len_y * sizeof(int));
   ramd_h2d(d_off + 2 * ca->len_y, ca->offsets_c, 2 * (size_t)ca->len_c * sizeof(int));
   const AutomatonRule grid = {ca->width, ca->height, d_off, ca->len_y, d_off + 2 * ca->len_y, ca->len_c, ca->len_pos,
                               ca->edges};
-  u8 *d_seed = ramd_dev_alloc(frame_bytes);
-  u8 *d_frames = ramd_dev_alloc(F * frame_bytes);
+  u8 *d_seed = ramd_rows_dev(&rows, frame_bytes);
+  u8 *d_frames = ramd_rows_dev(&rows, F * frame_bytes);
   ramd_h2d(d_seed, seed, frame_bytes);
   const RamdFwdCall call = {.row0 = r0, .nrows = cells, .rows_built = 1};
   /* launch 0 feeds from the seed; launch t + 1 paints frame t and, unless it was the last, feeds from it */
@@ -144,15 +138,13 @@ int rnn_amd_run_automaton(RecurNN *net, const RnnAmdAutomaton *ca, const u8 *see
     }
     if (slot + 1 == F || last) {
       ramd_d2h(frames + t0 * frame_bytes, d_frames, (slot + 1) * frame_bytes);
-      if (last && h_out) { /* a row's last forward pass was its last writer */
-        ramd_d2h(h_out, states, (size_t)cells * s->H * sizeof(float));
+      if (last) { /* a row's last forward pass was its last writer */
+        ramd_rows_states_out(&rows, cells, h_out);
       }
       ramd_dsync(); /* the segment's one synchronisation */
       t0 = t + 1;
     }
   }
-  ramd_dev_free(d_off);
-  ramd_dev_free(d_seed);
-  ramd_dev_free(d_frames);
+  ramd_rows_close(&rows);
   return 0;
 }

@@ -706,7 +706,7 @@ struct TextsStep {
   int t_score, a_score, t_feed, a_feed;
 };
 constexpr int TS_WAVES = 4;
-// Where the feed half of the four k_texts_* kernels takes state row r's hidden values from, stated once: from hid0 in a
+// Where the feed half of the k_texts_*, k_seqs_step and k_automaton_step kernels takes state row r's hidden values from, stated once: from hid0 in a
 // wave's first feed (`first`) when the call has one -- the hidden row of the net, which every row then starts from --,
 // else from the row's own hidden row: what the forward pass before left there, or, with a null hid0 in the first feed,
 // the start state the host has put there (the _from calls, texts_api.c and sample_api.c).
@@ -931,29 +931,6 @@ __global__ __launch_bounds__(256) void k_automaton_step(View v, AutomatonStep p)
   }
 }
 
-// The one launch between two forward passes of rnn_amd_sample_texts (sample_api.c): N texts drawn from one net side by
-// side, a state row each.  One workgroup of 256 threads per row (assemble_input_row's), two halves:
-//   draw (not in a wave's first launch, t == 0; not for a row that is done): wave 0 turns the row's slice of the output
-//     row, out[r][head * alen .. + alen), into the distribution in LDS (sample_rule.h, the wave as the team, lane-strided
-//     loops); lane 0 draws from it with the row's own generator -- p.rng, owned by the call, not b.rng -- stores symbol
-//     t - 1 of the row's text, the count and the generator.  The stop symbol ends the row (done 1), a draw that met the
-//     attempt cap fails it (done 2); its text and length are fixed from then on.  bias >= SAMPLE_GREEDY_BIAS: no draw, no
-//     generator.  Every word has one writer: no atomics.
-//   feed (t < max_len): the input row of the next forward pass -- assemble_input_row with the one-hot of the symbol just
-//     drawn, which reaches the workgroup through LDS behind a barrier; in the first launch the one-hot of first[j] on
-//     hid0, the hidden row of the net every text starts from (as k_texts_step).  A row that is done is not fed: its
-//     input row stays what it was and the forward passes that follow recompute what they computed.
-struct TextsSample {
-  const int *first;       /* [rows] the symbol in front of each text         */
-  DevRng *rng;            /* [rows] the rows' generators                      */
-  unsigned char *text;    /* [rows][max_len] the symbols drawn                */
-  int *len;               /* [rows] how many                                  */
-  int *done;              /* [rows] 0 running, 1 stopped, 2 failed            */
-  const float *hid0;      /* the hidden row of the first feed, or nullptr     */
-  int row0;               /* state row of the wave's row 0 (forward-only)     */
-  int alen, head, max_len, t, stop_point;
-  float bias;
-};
 struct SampleWave { /* sample_rule.h's team: the 64 lanes of one wave */
   int l;
   __device__ __forceinline__ int lane() const { return l; }
@@ -968,11 +945,11 @@ struct SampleRand64 {
   DevRng &g;
   __device__ __forceinline__ unsigned long long operator()() { return dev_rand64(g); }
 };
-// The draw half of k_texts_sample and k_texts_continue, stated once: the whole of wave 0 calls it for a row that is not
-// done.  The wave turns the row's slice of the output row into the distribution in sdist (LDS, alen floats); lane 0 draws
-// from it with rng[j], stores the pick as symbol `idx` of the row's text, the count idx + 1 and the generator, and sets
-// done[j] (1: the pick was stop_point, 2: the draw met the attempt cap and nothing was stored).  Returns, in lane 0, the
-// pick if the row runs on, else -1; in the other lanes -1.
+// The draw half of k_texts_continue: the whole of wave 0 calls it for a row that is not done.  The wave turns the row's
+// slice of the output row into the distribution in sdist (LDS, alen floats); lane 0 draws from it with rng[j], stores the
+// pick as symbol `idx` of the row's text, the count idx + 1 and the generator, and sets done[j] (1: the pick was
+// stop_point, 2: the draw met the attempt cap and nothing was stored).  Returns, in lane 0, the pick if the row runs on,
+// else -1; in the other lanes -1.
 __device__ __forceinline__ int texts_draw_and_store(const View &v, int r, int j, int lane, float *sdist, DevRng *rng,
                                                     unsigned char *text, int *len, int *done, int alen, int head,
                                                     int max_len, int idx, int stop_point, float bias) {
@@ -1002,42 +979,28 @@ __device__ __forceinline__ int texts_draw_and_store(const View &v, int r, int j,
   return hot;
 }
 
-__global__ __launch_bounds__(256) void k_texts_sample(View v, TextsSample p) {
-  extern __shared__ float sdist[]; /* [alen] the row's distribution */
-  __shared__ float red[4];
-  __shared__ int hot_sh; /* the symbol to feed, or -1 */
-  const RamdShape &s = v.sh;
-  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  if (wave == 0) {
-    int hot = -1;
-    if (p.t == 0) {
-      hot = p.first[j];
-    } else if (p.done[j] == 0) { /* (the same word in every lane: the wave takes one side) */
-      hot = texts_draw_and_store(v, r, j, lane, sdist, p.rng, p.text, p.len, p.done, p.alen, p.head, p.max_len, p.t - 1,
-                                 p.stop_point, p.bias);
-    }
-    if (lane == 0) hot_sh = p.t < p.max_len ? hot : -1;
-  }
-  __syncthreads();
-  const int hot = hot_sh;
-  if (hot >= 0) /* (the whole workgroup: assemble_input_row has barriers) */
-    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, p.t == 0), RAMD_IN_ONE_HOT, hot, nullptr, red);
-}
-
-// The one launch between two forward passes of rnn_amd_continue_texts (sample_api.c): N prompts continued by one net side
-// by side, a state row each, the rows ordered by prompt length + max_len, longest first (texts_plan.h), so that the rows
-// still running are a prefix.  One workgroup of 256 threads per row, as k_texts_sample; what launch t is for a row --
-// feeding prompt symbol t, drawing text index t - plen, or nothing -- is continue_rule.h's answer for the row's plen:
+// The one launch between two forward passes of rnn_amd_continue_texts and rnn_amd_sample_texts (sample_api.c): N prompts
+// continued by one net side by side, a state row each, the rows ordered by prompt length + max_len, longest first
+// (texts_plan.h), so that the rows still running are a prefix.  The sampler's rows are one-symbol prompts: `first` is set,
+// every row's plen is 1 and its prompt symbol first[j], an int that may lie above 255.  One workgroup of 256 threads per
+// row (assemble_input_row's); what launch t is for a row -- feeding prompt symbol t, drawing text index t - plen, or
+// nothing -- is continue_rule.h's answer for the row's plen:
 //   prompt: the one-hot of the row's prompt symbol on the row's hidden values, at t == 0 on hid0's (texts_feed_hidden).  No
 //     draw, no generator.
-//   draw (a row that is not done): texts_draw_and_store, k_texts_sample's draw half; the pick is fed unless it was the
-//     text's last index, the stop symbol, or a failure.
-// The symbol reaches the workgroup through LDS behind a barrier.  A row that is done or idle is not fed.  Every word has
-// one writer: no atomics.
+//   draw (a row that is not done): texts_draw_and_store -- wave 0 turns the row's slice of the output row,
+//     out[r][head * alen .. + alen), into the distribution in LDS (sample_rule.h, the wave as the team, lane-strided
+//     loops); lane 0 draws from it with the row's own generator -- p.rng, owned by the call, not b.rng -- and stores the
+//     symbol, the count and the generator.  The stop symbol ends the row (done 1), a draw that met the attempt cap fails
+//     it (done 2); its text and length are fixed from then on.  bias >= SAMPLE_GREEDY_BIAS: no draw, no generator.  The
+//     pick is fed unless it was the text's last index, the stop symbol, or a failure.
+// The symbol reaches the workgroup through LDS behind a barrier.  A row that is done or idle is not fed: its input row
+// stays what it was and the forward passes that follow recompute what they computed.  Every word has one writer: no
+// atomics.
 struct TextsContinue {
   const unsigned char *prompt;   /* the wave's prompts behind one another             */
   const unsigned long long *off; /* [rows] where row j's prompt starts                */
   const int *plen;               /* [rows] its length, at least 1                     */
+  const int *first;              /* [rows] the rows' one-symbol prompts, or nullptr   */
   DevRng *rng;                   /* [rows] the rows' generators                       */
   unsigned char *text;           /* [rows][max_len] the symbols drawn                 */
   int *len;                      /* [rows] how many                                   */
@@ -1053,11 +1016,11 @@ __global__ __launch_bounds__(256) void k_texts_continue(View v, TextsContinue p)
   __shared__ int hot_sh; /* the symbol to feed, or -1 */
   const RamdShape &s = v.sh;
   const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const ContinueStep st = continue_step(p.plen[j], p.max_len, p.t); /* (the same in every thread) */
+  const ContinueStep st = continue_step(p.first ? 1 : p.plen[j], p.max_len, p.t); /* (the same in every thread) */
   if (wave == 0) {
     int hot = -1;
     if (st.what == CONTINUE_PROMPT) {
-      hot = p.prompt[p.off[j] + st.index];
+      hot = p.first ? p.first[j] : p.prompt[p.off[j] + st.index];
     } else if (st.what == CONTINUE_DRAW && p.done[j] == 0) { /* (the same word in every lane: the wave takes one side) */
       hot = texts_draw_and_store(v, r, j, lane, sdist, p.rng, p.text, p.len, p.done, p.alen, p.head, p.max_len, st.index,
                                  p.stop_point, p.bias);
@@ -1169,24 +1132,37 @@ extern "C" void ramd_launch_multi_xent_accumulate(ramd_stream_t st_, const RamdS
               v, row, alphabet_len, acc, count_it);
 }
 
+// What the launchers of the batched calls' kernels share.  The kernels write forward-only input rows (the automaton's also
+// reads every cell's out row): rows row0 .. row0 + rows are such rows, or abort naming `who`
+static void forward_rows_or_abort(const char *who, const RamdShape *sh, int row0, long long rows) {
+  if (rows < 1 || row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) {
+    fprintf(stderr, "librecur_amd: %s: rows %d .. %lld are not forward-only state rows\n", who, row0, row0 + rows);
+    abort();
+  }
+}
+// `floats` floats of LDS for KERNEL's softmax over `outputs` outputs, in bytes: they fit, or abort; above 64 KiB the
+// kernel's limit is raised
+template <auto KERNEL>
+static size_t softmax_lds_or_abort(size_t floats, int outputs) {
+  const size_t shm = floats * sizeof(float);
+  if (shm > 160 * 1024 - 64) {
+    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", outputs);
+    abort();
+  }
+  if (shm > 64 * 1024) raise_lds_limit<KERNEL>(160 * 1024 - 64);
+  return shm;
+}
+
 extern "C" void ramd_launch_texts_step(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
                                        const unsigned char *text, const unsigned long long *off, const int *skip,
                                        double *acc, const float *hid0, int alphabet_len, int n_sums, int t_score,
                                        int a_score, int t_feed, int a_feed) {
   const int rows = a_score > a_feed ? a_score : a_feed;
   if (rows < 1) return;
-  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
-    fprintf(stderr, "librecur_amd: ramd_launch_texts_step: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
-    abort();
-  }
+  forward_rows_or_abort("ramd_launch_texts_step", sh, row0, rows);
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
-  const size_t shm = (size_t)TS_WAVES * ((alphabet_len + 3) & ~3) * sizeof(float);
-  if (shm > 160 * 1024 - 64) {
-    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", alphabet_len);
-    abort();
-  }
-  if (shm > 64 * 1024) raise_lds_limit<k_texts_step>(160 * 1024 - 64);
+  const size_t shm = softmax_lds_or_abort<k_texts_step>((size_t)TS_WAVES * ((alphabet_len + 3) & ~3), alphabet_len);
   TextsStep p = {text, off, skip, acc, hid0, row0, alphabet_len, n_sums, t_score, a_score, t_feed, a_feed};
   RAMD_LAUNCH(k_texts_step, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
 }
@@ -1198,10 +1174,7 @@ extern "C" void ramd_launch_texts_trace(ramd_stream_t st_, const RamdShape *sh, 
                                         int t_feed, int a_feed) {
   const int rows = a_score > a_feed ? a_score : a_feed;
   if (rows < 1) return;
-  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
-    fprintf(stderr, "librecur_amd: ramd_launch_texts_trace: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
-    abort();
-  }
+  forward_rows_or_abort("ramd_launch_texts_trace", sh, row0, rows);
   if (alphabet_len < 1 || n_sums < 1 || (size_t)n_sums * alphabet_len > (size_t)sh->O || (a_score > 0 && t_score < 0)) {
     fprintf(stderr, "librecur_amd: ramd_launch_texts_trace: %d heads of %d outputs in a row of %d, step %d\n", n_sums,
             alphabet_len, sh->O, t_score);
@@ -1209,12 +1182,7 @@ extern "C" void ramd_launch_texts_trace(ramd_stream_t st_, const RamdShape *sh, 
   }
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
-  const size_t shm = (size_t)TS_WAVES * ((alphabet_len + 3) & ~3) * sizeof(float);
-  if (shm > 160 * 1024 - 64) {
-    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", alphabet_len);
-    abort();
-  }
-  if (shm > 64 * 1024) raise_lds_limit<k_texts_trace>(160 * 1024 - 64);
+  const size_t shm = softmax_lds_or_abort<k_texts_trace>((size_t)TS_WAVES * ((alphabet_len + 3) & ~3), alphabet_len);
   TextsTrace p = {text, off, off_tr, trace, guess, hid0, row0, alphabet_len, n_sums, t_score, a_score, t_feed, a_feed};
   RAMD_LAUNCH(k_texts_trace, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
 }
@@ -1225,10 +1193,7 @@ extern "C" void ramd_launch_seqs_step(ramd_stream_t st_, const RamdShape *sh, co
                                       int n_gap, const float *hid0, int t_score, int a_score, int t_feed, int a_feed) {
   const int rows = a_score > a_feed ? a_score : a_feed;
   if (rows < 1) return;
-  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
-    fprintf(stderr, "librecur_amd: ramd_launch_seqs_step: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
-    abort();
-  }
+  forward_rows_or_abort("ramd_launch_seqs_step", sh, row0, rows);
   if (n_groups < 0 || n_gap < 0 || largest < 0 || largest > sh->output_size || n_gap > sh->output_size ||
       (n_groups > 0 && (!goff || !gsize || largest < 1)) || (n_gap > 0 && !gap) || (win && n_groups < 1) ||
       (a_score > 0 && (t_score < 0 || !ans)) || (a_feed > 0 && (t_feed < 0 || !in)) || !off) {
@@ -1239,12 +1204,7 @@ extern "C" void ramd_launch_seqs_step(ramd_stream_t st_, const RamdShape *sh, co
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
   const int stride = (largest + 3) & ~3;
-  const size_t shm = (size_t)TS_WAVES * stride * sizeof(float);
-  if (shm > 160 * 1024 - 64) {
-    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", largest);
-    abort();
-  }
-  if (shm > 64 * 1024) raise_lds_limit<k_seqs_step>(160 * 1024 - 64);
+  const size_t shm = softmax_lds_or_abort<k_seqs_step>((size_t)TS_WAVES * stride, largest);
   SeqsStep p = {in, ans, win, off, goff, gsize, gap, hid0, row0, n_groups, n_gap, stride, t_score, a_score, t_feed, a_feed};
   RAMD_LAUNCH(k_seqs_step, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
 }
@@ -1252,14 +1212,9 @@ extern "C" void ramd_launch_seqs_step(ramd_stream_t st_, const RamdShape *sh, co
 extern "C" void ramd_launch_automaton_step(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
                                            const AutomatonRule *grid, const unsigned char *seed, unsigned char *paint,
                                            const float *hid0, int feed) {
-  const long long cells = (long long)grid->width * grid->height;
+  const long long cells = grid->width < 1 || grid->height < 1 ? 0 : (long long)grid->width * grid->height;
   if (!paint && !feed) return;
-  if (grid->width < 1 || grid->height < 1 || row0 < sh->Scap || row0 + cells > sh->Scap + sh->Fcap) {
-    /* (the kernel writes forward-only input rows and reads every cell's out row) */
-    fprintf(stderr, "librecur_amd: ramd_launch_automaton_step: rows %d .. %lld are not forward-only state rows\n", row0,
-            row0 + cells);
-    abort();
-  }
+  forward_rows_or_abort("ramd_launch_automaton_step", sh, row0, cells); /* (a grid without a cell has no rows) */
   if (grid->len_y < 0 || grid->len_c < 0 || (grid->len_y > 0 && !grid->offsets_y) || (grid->len_c > 0 && !grid->offsets_c) ||
       automaton_input_size(grid) != sh->input_size || sh->output_size < 3) {
     fprintf(stderr, "librecur_amd: ramd_launch_automaton_step: %d + 2 * %d + %d inputs for a net of %d, %d outputs\n",
@@ -1277,41 +1232,12 @@ extern "C" void ramd_launch_automaton_step(ramd_stream_t st_, const RamdShape *s
   RAMD_LAUNCH(k_automaton_step, dim3((unsigned)cells), dim3(256), shm, st, v, p);
 }
 
-extern "C" void ramd_launch_texts_sample(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
-                                         const int *first, void *rng, unsigned char *text, int *len, int *done,
-                                         const float *hid0, int alphabet_len, int head, int max_len, int t, int stop_point,
-                                         float bias) {
-  if (rows < 1) return;
-  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
-    fprintf(stderr, "librecur_amd: ramd_launch_texts_sample: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
-    abort();
-  }
-  if (alphabet_len < 1 || head < 0 || (size_t)(head + 1) * alphabet_len > (size_t)sh->O || t < 0 || t > max_len) {
-    fprintf(stderr, "librecur_amd: ramd_launch_texts_sample: head %d of %d outputs in a row of %d, step %d of %d\n", head,
-            alphabet_len, sh->O, t, max_len);
-    abort();
-  }
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  const size_t shm = (size_t)((alphabet_len + 3) & ~3) * sizeof(float);
-  if (shm > 160 * 1024 - 64) {
-    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", alphabet_len);
-    abort();
-  }
-  if (shm > 64 * 1024) raise_lds_limit<k_texts_sample>(160 * 1024 - 64);
-  TextsSample p = {first, (DevRng *)rng, text, len, done, hid0, row0, alphabet_len, head, max_len, t, stop_point, bias};
-  RAMD_LAUNCH(k_texts_sample, dim3(rows), dim3(256), shm, st, v, p);
-}
-
 extern "C" void ramd_launch_texts_continue(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
                                            const unsigned char *prompt, const unsigned long long *off, const int *plen,
-                                           void *rng, unsigned char *text, int *len, int *done, const float *hid0,
+                                           const int *first, void *rng, unsigned char *text, int *len, int *done, const float *hid0,
                                            int alphabet_len, int head, int max_len, int t, int stop_point, float bias) {
   if (rows < 1) return;
-  if (row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) { /* (the kernel writes forward-only input rows) */
-    fprintf(stderr, "librecur_amd: ramd_launch_texts_continue: rows %d .. %d are not forward-only state rows\n", row0, row0 + rows);
-    abort();
-  }
+  forward_rows_or_abort("ramd_launch_texts_continue", sh, row0, rows);
   if (alphabet_len < 1 || head < 0 || (size_t)(head + 1) * alphabet_len > (size_t)sh->O || t < 0 || max_len < 1) {
     fprintf(stderr, "librecur_amd: ramd_launch_texts_continue: head %d of %d outputs in a row of %d, step %d, texts of %d\n",
             head, alphabet_len, sh->O, t, max_len);
@@ -1319,13 +1245,8 @@ extern "C" void ramd_launch_texts_continue(ramd_stream_t st_, const RamdShape *s
   }
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
-  const size_t shm = (size_t)((alphabet_len + 3) & ~3) * sizeof(float);
-  if (shm > 160 * 1024 - 64) {
-    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", alphabet_len);
-    abort();
-  }
-  if (shm > 64 * 1024) raise_lds_limit<k_texts_continue>(160 * 1024 - 64);
-  TextsContinue p = {prompt, off, plen, (DevRng *)rng, text, len, done, hid0, row0, alphabet_len, head, max_len, t, stop_point, bias};
+  const size_t shm = softmax_lds_or_abort<k_texts_continue>((size_t)((alphabet_len + 3) & ~3), alphabet_len);
+  TextsContinue p = {prompt, off, plen, first, (DevRng *)rng, text, len, done, hid0, row0, alphabet_len, head, max_len, t, stop_point, bias};
   RAMD_LAUNCH(k_texts_continue, dim3(rows), dim3(256), shm, st, v, p);
 }
 

@@ -283,27 +283,23 @@ struct AutomatonRule;
 void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
                                 const struct AutomatonRule *grid, const unsigned char *seed, unsigned char *paint,
                                 const float *hid0, int feed);
-/* the launch between two forward passes of rnn_amd_sample_texts, launch t = 0 .. max_len of a wave of `rows` texts on
- * forward-only state rows row0 ...: for t > 0 draws symbol t - 1 of every row that is not done from head `head` of
- * alphabet_len outputs of its output row (sample_rule.h: the biased clamped softmax, a draw with rng[row], or the best
- * output when bias >= 100) into text[row][max_len], counts it in len[row] and sets done[row] (1: it was stop_point, 2: the
- * draw failed); for t < max_len builds the input row of the next forward pass (the one-hot of that symbol on the row's
- * hidden values; for t == 0 of first[row] on hid0's, or with a NULL hid0 on the row's own there too).  All pointers are
- * device pointers; rng is [rows] rand_ctx. */
-void ramd_launch_texts_sample(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
-                              const int *first, void *rng, unsigned char *text, int *len, int *done, const float *hid0,
-                              int alphabet_len, int head, int max_len, int t, int stop_point, float bias);
-/* the launch between two forward passes of rnn_amd_continue_texts, launch t = 0 .. of a wave of `rows` prompts on
- * forward-only state rows row0 ... (texts_plan.h's order for prompt length + max_len): what it does for a row is
- * continue_rule.h's continue_step(plen[row], max_len, t) -- the input row of the next pass from prompt symbol t (the
- * row's prompt starts at prompt[off[row]]; on hid0's hidden values at t == 0 unless hid0 is NULL, else on the row's own:
- * with a NULL hid0 the caller has put the rows' start states into their hidden rows), or the draw of text
- * index t - plen[row] exactly as ramd_launch_texts_sample makes it (text, len, done, rng as there) and the input row from
- * the pick, or nothing.  All pointers are device pointers. */
+/* the launch between two forward passes of rnn_amd_continue_texts and rnn_amd_sample_texts, launch t = 0 .. of a wave
+ * of `rows` prompts on forward-only state rows row0 ... (texts_plan.h's order for prompt length + max_len): what it does
+ * for a row is continue_rule.h's continue_step(plen[row], max_len, t) --
+ *   the input row of the next pass from prompt symbol t (the row's prompt starts at prompt[off[row]]; on hid0's hidden
+ *   values at t == 0 unless hid0 is NULL, else on the row's own: with a NULL hid0 the caller has put the rows' start
+ *   states into their hidden rows), or
+ *   the draw of text index t - plen[row] of a row that is not done, from head `head` of alphabet_len outputs of its
+ *   output row (sample_rule.h: the biased clamped softmax, a draw with rng[row], or the best output when bias >= 100)
+ *   into text[row][max_len], counted in len[row], with done[row] set (1: it was stop_point, 2: the draw failed), and --
+ *   unless the index was the last -- the input row of the next pass from the one-hot of the pick, or
+ *   nothing.
+ * first != NULL is the sampler's form: every row's prompt is the one symbol first[row] (an int: it may lie above 255),
+ * and prompt, off and plen are not read.  All pointers are device pointers; rng is [rows] rand_ctx. */
 void ramd_launch_texts_continue(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
-                                const unsigned char *prompt, const unsigned long long *off, const int *plen, void *rng,
-                                unsigned char *text, int *len, int *done, const float *hid0, int alphabet_len, int head,
-                                int max_len, int t, int stop_point, float bias);
+                                const unsigned char *prompt, const unsigned long long *off, const int *plen,
+                                const int *first, void *rng, unsigned char *text, int *len, int *done, const float *hid0,
+                                int alphabet_len, int head, int max_len, int t, int stop_point, float bias);
 /* rnnca's loss (gstrnnca.c:701-714): sigmoid in place on the first n outputs, slope * (target -
  * a) into o_error; targets is a device array [nrows][ld] */
 void ramd_launch_sigmoid_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,

@@ -216,16 +216,46 @@ void ramd_fused_net_update(RamdEngine *e, RecurNN *net, int row, unsigned batch_
 
 /* texts_api.c: the refusals of rnn_amd_run_texts / _heads (alphabet_len 0: no heads), which need no device: -1 with a
  * message on stderr, else 0 */
-/* the part of them that is about the net, shared with rnn_amd_sample_texts (sample_api.c): a bottom layer, heads that do
- * not divide the output row */
-int ramd_texts_net_refused(const char *who, const RecurNN *net, int alphabet_len);
 int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const *texts, const int *lens, int n_texts,
                            int alphabet_len, const void *out);
-/* net's hidden row as it stands, into row[h_size], with neither of net's copies changed; and, shared with
- * rnn_amd_continue_texts_from (sample_api.c), h_out of the texts that take no row (lens[k] < 2; n_rows: how many take
- * one): their start state, h_in[k] or -- h_in NULL -- that hidden row (texts_states.h).  Returns 0, or -1 out of memory */
+
+/* rows_host.c: what the batched calls on forward-only state rows share (texts_api.c, sample_api.c, seqs_api.c,
+ * automaton_api.c) */
+/* what all of them refuse about the net, without a device: a bottom layer, heads that do not divide the output row
+ * (alphabet_len 0: no heads).  -1 with a message on stderr, else 0 */
+int ramd_texts_net_refused(const char *who, const RecurNN *net, int alphabet_len);
+/* net's hidden row as it stands, into row[h_size], with neither of net's copies changed; and h_out of the texts that
+ * take no row (lens[k] < 2; n_rows: how many take one): their start state, h_in[k] or -- h_in NULL -- that hidden row
+ * (texts_states.h).  Returns 0, or -1 out of memory */
 void ramd_texts_net_hidden_row(RecurNN *net, float *row);
 int ramd_texts_fill_rowless(RecurNN *net, const int *lens, int n_texts, int n_rows, const float *h_in, float *h_out);
+/* One call's forward-only rows, behind the returns that ask for no device.  ramd_rows_open: the engine's image has room
+ * for `widest` scratch rows, the weights and net's own state are current on the device, and the rows have no ring
+ * position; e, r0 (the state row of the call's row 0), hid0 (net's hidden row on the device) and states (the rows'
+ * hidden rows, contiguous from r0 on) are set.  ramd_rows_host / _dev: a zeroed staging buffer of the call's on that
+ * side, at most RAMD_ROWS_STAGING a side (more aborts); ramd_rows_close frees them all. */
+#define RAMD_ROWS_STAGING 8
+typedef struct RamdRows {
+  RamdEngine *e;
+  int r0;
+  const float *hid0;
+  float *states;
+  void *host[RAMD_ROWS_STAGING], *dev[RAMD_ROWS_STAGING];
+  int n_host, n_dev;
+} RamdRows;
+void ramd_rows_open(RamdRows *rows, RecurNN *net, int widest);
+void *ramd_rows_host(RamdRows *rows, size_t bytes);
+void *ramd_rows_dev(RamdRows *rows, size_t bytes);
+void ramd_rows_close(RamdRows *rows);
+/* Where wave w of the plan starts: with h_in its rows' start states are packed into h_state ([rows][H], texts_states.h)
+ * and copied into `states`, and NULL is returned -- the first launch reads them there as every later one does; without,
+ * hid0 is returned and the first launch builds every input row from it.  ramd_rows_states_out issues the copy of the
+ * first n state rows to dst (NULL: not wanted) in front of the wave's or segment's synchronisation; the caller unpacks
+ * behind it. */
+struct TextsPlan;
+const float *ramd_rows_states_in(const RamdRows *rows, const struct TextsPlan *plan, int w, const float *h_in,
+                                 float *h_state);
+void ramd_rows_states_out(const RamdRows *rows, int n, float *dst);
 
 /* set_api.c */
 void ramd_set_need_training(const RnnAmdSet *set, const char *what);

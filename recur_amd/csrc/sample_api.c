@@ -1,15 +1,16 @@
-/* sample_api.c -- many texts drawn from one net in one batched device run (gnu11 C): rnn_amd_sample_texts, the
- * generative counterpart of rnn_amd_run_texts (texts_api.c), and rnn_amd_char_confabulate_texts, its character layer.
- * Where rnn_char_confabulate (char_sampling.c) visits the host for every symbol of one net -- the output row comes back,
- * the host draws, the generator goes out again -- these give every text a forward-only state row of the engine's own and
- * a generator of its own in a buffer of the call's, and run the rows together: between two forward passes of the rows
- * there is one launch (k_texts_sample, kernels_loss.hip) that draws each row's next symbol on the device (sample_rule.h)
- * and builds the input rows of the next pass from it.  The net the caller passes is read -- its weights, its hidden row --
- * and not written.
- * rnn_amd_continue_texts and rnn_amd_char_continue_texts are the same with a prompt per row in front of the draws: the
- * rows are laid out by prompt length + max_len (texts_plan.h, as rnn_amd_run_texts lays out its texts), and the launch
- * between two forward passes (k_texts_continue) feeds a row its prompt or draws for it, as continue_rule.h says.
- * rnn_amd_continue_texts_from is that call with every row's start state and generator from the caller's arrays and its
+/* sample_api.c -- many texts drawn from one net in one batched device run (gnu11 C): rnn_amd_continue_texts, the
+ * generative counterpart of rnn_amd_run_texts (texts_api.c), rnn_amd_sample_texts, which is that call with every prompt
+ * one symbol, and their character layers.  Where rnn_char_confabulate (char_sampling.c) visits the host for every symbol
+ * of one net -- the output row comes back, the host draws, the generator goes out again -- these give every text a
+ * forward-only state row of the engine's own (rows_host.c) and a generator of its own in a buffer of the call's, and run
+ * the rows together.  The rows are laid out by prompt length + max_len (texts_plan.h, as rnn_amd_run_texts lays out its
+ * texts), and between two forward passes of the rows there is one launch (k_texts_continue, kernels_loss.hip) that feeds
+ * a row its prompt or draws its next symbol on the device (sample_rule.h) and builds the input row of the next pass from
+ * it, as continue_rule.h says.  There is ONE wave loop, continue_wave, and one body behind the refusals, draw_texts:
+ * the sampler hands it its first symbols as ints (they may lie above 255, so they do not travel as prompt bytes) and
+ * equal lengths, for which the plan keeps the caller's order in waves of 256.  The net the caller passes is read -- its
+ * weights, its hidden row -- and not written.
+ * rnn_amd_continue_texts_from is the call with every row's start state and generator from the caller's arrays and its
  * final state handed back (texts_states.h: which state belongs to which row); rnn_amd_continue_texts is it with NULLs. */
 #define RAMD_HIP_HOST 1
 #include <limits.h>
@@ -94,200 +95,94 @@ static int nothing_to_draw(const u64 *seeds, int n_texts, int *out_lens, rand_ct
   return 0;
 }
 
-/* the device and host sides of one wave's arrays, with room for TEXTS_PLAN_WIDTH rows (or all the texts, if fewer) */
-typedef struct SampleBuffers {
-  int *d_first, *d_len, *d_done, *h_len, *h_done;
+/* the device and host sides of one wave's arrays, with room for the plan's first (largest) wave; the prompts' three, or
+ * d_first alone where every row's prompt is the one symbol first[k] */
+typedef struct ContinueBuffers {
+  int *d_len, *d_done, *h_len, *h_done;
   rand_ctx *d_rng, *h_rng;
   u8 *d_text, *h_text;
-} SampleBuffers;
-
-/* rows [k0, k0 + n) of the call on the state rows from r0 on; returns the number of rows whose draw failed */
-static int sample_wave(RamdEngine *e, const RecurNN *net, int r0, const int *first, const u64 *seeds, int k0, int n,
-                       int max_len, float bias, int stop_point, int alen, int head, const SampleBuffers *sb, u8 *out,
-                       int *out_lens, rand_ctx *rng_out) {
-  const RamdShape *s = &e->sh;
-  for (int j = 0; j < n; j++) {
-    ramd_init_rand64(&sb->h_rng[j], seeds[k0 + j]);
-  }
-  ramd_h2d(sb->d_first, first + k0, (size_t)n * sizeof(int));
-  ramd_h2d(sb->d_rng, sb->h_rng, (size_t)n * sizeof(rand_ctx));
-  HIP_OK(hipMemsetAsync(sb->d_len, 0, (size_t)n * sizeof(int), ramd_stream));
-  HIP_OK(hipMemsetAsync(sb->d_done, 0, (size_t)n * sizeof(int), ramd_stream));
-  /* every row starts from the net's hidden row: the first launch builds the input rows from it */
-  const float *hid0 = e->b.hidden + (size_t)ramd_state_row(e, ramd_priv(net)) * s->H;
-  for (int t = 0; t <= max_len; t++) {
-    ramd_launch_texts_sample(ramd_stream, s, &e->b, r0, n, sb->d_first, sb->d_rng, sb->d_text, sb->d_len, sb->d_done, hid0,
-                             alen, head, max_len, t, stop_point, bias);
-    if (t == max_len) {
-      break;
-    }
-    if (t > 0 && t % SAMPLE_CHECK_EVERY == 0) { /* has every row met its stop symbol?  then the rest would run on nothing */
-      ramd_d2h(sb->h_done, sb->d_done, (size_t)n * sizeof(int));
-      ramd_dsync();
-      int running = 0;
-      for (int j = 0; j < n; j++) {
-        running += sb->h_done[j] == 0;
-      }
-      if (!running) {
-        break;
-      }
-    }
-    const RamdFwdCall call = {.row0 = r0, .nrows = n, .rows_built = 1};
-    ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
-  }
-  ramd_d2h(sb->h_text, sb->d_text, (size_t)n * max_len);
-  ramd_d2h(sb->h_len, sb->d_len, (size_t)n * sizeof(int));
-  ramd_d2h(sb->h_done, sb->d_done, (size_t)n * sizeof(int));
-  ramd_d2h(sb->h_rng, sb->d_rng, (size_t)n * sizeof(rand_ctx));
-  ramd_dsync(); /* the wave's synchronisation */
-  int failed = 0;
-  for (int j = 0; j < n; j++) {
-    const int len = RAMD_MIN(RAMD_MAX(sb->h_len[j], 0), max_len);
-    memcpy(out + (size_t)(k0 + j) * max_len, sb->h_text + (size_t)j * max_len, (size_t)len);
-    out_lens[k0 + j] = len;
-    failed += sb->h_done[j] == 2;
-    if (rng_out) {
-      rng_out[k0 + j] = sb->h_rng[j];
-    }
-  }
-  return failed;
-}
-
-int rnn_amd_sample_texts(RecurNN *net, const int *first, const u64 *seeds, int n_texts, int max_len, float bias,
-                         int stop_point, int alphabet_len, int head, u8 *out, int *out_lens, rand_ctx *rng_out) {
-  const char *who = "rnn_amd_sample_texts";
-  if (sample_texts_refused(who, net, first, seeds, n_texts, max_len, alphabet_len, head, out, out_lens)) {
-    return -1;
-  }
-  if (n_texts == 0 || max_len == 0) {
-    return nothing_to_draw(seeds, n_texts, out_lens, rng_out);
-  }
-  const int alen = alphabet_len ? alphabet_len : net->output_size;
-  RamdEngine *e = ramd_engine_of(net);
-  const int widest = RAMD_MIN(n_texts, TEXTS_PLAN_WIDTH);
-  if (e->scratch_fwd < widest) {
-    e->scratch_fwd = widest; /* the image grows once (every net's state survives: ramd_engine_ensure_device) */
-  }
-  ramd_engine_ensure_device(e);
-  ramd_engine_need_dev(e, RNN_AMD_WEIGHTS);
-  ramd_stream_need_dev(e, net);
-  ramd_set_uniform_idx(e, e->n_streams, 0); /* forward-only rows: no ring position */
-  const int r0 = e->sh.Scap + e->n_fwd; /* the engine's scratch rows lie behind the clones' */
-  SampleBuffers sb;
-  sb.h_len = ramd_zalloc((size_t)widest * sizeof(int));
-  sb.h_done = ramd_zalloc((size_t)widest * sizeof(int));
-  sb.h_rng = ramd_zalloc((size_t)widest * sizeof(rand_ctx));
-  sb.h_text = ramd_zalloc((size_t)widest * max_len);
-  sb.d_first = ramd_dev_alloc((size_t)widest * sizeof(int));
-  sb.d_len = ramd_dev_alloc((size_t)widest * sizeof(int));
-  sb.d_done = ramd_dev_alloc((size_t)widest * sizeof(int));
-  sb.d_rng = ramd_dev_alloc((size_t)widest * sizeof(rand_ctx));
-  sb.d_text = ramd_dev_alloc((size_t)widest * max_len);
-  int failed = 0;
-  for (int k0 = 0; k0 < n_texts; k0 += TEXTS_PLAN_WIDTH) {
-    failed += sample_wave(e, net, r0, first, seeds, k0, RAMD_MIN(n_texts - k0, TEXTS_PLAN_WIDTH), max_len, bias, stop_point,
-                          alen, head, &sb, out, out_lens, rng_out);
-  }
-  ramd_dev_free(sb.d_first);
-  ramd_dev_free(sb.d_len);
-  ramd_dev_free(sb.d_done);
-  ramd_dev_free(sb.d_rng);
-  ramd_dev_free(sb.d_text);
-  free(sb.h_len);
-  free(sb.h_done);
-  free(sb.h_rng);
-  free(sb.h_text);
-  if (failed) {
-    fprintf(stderr, "librecur_amd: %s: %d of %d texts met the attempt cap of the draw (an output row without a total)\n",
-            who, failed, n_texts);
-    return -1;
-  }
-  return 0;
-}
-
-/* the device and host sides of one wave of rnn_amd_continue_texts: SampleBuffers (d_first unused) and the prompts */
-typedef struct ContinueBuffers {
-  SampleBuffers sb;
   u8 *h_prompt, *d_prompt;
   unsigned long long *h_off, *d_off;
   int *h_plen, *d_plen;
+  int *d_first;
   float *h_state; /* [rows][H] the wave's states on their way in and out, or NULL */
 } ContinueBuffers;
 
-/* where a call's rows start and what it hands back of them besides the text: start states and generators (NULL: the
- * net's hidden row, init_rand64 of the seeds), final states and generators (NULL: not wanted) */
-typedef struct ContinueStates {
+/* what a call's rows start from -- their prompts, or (first != NULL) one symbol each, which may lie above 255 -- and
+ * where, and what it hands back of them besides the text: start states and generators (NULL: the net's hidden row,
+ * init_rand64 of the seeds), final states and generators (NULL: not wanted) */
+typedef struct ContinueCall {
+  const u8 *const *prompts;
+  const int *first;
   const float *h_in;
   float *h_out;
   const u64 *seeds;
   const rand_ctx *rng_in;
   rand_ctx *rng_out;
-} ContinueStates;
+} ContinueCall;
 
 /* row k's generator before its first draw */
-static rand_ctx start_generator(const ContinueStates *cs, int k) {
+static rand_ctx start_generator(const ContinueCall *cc, int k) {
   rand_ctx g;
-  if (cs->rng_in) {
-    g = cs->rng_in[k];
+  if (cc->rng_in) {
+    g = cc->rng_in[k];
   } else {
-    ramd_init_rand64(&g, cs->seeds[k]);
+    ramd_init_rand64(&g, cc->seeds[k]);
   }
   return g;
 }
 
-/* wave w of the plan (its len is prompt length + max_len) on the state rows from r0 on; returns the number of rows whose
+/* wave w of the plan (its len is prompt length + max_len) on the call's state rows; returns the number of rows whose
  * draw failed */
-static int continue_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, int w, int r0, const u8 *const *prompts,
-                         const ContinueStates *cs, int max_len, float bias, int stop_point, int alen, int head,
-                         const ContinueBuffers *cb, u8 *out, int *out_lens) {
+static int continue_wave(const RamdRows *rows, const TextsPlan *plan, int w, const ContinueCall *cc, int max_len,
+                         float bias, int stop_point, int alen, int head, const ContinueBuffers *cb, u8 *out,
+                         int *out_lens) {
+  RamdEngine *e = rows->e;
   const RamdShape *s = &e->sh;
-  const SampleBuffers *sb = &cb->sb;
+  const int r0 = rows->r0;
   const TextsWave *wave = &plan->waves[w];
   const int n = wave->nrows;
   size_t at = 0;
   for (int j = 0; j < n; j++) {
     const int k = plan->order[wave->row0 + j], plen = plan->len[wave->row0 + j] - max_len;
-    cb->h_off[j] = at;
-    cb->h_plen[j] = plen;
-    memcpy(cb->h_prompt + at, prompts[k], (size_t)plen);
-    at += (size_t)plen;
-    sb->h_rng[j] = start_generator(cs, k);
+    if (!cc->first) {
+      cb->h_off[j] = at;
+      cb->h_plen[j] = plen;
+      memcpy(cb->h_prompt + at, cc->prompts[k], (size_t)plen);
+      at += (size_t)plen;
+    }
+    cb->h_rng[j] = start_generator(cc, k);
   }
-  ramd_h2d(cb->d_prompt, cb->h_prompt, at);
-  ramd_h2d(cb->d_off, cb->h_off, (size_t)n * sizeof(unsigned long long));
-  ramd_h2d(cb->d_plen, cb->h_plen, (size_t)n * sizeof(int));
-  ramd_h2d(sb->d_rng, sb->h_rng, (size_t)n * sizeof(rand_ctx));
-  HIP_OK(hipMemsetAsync(sb->d_len, 0, (size_t)n * sizeof(int), ramd_stream));
-  HIP_OK(hipMemsetAsync(sb->d_done, 0, (size_t)n * sizeof(int), ramd_stream));
-  /* every row starts from the net's hidden row: the first launch builds the input rows from it.  Or from its own state:
-   * the wave's rows of h_in go into the state rows, which are contiguous, and the first launch reads them there as every
-   * later one does (a null hid0, k_texts_continue) */
-  const float *hid0 = e->b.hidden + (size_t)ramd_state_row(e, ramd_priv(net)) * s->H;
-  float *states = e->b.hidden + (size_t)r0 * s->H;
-  if (cs->h_in) {
-    texts_states_pack(plan, w, cs->h_in, NULL, s->H, s->hidden_size, cb->h_state);
-    ramd_h2d(states, cb->h_state, (size_t)n * s->H * sizeof(float));
-    hid0 = NULL;
+  if (cc->first) { /* (equal lengths: the plan keeps the caller's order, row row0 + j is text row0 + j) */
+    ramd_h2d(cb->d_first, cc->first + wave->row0, (size_t)n * sizeof(int));
+  } else {
+    ramd_h2d(cb->d_prompt, cb->h_prompt, at);
+    ramd_h2d(cb->d_off, cb->h_off, (size_t)n * sizeof(unsigned long long));
+    ramd_h2d(cb->d_plen, cb->h_plen, (size_t)n * sizeof(int));
   }
-  const int lead = cb->h_plen[0]; /* the wave's longest row: its launches are the wave's */
-  int rows = n;                   /* the rows launch t is for: those that were fed after launch t - 1 */
+  ramd_h2d(cb->d_rng, cb->h_rng, (size_t)n * sizeof(rand_ctx));
+  HIP_OK(hipMemsetAsync(cb->d_len, 0, (size_t)n * sizeof(int), ramd_stream));
+  HIP_OK(hipMemsetAsync(cb->d_done, 0, (size_t)n * sizeof(int), ramd_stream));
+  const float *hid0 = ramd_rows_states_in(rows, plan, w, cc->h_in, cb->h_state);
+  const int lead = plan->len[wave->row0] - max_len; /* the wave's longest row: its launches are the wave's */
+  int fed = n;                                      /* the rows launch t is for: those that were fed after launch t - 1 */
   for (int t = 0;; t++) {
     const ContinueStep st = continue_step(lead, max_len, t);
     if (st.what == CONTINUE_IDLE) {
       break;
     }
-    ramd_launch_texts_continue(ramd_stream, s, &e->b, r0, rows, cb->d_prompt, cb->d_off, cb->d_plen, sb->d_rng, sb->d_text,
-                               sb->d_len, sb->d_done, hid0, alen, head, max_len, t, stop_point, bias);
+    ramd_launch_texts_continue(ramd_stream, s, &e->b, r0, fed, cb->d_prompt, cb->d_off, cb->d_plen, cb->d_first, cb->d_rng,
+                               cb->d_text, cb->d_len, cb->d_done, hid0, alen, head, max_len, t, stop_point, bias);
     if (!st.feeds) { /* the longest row's last draw */
       break;
     }
     const int a = texts_plan_active(plan, w, t); /* the rows that are fed after launch t: a prefix (texts_plan.h) */
     if (t > 0 && t % SAMPLE_CHECK_EVERY == 0) { /* has every such row met its stop symbol?  then the rest would run on nothing */
-      ramd_d2h(sb->h_done, sb->d_done, (size_t)a * sizeof(int));
+      ramd_d2h(cb->h_done, cb->d_done, (size_t)a * sizeof(int));
       ramd_dsync();
       int running = 0;
       for (int j = 0; j < a; j++) {
-        running += sb->h_done[j] == 0;
+        running += cb->h_done[j] == 0;
       }
       if (!running) {
         break;
@@ -295,64 +190,42 @@ static int continue_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *pla
     }
     const RamdFwdCall call = {.row0 = r0, .nrows = a, .rows_built = 1};
     ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
-    rows = a;
+    fed = a;
   }
-  ramd_d2h(sb->h_text, sb->d_text, (size_t)n * max_len);
-  ramd_d2h(sb->h_len, sb->d_len, (size_t)n * sizeof(int));
-  ramd_d2h(sb->h_done, sb->d_done, (size_t)n * sizeof(int));
-  ramd_d2h(sb->h_rng, sb->d_rng, (size_t)n * sizeof(rand_ctx));
-  if (cs->h_out) {
-    /* every row has had a forward pass (launch 0 feeds them all), and its hidden row is the one after its last feed: a
-     * pass over a row that was not fed since recomputes that row from the same input row, and a look above ends the wave
-     * only where its launch fed no row (every row it could have fed is done) */
-    ramd_d2h(cb->h_state, states, (size_t)n * s->H * sizeof(float));
-  }
+  ramd_d2h(cb->h_text, cb->d_text, (size_t)n * max_len);
+  ramd_d2h(cb->h_len, cb->d_len, (size_t)n * sizeof(int));
+  ramd_d2h(cb->h_done, cb->d_done, (size_t)n * sizeof(int));
+  ramd_d2h(cb->h_rng, cb->d_rng, (size_t)n * sizeof(rand_ctx));
+  /* every row has had a forward pass (launch 0 feeds them all), and its hidden row is the one after its last feed: a
+   * pass over a row that was not fed since recomputes that row from the same input row, and a look above ends the wave
+   * only where its launch fed no row (every row it could have fed is done) */
+  ramd_rows_states_out(rows, n, cc->h_out ? cb->h_state : NULL);
   ramd_dsync(); /* the wave's synchronisation */
-  if (cs->h_out) {
-    texts_states_unpack(plan, w, cb->h_state, s->H, cs->h_out);
+  if (cc->h_out) {
+    texts_states_unpack(plan, w, cb->h_state, s->H, cc->h_out);
   }
   int failed = 0;
   for (int j = 0; j < n; j++) {
     const int k = plan->order[wave->row0 + j];
-    const int len = RAMD_MIN(RAMD_MAX(sb->h_len[j], 0), max_len);
-    memcpy(out + (size_t)k * max_len, sb->h_text + (size_t)j * max_len, (size_t)len);
+    const int len = RAMD_MIN(RAMD_MAX(cb->h_len[j], 0), max_len);
+    memcpy(out + (size_t)k * max_len, cb->h_text + (size_t)j * max_len, (size_t)len);
     out_lens[k] = len;
-    failed += sb->h_done[j] == 2;
-    if (cs->rng_out) {
-      cs->rng_out[k] = sb->h_rng[j];
+    failed += cb->h_done[j] == 2;
+    if (cc->rng_out) {
+      cc->rng_out[k] = cb->h_rng[j];
     }
   }
   return failed;
 }
 
-static int continue_texts(const char *who, RecurNN *net, const u8 *const *prompts, const int *prompt_lens, int n_texts,
-                          int max_len, float bias, int stop_point, int alphabet_len, int head, const ContinueStates *cs,
-                          u8 *out, int *out_lens) {
-  if (continue_texts_refused(who, net, prompts, prompt_lens, cs->rng_in ? (const void *)cs->rng_in : (const void *)cs->seeds,
-                             n_texts, max_len, alphabet_len, head, out, out_lens)) {
-    return -1;
-  }
-  if (n_texts == 0) {
-    return 0;
-  }
-  if (max_len == 0) { /* nothing to draw: lengths zeroed, generators and states as they start, no device asked for... */
-    for (int k = 0; k < n_texts; k++) {
-      out_lens[k] = 0;
-      if (cs->rng_out) {
-        cs->rng_out[k] = start_generator(cs, k);
-      }
-    }
-    /* (... unless the start state is the net's hidden row and only the device has it.  No text takes a row) */
-    if (ramd_texts_fill_rowless(net, out_lens, n_texts, 0, cs->h_in, cs->h_out)) {
-      fprintf(stderr, "librecur_amd: %s: out of memory\n", who);
-      return -1;
-    }
-    return 0;
-  }
+/* what every drawing call runs behind its refusals and its returns that ask for no device: n_texts >= 1 rows of
+ * prompt_lens[k] (with cc->first: 1) + max_len >= 2 launches each, planned, opened and run wave by wave */
+static int draw_texts(const char *who, RecurNN *net, const int *prompt_lens, int n_texts, int max_len, float bias,
+                      int stop_point, int alphabet_len, int head, const ContinueCall *cc, u8 *out, int *out_lens) {
   int *lens = ramd_zalloc((size_t)n_texts * sizeof(int)); /* what a row is planned by: the forward passes it takes, plus 1 */
   TextsPlan plan;
   for (int k = 0; k < n_texts; k++) {
-    lens[k] = prompt_lens[k] + max_len; /* at least 2: every prompt takes a row */
+    lens[k] = (cc->first ? 1 : prompt_lens[k]) + max_len; /* at least 2: every prompt takes a row */
   }
   const int unplanned = texts_plan_make(&plan, lens, NULL, n_texts, TEXTS_PLAN_WIDTH);
   free(lens);
@@ -361,56 +234,43 @@ static int continue_texts(const char *who, RecurNN *net, const u8 *const *prompt
     return -1;
   }
   const int alen = alphabet_len ? alphabet_len : net->output_size;
-  RamdEngine *e = ramd_engine_of(net);
   const int widest = plan.waves[0].nrows;
-  if (e->scratch_fwd < widest) {
-    e->scratch_fwd = widest; /* the image grows once (every net's state survives: ramd_engine_ensure_device) */
-  }
-  ramd_engine_ensure_device(e);
-  ramd_engine_need_dev(e, RNN_AMD_WEIGHTS);
-  ramd_stream_need_dev(e, net);
-  ramd_set_uniform_idx(e, e->n_streams, 0); /* forward-only rows: no ring position */
-  const int r0 = e->sh.Scap + e->n_fwd; /* the engine's scratch rows lie behind the clones' */
+  RamdRows rows;
+  ramd_rows_open(&rows, net, widest);
   size_t bytes = 0; /* of the first wave's prompts: the longest rows, and the most */
   for (int j = 0; j < widest; j++) {
     bytes += (size_t)(plan.len[j] - max_len);
   }
-  ContinueBuffers cb;
-  cb.sb.d_first = NULL;
-  cb.sb.h_len = ramd_zalloc((size_t)widest * sizeof(int));
-  cb.sb.h_done = ramd_zalloc((size_t)widest * sizeof(int));
-  cb.sb.h_rng = ramd_zalloc((size_t)widest * sizeof(rand_ctx));
-  cb.sb.h_text = ramd_zalloc((size_t)widest * max_len);
-  cb.h_prompt = ramd_zalloc(bytes);
-  cb.h_off = ramd_zalloc((size_t)widest * sizeof(unsigned long long));
-  cb.h_plen = ramd_zalloc((size_t)widest * sizeof(int));
-  cb.h_state = cs->h_in || cs->h_out ? ramd_zalloc((size_t)widest * e->sh.H * sizeof(float)) : NULL;
-  cb.sb.d_len = ramd_dev_alloc((size_t)widest * sizeof(int));
-  cb.sb.d_done = ramd_dev_alloc((size_t)widest * sizeof(int));
-  cb.sb.d_rng = ramd_dev_alloc((size_t)widest * sizeof(rand_ctx));
-  cb.sb.d_text = ramd_dev_alloc((size_t)widest * max_len);
-  cb.d_prompt = ramd_dev_alloc(bytes);
-  cb.d_off = ramd_dev_alloc((size_t)widest * sizeof(unsigned long long));
-  cb.d_plen = ramd_dev_alloc((size_t)widest * sizeof(int));
+  ContinueBuffers cb = {0};
+  cb.h_len = ramd_rows_host(&rows, (size_t)widest * sizeof(int));
+  cb.h_done = ramd_rows_host(&rows, (size_t)widest * sizeof(int));
+  cb.h_rng = ramd_rows_host(&rows, (size_t)widest * sizeof(rand_ctx));
+  cb.h_text = ramd_rows_host(&rows, (size_t)widest * max_len);
+  if (!cc->first) {
+    cb.h_prompt = ramd_rows_host(&rows, bytes);
+    cb.h_off = ramd_rows_host(&rows, (size_t)widest * sizeof(unsigned long long));
+    cb.h_plen = ramd_rows_host(&rows, (size_t)widest * sizeof(int));
+  }
+  if (cc->h_in || cc->h_out) {
+    cb.h_state = ramd_rows_host(&rows, (size_t)widest * rows.e->sh.H * sizeof(float));
+  }
+  if (cc->first) {
+    cb.d_first = ramd_rows_dev(&rows, (size_t)widest * sizeof(int));
+  }
+  cb.d_len = ramd_rows_dev(&rows, (size_t)widest * sizeof(int));
+  cb.d_done = ramd_rows_dev(&rows, (size_t)widest * sizeof(int));
+  cb.d_rng = ramd_rows_dev(&rows, (size_t)widest * sizeof(rand_ctx));
+  cb.d_text = ramd_rows_dev(&rows, (size_t)widest * max_len);
+  if (!cc->first) {
+    cb.d_prompt = ramd_rows_dev(&rows, bytes);
+    cb.d_off = ramd_rows_dev(&rows, (size_t)widest * sizeof(unsigned long long));
+    cb.d_plen = ramd_rows_dev(&rows, (size_t)widest * sizeof(int));
+  }
   int failed = 0;
   for (int w = 0; w < plan.n_waves; w++) {
-    failed += continue_wave(e, net, &plan, w, r0, prompts, cs, max_len, bias, stop_point, alen, head, &cb, out, out_lens);
+    failed += continue_wave(&rows, &plan, w, cc, max_len, bias, stop_point, alen, head, &cb, out, out_lens);
   }
-  ramd_dev_free(cb.sb.d_len);
-  ramd_dev_free(cb.sb.d_done);
-  ramd_dev_free(cb.sb.d_rng);
-  ramd_dev_free(cb.sb.d_text);
-  ramd_dev_free(cb.d_prompt);
-  ramd_dev_free(cb.d_off);
-  ramd_dev_free(cb.d_plen);
-  free(cb.sb.h_len);
-  free(cb.sb.h_done);
-  free(cb.sb.h_rng);
-  free(cb.sb.h_text);
-  free(cb.h_prompt);
-  free(cb.h_off);
-  free(cb.h_plen);
-  free(cb.h_state);
+  ramd_rows_close(&rows);
   texts_plan_free(&plan);
   if (failed) {
     fprintf(stderr, "librecur_amd: %s: %d of %d texts met the attempt cap of the draw (an output row without a total)\n",
@@ -420,21 +280,91 @@ static int continue_texts(const char *who, RecurNN *net, const u8 *const *prompt
   return 0;
 }
 
+/* every row a one-symbol prompt, first[k], on the net's hidden row: continue_rule.h's schedule for plen == 1 is the
+ * sampler's (launch 0 feeds the first symbol on hid0, launch t >= 1 draws index t - 1 and feeds the pick unless it was
+ * the last), and a plan over equal lengths keeps the caller's order in waves of TEXTS_PLAN_WIDTH */
+int rnn_amd_sample_texts(RecurNN *net, const int *first, const u64 *seeds, int n_texts, int max_len, float bias,
+                         int stop_point, int alphabet_len, int head, u8 *out, int *out_lens, rand_ctx *rng_out) {
+  const char *who = "rnn_amd_sample_texts";
+  if (sample_texts_refused(who, net, first, seeds, n_texts, max_len, alphabet_len, head, out, out_lens)) {
+    return -1;
+  }
+  if (n_texts == 0 || max_len == 0) {
+    return nothing_to_draw(seeds, n_texts, out_lens, rng_out);
+  }
+  const ContinueCall cc = {.first = first, .seeds = seeds, .rng_out = rng_out};
+  return draw_texts(who, net, NULL, n_texts, max_len, bias, stop_point, alphabet_len, head, &cc, out, out_lens);
+}
+
+static int continue_texts(const char *who, RecurNN *net, const int *prompt_lens, int n_texts, int max_len, float bias,
+                          int stop_point, int alphabet_len, int head, const ContinueCall *cc, u8 *out, int *out_lens) {
+  if (continue_texts_refused(who, net, cc->prompts, prompt_lens,
+                             cc->rng_in ? (const void *)cc->rng_in : (const void *)cc->seeds, n_texts, max_len,
+                             alphabet_len, head, out, out_lens)) {
+    return -1;
+  }
+  if (n_texts == 0) {
+    return 0;
+  }
+  if (max_len == 0) { /* nothing to draw: lengths zeroed, generators and states as they start, no device asked for... */
+    for (int k = 0; k < n_texts; k++) {
+      out_lens[k] = 0;
+      if (cc->rng_out) {
+        cc->rng_out[k] = start_generator(cc, k);
+      }
+    }
+    /* (... unless the start state is the net's hidden row and only the device has it.  No text takes a row) */
+    if (ramd_texts_fill_rowless(net, out_lens, n_texts, 0, cc->h_in, cc->h_out)) {
+      fprintf(stderr, "librecur_amd: %s: out of memory\n", who);
+      return -1;
+    }
+    return 0;
+  }
+  return draw_texts(who, net, prompt_lens, n_texts, max_len, bias, stop_point, alphabet_len, head, cc, out, out_lens);
+}
+
 int rnn_amd_continue_texts_from(RecurNN *net, const u8 *const *prompts, const int *prompt_lens, const u64 *seeds,
                                 const rand_ctx *rng_in, int n_texts, int max_len, float bias, int stop_point,
                                 int alphabet_len, int head, const float *h_in, float *h_out, u8 *out, int *out_lens,
                                 rand_ctx *rng_out) {
-  const ContinueStates cs = {.h_in = h_in, .h_out = h_out, .seeds = seeds, .rng_in = rng_in, .rng_out = rng_out};
-  return continue_texts("rnn_amd_continue_texts_from", net, prompts, prompt_lens, n_texts, max_len, bias, stop_point,
-                        alphabet_len, head, &cs, out, out_lens);
+  const ContinueCall cc = {.prompts = prompts, .h_in = h_in, .h_out = h_out, .seeds = seeds, .rng_in = rng_in,
+                             .rng_out = rng_out};
+  return continue_texts("rnn_amd_continue_texts_from", net, prompt_lens, n_texts, max_len, bias, stop_point, alphabet_len,
+                        head, &cc, out, out_lens);
 }
 
 int rnn_amd_continue_texts(RecurNN *net, const u8 *const *prompts, const int *prompt_lens, const u64 *seeds, int n_texts,
                            int max_len, float bias, int stop_point, int alphabet_len, int head, u8 *out, int *out_lens,
                            rand_ctx *rng_out) {
-  const ContinueStates cs = {.seeds = seeds, .rng_out = rng_out};
-  return continue_texts("rnn_amd_continue_texts", net, prompts, prompt_lens, n_texts, max_len, bias, stop_point, alphabet_len,
-                        head, &cs, out, out_lens);
+  const ContinueCall cc = {.prompts = prompts, .seeds = seeds, .rng_out = rng_out};
+  return continue_texts("rnn_amd_continue_texts", net, prompt_lens, n_texts, max_len, bias, stop_point, alphabet_len, head,
+                        &cc, out, out_lens);
+}
+
+/* nothing computed: every text empty */
+static void empty_texts(int n_texts, char **dest, int byte_len, int *bytes) {
+  for (int k = 0; k < n_texts; k++) {
+    if (byte_len > 0) {
+      dest[k][0] = 0;
+    }
+    bytes[k] = 0;
+  }
+}
+
+/* every prompt encoded as the alphabet says into enc[k] (the caller's to free, NULL where there is none) and plens[k];
+ * returns -1 after saying so at the first prompt that encodes to no symbol */
+static int encode_prompts(const char *who, RnnCharAlphabet *a, const char *const *prompts, const int *prompt_bytes,
+                          int n_texts, u8 **enc, int *plens) {
+  for (int k = 0; k < n_texts; k++) {
+    if (prompts[k] && prompt_bytes[k] >= 0) {
+      enc[k] = rnn_char_alloc_encoded_text(a, prompts[k], prompt_bytes[k], &plens[k], NULL, false);
+    }
+    if (plens[k] < 1) {
+      fprintf(stderr, "librecur_amd: %s: prompt %d encodes to no symbol\n", who, k);
+      return -1;
+    }
+  }
+  return 0;
 }
 
 /* rnn_char_confabulate's room rule (char_sampling.c): byte_len - (utf8 ? 5 : 1) bytes for symbols -- one may need four,
@@ -445,12 +375,7 @@ static int room_for_texts(const RnnCharAlphabet *a, int n_texts, char **dest, in
     return room;
   }
   fprintf(stderr, "insufficient space to confabulate (%d bytes)\n", byte_len);
-  for (int k = 0; k < n_texts; k++) {
-    if (byte_len > 0) {
-      dest[k][0] = 0;
-    }
-    bytes[k] = 0;
-  }
+  empty_texts(n_texts, dest, byte_len, bytes);
   return 0;
 }
 
@@ -513,23 +438,9 @@ int rnn_amd_char_continue_texts(RecurNN *net, RnnCharAlphabet *a, const char *co
   int *plens = calloc((size_t)n_texts, sizeof(int));
   int *lens = calloc((size_t)n_texts, sizeof(int)); /* (a refused call writes none) */
   u8 *syms = malloc((size_t)n_texts * RAMD_MAX(char_len, 1));
-  int r = 0;
-  for (int k = 0; k < n_texts && r == 0; k++) {
-    if (prompts[k] && prompt_bytes[k] >= 0) {
-      enc[k] = rnn_char_alloc_encoded_text(a, prompts[k], prompt_bytes[k], &plens[k], NULL, false);
-    }
-    if (plens[k] < 1) {
-      fprintf(stderr, "librecur_amd: %s: prompt %d encodes to no symbol\n", who, k);
-      r = -1;
-    }
-  }
-  if (r) { /* refused: nothing computed, every text empty */
-    for (int k = 0; k < n_texts; k++) {
-      if (byte_len > 0) {
-        dest[k][0] = 0;
-      }
-      bytes[k] = 0;
-    }
+  int r = encode_prompts(who, a, prompts, prompt_bytes, n_texts, enc, plens);
+  if (r) { /* refused */
+    empty_texts(n_texts, dest, byte_len, bytes);
   } else {
     const int room = room_for_texts(a, n_texts, dest, byte_len, bytes);
     if (room > 0) {
@@ -571,24 +482,10 @@ int rnn_amd_char_score_and_continue_texts(RecurNN *net, RnnCharAlphabet *a, cons
   int *plens = calloc((size_t)n_texts, sizeof(int));
   int *lens = calloc((size_t)rows, sizeof(int)); /* (a refused call writes none) */
   u8 *syms = malloc((size_t)rows * RAMD_MAX(char_len, 1));
-  int r = 0;
-  for (int k = 0; k < n_texts && r == 0; k++) {
-    if (prompts[k] && prompt_bytes[k] >= 0) {
-      enc[k] = rnn_char_alloc_encoded_text(a, prompts[k], prompt_bytes[k], &plens[k], NULL, false);
-    }
-    if (plens[k] < 1) {
-      fprintf(stderr, "librecur_amd: %s: prompt %d encodes to no symbol\n", who, k);
-      r = -1;
-    }
-  }
+  int r = encode_prompts(who, a, prompts, prompt_bytes, n_texts, enc, plens);
   const int room = r ? 0 : room_for_texts(a, rows, dest, byte_len, bytes);
-  if (r) { /* refused: nothing computed, every text empty */
-    for (int i = 0; i < rows; i++) {
-      if (byte_len > 0) {
-        dest[i][0] = 0;
-      }
-      bytes[i] = 0;
-    }
+  if (r) { /* refused */
+    empty_texts(rows, dest, byte_len, bytes);
   } else if (room > 0) {
     float *state = malloc((size_t)n_texts * H * sizeof(float));
     float *start = malloc((size_t)rows * H * sizeof(float));

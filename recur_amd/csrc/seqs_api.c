@@ -94,20 +94,14 @@ typedef struct SeqsBuffers {
   float *h_state; /* [rows][H] the wave's states on their way in and out, or NULL */
 } SeqsBuffers;
 
-static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, int w, int r0, const SeqsCall *c,
-                     const SeqsBuffers *sb) {
+static void run_wave(const RamdRows *rows, const TextsPlan *plan, int w, const SeqsCall *c, const SeqsBuffers *sb) {
+  RamdEngine *e = rows->e;
   const RamdShape *s = &e->sh;
+  const int r0 = rows->r0;
   const TextsWave *wave = &plan->waves[w];
   const int n = wave->nrows;
   const size_t in_w = (size_t)s->input_size, out_w = (size_t)s->output_size;
-  /* every row starts from the net's hidden row, or from its own state (texts_api.c's run_wave) */
-  const float *hid0 = e->b.hidden + (size_t)ramd_state_row(e, ramd_priv(net)) * s->H;
-  float *states = e->b.hidden + (size_t)r0 * s->H;
-  if (c->h_in) {
-    texts_states_pack(plan, w, c->h_in, NULL, s->H, s->hidden_size, sb->h_state);
-    ramd_h2d(states, sb->h_state, (size_t)n * s->H * sizeof(float));
-    hid0 = NULL;
-  }
+  const float *hid0 = ramd_rows_states_in(rows, plan, w, c->h_in, sb->h_state);
   const int n_segments = seqs_plan_segments(plan, w, c->F);
   for (int q = 0; q < n_segments; q++) {
     int t0, frames, live;
@@ -140,8 +134,8 @@ static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, i
     if (c->winners) {
       ramd_d2h(sb->h_win, sb->d_win, total * (size_t)c->n_groups);
     }
-    if (c->h_out && q == n_segments - 1) { /* a row's last forward pass was its last writer */
-      ramd_d2h(sb->h_state, states, (size_t)n * s->H * sizeof(float));
+    if (q == n_segments - 1) { /* a row's last forward pass was its last writer */
+      ramd_rows_states_out(rows, n, c->h_out ? sb->h_state : NULL);
     }
     ramd_dsync(); /* the segment's one synchronisation */
     for (int j = 0; j < live; j++) {
@@ -209,53 +203,36 @@ int rnn_amd_run_sequences(RecurNN *net, const float *const *inputs, const int *n
       gap[c.n_gap++] = i;
     }
   }
-  RamdEngine *e = ramd_engine_of(net);
   const int widest = plan.waves[0].nrows;
-  if (e->scratch_fwd < widest) {
-    e->scratch_fwd = widest; /* the image grows once (every net's state survives: ramd_engine_ensure_device) */
-  }
-  ramd_engine_ensure_device(e);
-  ramd_engine_need_dev(e, RNN_AMD_WEIGHTS);
-  ramd_stream_need_dev(e, net);
-  ramd_set_uniform_idx(e, e->n_streams, 0); /* forward-only rows: no ring position */
-  const int r0 = e->sh.Scap + e->n_fwd; /* the engine's scratch rows lie behind the clones' */
+  RamdRows rows;
+  ramd_rows_open(&rows, net, widest);
   const size_t room = (size_t)seqs_plan_largest(&plan, c.F); /* frames of the largest segment */
   const size_t n_ints = (size_t)(2 * n_groups + c.n_gap);
-  c.d_goff = ramd_dev_alloc((n_ints ? n_ints : 1) * sizeof(int));
+  c.d_goff = ramd_rows_dev(&rows, (n_ints ? n_ints : 1) * sizeof(int));
   c.d_gsize = c.d_goff + n_groups;
   c.d_gap = c.d_goff + 2 * n_groups;
   if (n_ints) {
     ramd_h2d(c.d_goff, groups, n_ints * sizeof(int));
   }
   SeqsBuffers sb = {0};
-  sb.h_in = ramd_zalloc(room * (size_t)net->input_size * sizeof(float));
-  sb.d_in = ramd_dev_alloc(room * (size_t)net->input_size * sizeof(float));
-  sb.h_ans = ramd_zalloc(room * (size_t)net->output_size * sizeof(float));
-  sb.d_ans = ramd_dev_alloc(room * (size_t)net->output_size * sizeof(float));
+  sb.h_in = ramd_rows_host(&rows, room * (size_t)net->input_size * sizeof(float));
+  sb.d_in = ramd_rows_dev(&rows, room * (size_t)net->input_size * sizeof(float));
+  sb.h_ans = ramd_rows_host(&rows, room * (size_t)net->output_size * sizeof(float));
+  sb.d_ans = ramd_rows_dev(&rows, room * (size_t)net->output_size * sizeof(float));
   if (winners) {
-    sb.h_win = ramd_zalloc(room * (size_t)n_groups);
-    sb.d_win = ramd_dev_alloc(room * (size_t)n_groups);
+    sb.h_win = ramd_rows_host(&rows, room * (size_t)n_groups);
+    sb.d_win = ramd_rows_dev(&rows, room * (size_t)n_groups);
   }
-  sb.h_off = ramd_zalloc((size_t)widest * sizeof(unsigned long long));
-  sb.d_off = ramd_dev_alloc((size_t)widest * sizeof(unsigned long long));
-  sb.count = ramd_zalloc((size_t)widest * sizeof(int));
+  sb.h_off = ramd_rows_host(&rows, (size_t)widest * sizeof(unsigned long long));
+  sb.d_off = ramd_rows_dev(&rows, (size_t)widest * sizeof(unsigned long long));
+  sb.count = ramd_rows_host(&rows, (size_t)widest * sizeof(int));
   if (h_in || h_out) {
-    sb.h_state = ramd_zalloc((size_t)widest * e->sh.H * sizeof(float));
+    sb.h_state = ramd_rows_host(&rows, (size_t)widest * rows.e->sh.H * sizeof(float));
   }
   for (int w = 0; w < plan.n_waves; w++) {
-    run_wave(e, net, &plan, w, r0, &c, &sb);
+    run_wave(&rows, &plan, w, &c, &sb);
   }
-  ramd_dev_free(c.d_goff);
-  ramd_dev_free(sb.d_in);
-  ramd_dev_free(sb.d_ans);
-  ramd_dev_free(sb.d_win);
-  ramd_dev_free(sb.d_off);
-  free(sb.h_in);
-  free(sb.h_ans);
-  free(sb.h_win);
-  free(sb.h_off);
-  free(sb.count);
-  free(sb.h_state);
+  ramd_rows_close(&rows);
   free(lens);
   free(groups);
   free(covered);

@@ -1,7 +1,8 @@
 /* texts_api.c -- many texts against one net in one batched device run (gnu11 C): rnn_amd_run_texts and
  * rnn_amd_run_texts_heads, the set form of rnn_amd_run_text / _heads (net_api.c), and rnn_amd_trace_texts, which hands
  * back per symbol what those add up (k_texts_trace in k_texts_step's place).  Where those feed one net a symbol per
- * launch sequence, these give every text a forward-only state row of the engine's own and run the rows together: which
+ * launch sequence, these give every text a forward-only state row of the engine's own (opened, and the call's staging
+ * buffers owned, by rows_host.c, which the other batched calls share) and run the rows together: which
  * text gets which row, in how many waves and with how many rows at each step is texts_plan.h's business; between two
  * forward passes of the rows there is one launch (k_texts_step, kernels_loss.hip) that scores the step just computed and
  * builds the input rows of the next.  The net the caller passes is read -- its weights, its hidden row -- and not written.
@@ -13,21 +14,6 @@
 #include "rnn_host.h"
 #include "texts_plan.h"
 #include "texts_states.h"
-
-int ramd_texts_net_refused(const char *who, const RecurNN *net, int alphabet_len) {
-  if (net->bottom_layer) {
-    /* the layer has ONE input buffer for every clone (recur-nn-init.c:345-346; RamdBuffers.blast): "independent clones
-     * of the net" is not a state the reference can be in */
-    fprintf(stderr, "librecur_amd: %s: the net has a bottom layer, whose one shared input buffer leaves independent "
-                    "clones undefined\n", who);
-    return -1;
-  }
-  if (alphabet_len && (alphabet_len < 0 || net->output_size % alphabet_len != 0)) {
-    fprintf(stderr, "librecur_amd: %s: %d outputs are not whole heads of %d\n", who, net->output_size, alphabet_len);
-    return -1;
-  }
-  return 0;
-}
 
 int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const *texts, const int *lens, int n_texts,
                            int alphabet_len, const void *out) {
@@ -48,38 +34,6 @@ int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const 
       return -1;
     }
   }
-  return 0;
-}
-
-/* net's hidden row as it stands at this moment, into row[h_size], with neither of net's copies changed: the host's where
- * that is current, else the device's, read and not adopted */
-void ramd_texts_net_hidden_row(RecurNN *net, float *row) {
-  const RamdPriv *p = ramd_priv(net);
-  RamdEngine *e = p->eng;
-  if (p->host_valid || !e || !e->dev_ready) {
-    memcpy(row, net->hidden_layer, (size_t)net->h_size * sizeof(float));
-    return;
-  }
-  ramd_d2h(row, e->b.hidden + (size_t)ramd_state_row(e, p) * e->sh.H, (size_t)e->sh.H * sizeof(float));
-  ramd_dsync();
-}
-
-/* h_out of the texts that take no row: their start state, by the host alone unless the net's hidden row is wanted (h_in
- * NULL) and only the device has it.  Returns 0, or -1 out of memory */
-int ramd_texts_fill_rowless(RecurNN *net, const int *lens, int n_texts, int n_rows, const float *h_in, float *h_out) {
-  if (!h_out || n_rows == n_texts) {
-    return 0;
-  }
-  float *row = NULL;
-  if (!h_in) {
-    row = malloc((size_t)net->h_size * sizeof(float));
-    if (!row) {
-      return -1;
-    }
-    ramd_texts_net_hidden_row(net, row);
-  }
-  texts_states_fill_rowless(lens, n_texts, h_in, row, net->h_size, net->hidden_size, h_out);
-  free(row);
   return 0;
 }
 
@@ -110,9 +64,11 @@ typedef struct TextsBuffers {
   float *h_state; /* [rows][H] the wave's states on their way in and out, or NULL */
 } TextsBuffers;
 
-static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, int w, const u8 *const *texts, int r0,
-                     int alphabet_len, int n_sums, const TextsBuffers *tb, const TextsWanted *want) {
+static void run_wave(const RamdRows *rows, const TextsPlan *plan, int w, const u8 *const *texts, int alphabet_len,
+                     int n_sums, const TextsBuffers *tb, const TextsWanted *want) {
+  RamdEngine *e = rows->e;
   const RamdShape *s = &e->sh;
+  const int r0 = rows->r0;
   const TextsWave *wave = &plan->waves[w];
   const int n = wave->nrows;
   const int alen = alphabet_len ? alphabet_len : s->output_size;
@@ -135,16 +91,7 @@ static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, i
     ramd_h2d(tb->d_off_tr, tb->h_off_tr, (size_t)n * sizeof(unsigned long long));
     d_guess = want->guess ? tb->d_trace + traced * sizeof(float) : NULL;
   }
-  /* every row starts from the net's hidden row: the first launch builds the input rows from it.  Or from its own state:
-   * the wave's rows of h_in go into the state rows, which are contiguous, and the first launch reads them there as every
-   * later one does */
-  const float *hid0 = e->b.hidden + (size_t)ramd_state_row(e, ramd_priv(net)) * s->H;
-  float *states = e->b.hidden + (size_t)r0 * s->H;
-  if (want->h_in) {
-    texts_states_pack(plan, w, want->h_in, NULL, s->H, s->hidden_size, tb->h_state);
-    ramd_h2d(states, tb->h_state, (size_t)n * s->H * sizeof(float));
-    hid0 = NULL;
-  }
+  const float *hid0 = ramd_rows_states_in(rows, plan, w, want->h_in, tb->h_state);
   int scored = 0; /* a(t - 1): the rows whose step t - 1 waits to be scored */
   for (int t = 0; t <= wave->steps; t++) {
     const int a = t < wave->steps ? texts_plan_active(plan, w, t) : 0;
@@ -166,9 +113,8 @@ static void run_wave(RamdEngine *e, const RecurNN *net, const TextsPlan *plan, i
   } else if (want->trace) {
     ramd_d2h(tb->h_trace, tb->d_trace, traced * (sizeof(float) + (want->guess ? 1 : 0)));
   }
-  if (want->h_out) { /* a row's last forward pass was its last writer: the passes after it had fewer rows */
-    ramd_d2h(tb->h_state, states, (size_t)n * s->H * sizeof(float));
-  }
+  /* (a row's last forward pass was its last writer: the passes after it had fewer rows) */
+  ramd_rows_states_out(rows, n, want->h_out ? tb->h_state : NULL);
   ramd_dsync(); /* the wave's one synchronisation */
   if (want->h_out) {
     texts_states_unpack(plan, w, tb->h_state, s->H, want->h_out);
@@ -233,54 +179,36 @@ static int run_texts(const char *who, RecurNN *net, const u8 *const *texts, cons
       plan.skip[r] = INT_MAX; /* fed, never scored */
     }
   }
-  RamdEngine *e = ramd_engine_of(net);
   const int widest = plan.waves[0].nrows;
-  if (e->scratch_fwd < widest) {
-    e->scratch_fwd = widest; /* the image grows once (every net's state survives: ramd_engine_ensure_device) */
-  }
-  ramd_engine_ensure_device(e);
-  ramd_engine_need_dev(e, RNN_AMD_WEIGHTS);
-  ramd_stream_need_dev(e, net);
-  ramd_set_uniform_idx(e, e->n_streams, 0); /* forward-only rows: no ring position */
-  const int r0 = e->sh.Scap + e->n_fwd; /* the engine's scratch rows lie behind the clones' */
+  RamdRows rows;
+  ramd_rows_open(&rows, net, widest);
   size_t bytes = 0;
   for (int j = 0; j < widest; j++) {
     bytes += (size_t)plan.len[j];
   }
   TextsBuffers tb = {0};
-  tb.h_text = ramd_zalloc(bytes);
-  tb.h_off = ramd_zalloc((size_t)widest * sizeof(unsigned long long));
-  tb.d_text = ramd_dev_alloc(bytes);
-  tb.d_off = ramd_dev_alloc((size_t)widest * sizeof(unsigned long long));
+  tb.h_text = ramd_rows_host(&rows, bytes);
+  tb.h_off = ramd_rows_host(&rows, (size_t)widest * sizeof(unsigned long long));
+  tb.d_text = ramd_rows_dev(&rows, bytes);
+  tb.d_off = ramd_rows_dev(&rows, (size_t)widest * sizeof(unsigned long long));
   if (want->h_in || want->h_out) {
-    tb.h_state = ramd_zalloc((size_t)widest * e->sh.H * sizeof(float));
+    tb.h_state = ramd_rows_host(&rows, (size_t)widest * rows.e->sh.H * sizeof(float));
   }
   if (!want->trace) {
-    tb.h_acc = ramd_zalloc((size_t)widest * n_sums * sizeof(double));
-    tb.d_skip = ramd_dev_alloc((size_t)widest * sizeof(int));
-    tb.d_acc = ramd_dev_alloc((size_t)widest * n_sums * sizeof(double));
+    tb.h_acc = ramd_rows_host(&rows, (size_t)widest * n_sums * sizeof(double));
+    tb.d_skip = ramd_rows_dev(&rows, (size_t)widest * sizeof(int));
+    tb.d_acc = ramd_rows_dev(&rows, (size_t)widest * n_sums * sizeof(double));
   } else { /* the first wave has the most rows and the longest texts: the largest trace */
-    tb.h_off_tr = ramd_zalloc((size_t)widest * sizeof(unsigned long long));
+    tb.h_off_tr = ramd_rows_host(&rows, (size_t)widest * sizeof(unsigned long long));
     const size_t room = texts_plan_trace_offsets(&plan, 0, n_sums, tb.h_off_tr) * (sizeof(float) + (guess ? 1 : 0));
-    tb.h_trace = ramd_zalloc(room);
-    tb.d_off_tr = ramd_dev_alloc((size_t)widest * sizeof(unsigned long long));
-    tb.d_trace = ramd_dev_alloc(room);
+    tb.h_trace = ramd_rows_host(&rows, room);
+    tb.d_off_tr = ramd_rows_dev(&rows, (size_t)widest * sizeof(unsigned long long));
+    tb.d_trace = ramd_rows_dev(&rows, room);
   }
   for (int w = 0; w < plan.n_waves; w++) {
-    run_wave(e, net, &plan, w, texts, r0, alphabet_len, n_sums, &tb, want);
+    run_wave(&rows, &plan, w, texts, alphabet_len, n_sums, &tb, want);
   }
-  ramd_dev_free(tb.d_text);
-  ramd_dev_free(tb.d_off);
-  ramd_dev_free(tb.d_skip);
-  ramd_dev_free(tb.d_acc);
-  ramd_dev_free(tb.d_off_tr);
-  ramd_dev_free(tb.d_trace);
-  free(tb.h_text);
-  free(tb.h_off);
-  free(tb.h_acc);
-  free(tb.h_off_tr);
-  free(tb.h_trace);
-  free(tb.h_state);
+  ramd_rows_close(&rows);
   texts_plan_free(&plan);
   return 0;
 }

@@ -1,5 +1,5 @@
 // sample_rule_harness.cpp -- recur_amd/csrc/sample_rule.h under the host compiler alone, for tests/test_sample_rule.py: the
-// rule k_texts_sample draws a text's next symbol by, asked on the CPU.  The exponential and the generator are the oracle's
+// rule k_texts_continue draws a text's next symbol by, asked on the CPU.  The exponential and the generator are the oracle's
 // (liboracle.so: orc_fast_expf, orc_rand64, orc_init_rand64), passed to the rule as its functors.
 //
 //   sample_rule_harness BIAS SEED COUNT SCORE...      (scores as C hexadecimal floats, or "nan")

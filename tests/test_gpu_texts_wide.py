@@ -7,7 +7,7 @@ rows (row0 = Scap + n_fwd = 16 for a net with its own BPTT, 17 for its forward c
   A  42 / 1024 / 42     trained for 600 generations: the hidden GEMM with nkt = 34 and ks = 7, 5, 7, 15 as the rows fall, k_fwd_finalize
                         over that many planes
   B  73 / 99 / 3650     tests/golden/multi-text-6c34c563i73-h99-o3650.net, 50 heads of 73: output=gemm with o_ks = 1, 2, 4 and
-                        k_sum_slabs, 50 heads over the 4 waves of k_texts_step (13, 13, 12, 12), k_texts_sample on head 49
+                        k_sum_slabs, 50 heads over the 4 waves of k_texts_step (13, 13, 12, 12), k_texts_continue on head 49
   C  128 / 512 / 4096   seeded weights, 32 heads of 128: output=wide (k_fwd_wide writing `out` at row0) from 128 rows on, below
                         that output=gemm with o_nkt = 17
   D  4 / 64 / 4         seeded weights: output=o4 (k_out_layer_o4) from 64 rows on, output=rows at 63
@@ -434,6 +434,36 @@ def test_samples_heads_of_128(amd, n, head):
     first, seeds, texts = sampled(amd, w, net, n, max_len, 0.0, alen=128, head=head, what="C head %d of 32" % head)
     other_head(amd, net, first, seeds, texts, max_len, 0.0, 128, 31 - head)
     amd.rnn_delete_net(net)
+
+
+def test_a_first_symbol_above_255(amd):
+    """first[k] is an int in [0, input_size), not a byte: on a net of 300 inputs the symbols 256 .. 299 are fed as they
+    are.  Six texts from 0, 255, 256, 257, 298 and 299 against the oracle, drawn and greedy; then two rows from 0 and 256
+    with ONE seed, chosen on the oracle so that its two texts differ and neither has a close step: a first symbol cut to
+    its low byte would make the device's two texts equal."""
+    lib = amd
+    w = Wide(lib, start_from(lib, seeded_net(lib, 300, 40, 48, 23, 2.0), 5), None)
+    net = a_clone(lib, w)
+    first = [0, 255, 256, 257, 298, 299]
+    checked(lib, w, net, first, clean_seeds(lib, w, net, first, 8, 0.0), 8, 0.0, what="300 inputs, bias 0")
+    checked(lib, w, net, first, list(range(1, 7)), 8, 200.0, what="300 inputs, greedy")
+    o = oracle_like(lib, w, net, 1)
+    start = o.arrays()["hidden"].copy()
+    for seed in range(1, 100):
+        runs = []
+        for f in (0, 256):
+            o.arrays()["hidden"][:] = start
+            runs.append(so.free_run(o, 0, f, seed, 8, 0.0))
+        if not runs[0][1] and not runs[1][1] and not np.array_equal(runs[0][0], runs[1][0]):
+            break
+    else:
+        raise AssertionError("no seed below 100 tells symbol 0 from symbol 256 on the oracle")
+    o.close()
+    print("seed %d: the oracle from 0 %s, from 256 %s" % (seed, list(runs[0][0]), list(runs[1][0])))
+    pair, _ = checked(lib, w, net, [0, 256], [seed, seed], 8, 0.0, what="0 and 256, one seed")
+    assert not np.array_equal(pair[0], pair[1])
+    lib.rnn_delete_net(net)
+    lib.rnn_delete_net(w.net)
 
 
 @pytest.mark.parametrize("n", [64, 63])

@@ -1,5 +1,5 @@
-"""How a text's next symbol is drawn, asked of the rule itself (recur_amd/csrc/sample_rule.h, what k_texts_sample runs on
-the device) without a GPU: sample_rule_harness.cpp is compiled with g++ alone, takes the oracle's exponential and generator
+"""How a text's next symbol is drawn, asked of the rule itself (recur_amd/csrc/sample_rule.h, what k_texts_continue runs
+on the device) without a GPU: sample_rule_harness.cpp is compiled with g++ alone, takes the oracle's exponential and generator
 (liboracle.so) as the rule's functors and prints the picks and the generator for a row of scores, a bias and a seed.  The
 expected values are tests/sample_oracle.py's restatement on the oracle -- orc_softmax twice, a float32 cumulative sum,
 orc_rand_double -- and must be met bit for bit: picks, the generator's four words, the number of rand64 steps.  And the
@@ -184,4 +184,20 @@ def test_refusals_need_no_device():
     assert list(nbytes) == [0, 0] and all(b.raw[0] == 0 and b.raw[1:] == b"\x55" * 7 for b in bufs)
     lib.rnn_char_free_alphabet(alphabet)
     lib.rnn_delete_net(bottom)
+    lib.rnn_delete_net(net)
+
+
+def test_nothing_to_draw_hands_back_the_seeded_generators(orc):
+    """max_len == 0 with rng_out: lengths zeroed, no symbol written, generator k init_rand64(seeds[k]), no device asked for"""
+    lib = rc.bind_char(rc.load_amd())
+    net = lib.rnn_new(42, 39, 42, rc.FLAG_STANDARD, 1, None, 4, 1e-3, 0.9, 0.0, rc.RELU)
+    first = np.array([3, 4, 41], np.int32)
+    seeds = np.array([1, 2 ** 40 + 5, 0], np.uint64)
+    out = np.full((3, 4), 0xEE, np.uint8)
+    lens = np.full(3, -7, np.int32)
+    rng = np.full((3, 4), 0x5555, np.uint64)
+    r = lib.rnn_amd_sample_texts(net, rc.iptr(first), seeds.ctypes.data_as(C.POINTER(C.c_uint64)), 3, 0, 0.0, -1, 0, 0,
+                                 rc.u8ptr(out), rc.iptr(lens), rng.ctypes.data_as(C.POINTER(rc.RandCtx)))
+    assert r == 0 and list(lens) == [0, 0, 0] and np.all(out == 0xEE)
+    assert [tuple(int(x) for x in row) for row in rng] == [so.words(so.seeded(orc, int(s))) for s in seeds]
     lib.rnn_delete_net(net)
