@@ -4,7 +4,7 @@
  * (setup_inputs, gstrnnca.c:375-439).  Every cell gets a forward-only state row of the engine's own, cell c the row
  * r0 + c, as seqs_api.c gives every sequence one; what differs from every other batched call is that the rows are not
  * independent -- frame t + 1 of a cell reads frame t of its neighbours -- so there are no waves: all width * height rows
- * run in lock step, and between two forward passes of them there is one launch (k_automaton_step, kernels_loss.hip) that
+ * run in lock step, and between two forward passes of them there is one launch (k_automaton_step, kernels_rows.hip) that
  * paints the frame just computed into the call's device frame buffer and builds every cell's next input row from its
  * neighbours' levels.  The rule itself is automaton_rule.h's.  The frames stay on the device and come back a segment at
  * a time: one copy, one synchronisation.  The states travel in one copy each way: all rows are live and lie in the
@@ -108,7 +108,6 @@ int rnn_amd_run_automaton(RecurNN *net, const RnnAmdAutomaton *ca, const u8 *see
   ramd_rows_open(&rows, net, cells);
   RamdEngine *e = rows.e;
   const RamdShape *s = &e->sh;
-  const int r0 = rows.r0;
   /* every cell starts from the net's hidden row, or from its own state: all rows are live and lie in the caller's order */
   const float *hid0 = rows.hid0;
   if (h_in) {
@@ -119,22 +118,26 @@ int rnn_amd_run_automaton(RecurNN *net, const RnnAmdAutomaton *ca, const u8 *see
   int *d_off = ramd_rows_dev(&rows, (n_off ? n_off : 1) * sizeof(int));
   ramd_h2d(d_off, ca->offsets_y, 2 * (size_t)ca->len_y * sizeof(int));
   ramd_h2d(d_off + 2 * ca->len_y, ca->offsets_c, 2 * (size_t)ca->len_c * sizeof(int));
-  const AutomatonRule grid = {ca->width, ca->height, d_off, ca->len_y, d_off + 2 * ca->len_y, ca->len_c, ca->len_pos,
-                              ca->edges};
   u8 *d_seed = ramd_rows_dev(&rows, frame_bytes);
   u8 *d_frames = ramd_rows_dev(&rows, F * frame_bytes);
   ramd_h2d(d_seed, seed, frame_bytes);
-  const RamdFwdCall call = {.row0 = r0, .nrows = cells, .rows_built = 1};
   /* launch 0 feeds from the seed; launch t + 1 paints frame t and, unless it was the last, feeds from it */
-  ramd_launch_automaton_step(ramd_stream, s, &e->b, r0, &grid, d_seed, NULL, hid0, 1);
-  ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
+  RamdAutomatonStep step = {.g = {ca->width, ca->height, d_off, ca->len_y, d_off + 2 * ca->len_y, ca->len_c, ca->len_pos,
+                                  ca->edges},
+                            .seed = d_seed, .hid0 = hid0, .row0 = rows.r0, .feed = 1};
+  ramd_launch_automaton_step(ramd_stream, s, &e->b, &step);
+  ramd_rows_forward(&rows, cells);
+  step.seed = NULL;
+  step.hid0 = NULL;
   size_t t0 = 0; /* the segment's first frame */
   for (size_t t = 0; t < (size_t)n_frames; t++) {
     const int last = t + 1 == (size_t)n_frames;
     const size_t slot = t - t0;
-    ramd_launch_automaton_step(ramd_stream, s, &e->b, r0, &grid, NULL, d_frames + slot * frame_bytes, NULL, !last);
+    step.paint = d_frames + slot * frame_bytes;
+    step.feed = !last;
+    ramd_launch_automaton_step(ramd_stream, s, &e->b, &step);
     if (!last) {
-      ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
+      ramd_rows_forward(&rows, cells);
     }
     if (slot + 1 == F || last) {
       ramd_d2h(frames + t0 * frame_bytes, d_frames, (slot + 1) * frame_bytes);

@@ -1,5 +1,5 @@
 /* automaton_rule.h -- how rnnca's automaton makes the next frame from the last one, stated once: for k_automaton_step
- * (kernels_loss.hip), which runs it with one workgroup per cell, for automaton_api.c (gnu11 C: the refusals, the offset
+ * (kernels_rows.hip), which runs it with one workgroup per cell, for automaton_api.c (gnu11 C: the refusals, the offset
  * pattern) and for any host compiler alone (tests/automaton_rule_harness.cpp runs it under g++ against numpy and the
  * oracle).  No HIP header is needed: under hipcc the functions are host and device functions, elsewhere plain inline
  * ones.  The level rule takes the exponential as an argument, as sample_rule.h's softmax does, and is C++; the rest is C.
@@ -54,6 +54,26 @@ typedef struct AutomatonRule {
   int len_pos; /* 2 or 3 */
   int edges;   /* non-zero: clamp; 0: wrap once */
 } AutomatonRule;
+
+/* The one launch between two forward passes of rnn_amd_run_automaton (k_automaton_step, kernels_rows.hip; the launcher is
+ * declared in ramd_internal.h), for the width * height cells of g on forward-only state rows, cell c on row row0 + c; g's
+ * offset lists are device arrays, and with edges == 0 the caller has refused offsets the single wrap does not bring back.
+ * Two halves:
+ *   paint (paint != NULL; not in a call's first launch): the three levels of every cell's outputs, which the forward pass
+ *     just left in its out row, as bytes into the planes of the frame paint[3][cells].  Every byte has one writer.
+ *   feed (feed != 0; not in a call's last launch): the input row of every cell's next forward pass, from the levels of its
+ *     neighbours -- gathered from the bytes of seed[3][cells] (a call's first launch), or with a NULL seed made from the
+ *     neighbours' out rows, which is the frame this launch paints -- and the position, on the row's hidden values, or on
+ *     hid0's when that is not NULL.
+ * All pointers are device pointers. */
+typedef struct RamdAutomatonStep {
+  AutomatonRule g;           /* the grid                                                 */
+  const unsigned char *seed; /* [3][cells] the frame the first feed gathers from, or NULL */
+  unsigned char *paint;      /* [3][cells] the frame to paint, or NULL                    */
+  const float *hid0;         /* the hidden row of the first feed, or NULL                 */
+  int row0;                  /* state row of cell 0 (forward-only)                        */
+  int feed;
+} RamdAutomatonStep;
 
 RAMD_HD int automaton_input_size(const AutomatonRule *g) { return g->len_y + 2 * g->len_c + g->len_pos; }
 

@@ -1,5 +1,5 @@
 /* continue_rule.h -- what launch t of rnn_amd_continue_texts does for one row, stated once: for k_texts_continue
- * (kernels_loss.hip), which asks it per row, for the host loop around it (sample_api.c), which asks it of a wave's longest
+ * (kernels_rows.hip), which asks it per row, for the host loop around it (sample_api.c), which asks it of a wave's longest
  * row, and for any host compiler alone (tests/continue_rule_harness.cpp asks it under g++).  No HIP header is needed:
  * under hipcc the function is a host and device function, elsewhere a plain inline one.  Plain C and valid C++.
  *

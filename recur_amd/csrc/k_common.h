@@ -9,7 +9,8 @@
 //   chain     E_i[S x I]  = E_h[S x H] . W_ih^T   per BPTT step (recur-nn.c:338-376)
 //   delta     dW[I x H]   = sum_t X_t^T . diag(c_t) . E_h,t      (recur-nn.c:344-356, 738)
 // kernels_forward.hip holds the first, kernels_chain.hip the second, kernels_bptt.hip the third with
-// the rest of rnn_bptt_calc_deltas, kernels_loss.hip the callers' loss functions on the device,
+// the rest of rnn_bptt_calc_deltas, kernels_loss.hip the callers' loss functions on the device, kernels_rows.hip
+// the batched forward-only calls' one launch between two forward passes,
 // kernels_apply.hip rnn_apply_learning and the conditioning helpers.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -180,7 +181,7 @@ __device__ __forceinline__ float block_sum_256(float v, float *red) {
 // The input row of one stream, by a workgroup of 256 threads: bias, the previous hidden values from `hid`, the real
 // inputs as `mode` says (recur-nn.c:104-112: kept, a dense row, or the one-hot of `hot`), the padding as it is (zero);
 // then the emergency soft clip of the whole row (maybe_scale_inputs, recur-nn.c:68-81).  The rule is stated here once,
-// for k_assemble (kernels_forward.hip) and the feed half of k_texts_step (kernels_loss.hip).  Every thread of the
+// for k_assemble (kernels_forward.hip) and the feed halves of kernels_rows.hip.  Every thread of the
 // workgroup calls it (block_sum_256's barriers); red: 4 floats of LDS.
 __device__ __forceinline__ void assemble_input_row(const RamdShape &s, float *slot, const float *hid, int mode, int hot,
                                                    const float *dense_row, float *red) {

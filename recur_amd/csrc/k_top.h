@@ -1,9 +1,12 @@
 // k_top.h -- the callers' softmax losses and the text model's top launch as device functions: the pieces every loss kernel
-// of kernels_loss.hip is built from, and the phases k_text_top and k_text_top2 share.  (Started for the fused forward + top
-// launch that round 4 built, measured and removed: profiles/NOTES_r04.md section 2; callable pieces are what folding the
-// top layer into another launch needs.)
+// of kernels_loss.hip and every scoring kernel of kernels_rows.hip is built from, and the phases k_text_top and k_text_top2
+// share.  (Started for the fused forward + top launch that round 4 built, measured and removed: profiles/NOTES_r04.md
+// section 2; callable pieces are what folding the top layer into another launch needs.)
 #pragma once
 #include "k_common.h"
+#ifndef TT_STAMP /* (development stamps of the top launches: kernels_loss.hip defines them in a PC_STAMPS build) */
+#define TT_STAMP(i) do { } while (0)
+#endif
 
 // badmaths.h:14-29, kept operation for operation
 __device__ __forceinline__ float fast_expf_dev(float x) {
@@ -50,6 +53,15 @@ __device__ __forceinline__ float softmax_shift_of(const float *src, int n, int l
   }
   wave_minmax(lo, hi);
   return softmax_shift(lo, hi);
+}
+/* the exponentials of src[0 .. n) under that shift into ex (LDS), by one wave, lane-strided; then the caller's fence
+ * (below) between these writes and the other lanes' reads of them */
+template <class FENCE>
+__device__ __forceinline__ void wave_softmax_exps(const float *src, float *ex, int n, int lane, FENCE fence) {
+#pragma clang fp contract(off)
+  const float adj = softmax_shift_of(src, n, lane);
+  for (int i = lane; i < n; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
+  fence();
 }
 /* sum of ex[0 .. len) in index order (the reference's), the same value in every lane */
 __device__ __forceinline__ float ordered_sum(const float *ex, int len) {

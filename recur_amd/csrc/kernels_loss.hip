@@ -11,9 +11,6 @@ __device__ unsigned long long g_tt_stamps[16];
 #endif
 #include "k_top.h"
 #include "fwd_plan.h"
-#include "sample_rule.h"
-#include "continue_rule.h"
-#include "automaton_rule.h"
 BND_DECL(g_bnd_top, ramd_bnd_top_stamps)
 #pragma clang fp contract(off)
 
@@ -36,11 +33,9 @@ __global__ __launch_bounds__(64) void k_softmax_error(View v, int row0, int nrow
   const float *src = v.b.out + (size_t)r * s.O;
   float *err = v.b.o_error + (size_t)r * s.O;
   int len = s.output_size;
-  // max and min are order independent: one pass over the lanes
-  const float adj = softmax_shift_of(src, len, threadIdx.x);
-  // the exponentials in parallel, their sum in the reference's order
-  for (int i = threadIdx.x; i < len; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
-  __syncthreads();
+  // max and min are order independent: one pass over the lanes; the exponentials in parallel, their sum in the
+  // reference's order
+  wave_softmax_exps(src, ex, len, threadIdx.x, FenceBlock{});
   // every lane adds the exponentials in the reference's order (the same value in all of
   // them); the divisions and the arg max (first of equal maxima, badmaths.h:126-139) are
   // spread over the lanes
@@ -659,9 +654,7 @@ __global__ __launch_bounds__(64) void k_xent_accumulate(View v, int r, int count
   const RamdShape &s = v.sh;
   const float *src = v.b.out + (size_t)r * s.O;
   int len = s.output_size;
-  const float adj = softmax_shift_of(src, len, threadIdx.x);
-  for (int i = threadIdx.x; i < len; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
-  __syncthreads();
+  wave_softmax_exps(src, ex, len, threadIdx.x, FenceBlock{});
   if (threadIdx.x != 0 || !count_it) return;
   float e = ex[v.b.target[r]] / ordered_sum(ex, len);
   v.b.xent[r] += (double)capped_log2f_dev(e);
@@ -676,362 +669,10 @@ __global__ __launch_bounds__(64) void k_multi_xent_accumulate(View v, int r, int
   const RamdShape &s = v.sh;
   const int c = blockIdx.x;
   const float *src = v.b.out + (size_t)r * s.O + (size_t)c * alen;
-  const float adj = softmax_shift_of(src, alen, threadIdx.x);
-  for (int i = threadIdx.x; i < alen; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
-  __syncthreads();
+  wave_softmax_exps(src, ex, alen, threadIdx.x, FenceBlock{});
   if (threadIdx.x != 0 || !count_it) return;
   float e = ex[v.b.target[r]] / ordered_sum(ex, alen);
   acc[c] += (double)capped_log2f_dev(e);
-}
-
-// The one launch between two forward passes of rnn_amd_run_texts (texts_api.c): N texts of different lengths through one
-// net, a state row each, the rows ordered longest text first (texts_plan.h) so that the rows still running are a prefix.
-// One workgroup per row, two halves:
-//   score step t_score, rows [0, a_score) from the row's skip on: what k_xent_accumulate / k_multi_xent_accumulate do --
-//     softmax of the output row, or of each of its n_sums heads of alen outputs (a wave per head, the heads shared out over
-//     the waves; badmaths.h:71-111, the sum in the reference's order), capped log2 of the probability of the text's next
-//     symbol added to the row's own double(s).  An accumulator has one writer: no atomics.
-//   feed step t_feed, rows [0, a_feed): the input row of the next forward pass -- assemble_input_row with the one-hot of
-//     text[t_feed] (charmodel-helpers.h:16-33).  The hidden values come from the row's own hidden row, or, in a wave's
-//     first launch, from hid0: the hidden row of the net the texts are scored against, which every text starts from.
-// a_score == 0: a wave's first launch, which only feeds; a_feed == 0: its last, which only scores.
-struct TextsStep {
-  const unsigned char *text;     /* the wave's texts behind one another           */
-  const unsigned long long *off; /* [rows] where row j's text starts              */
-  const int *skip;               /* [rows] steps fed but not scored               */
-  double *acc;                   /* [rows][n_sums] running sums                   */
-  const float *hid0;             /* the hidden row of the first feed, or nullptr   */
-  int row0;                      /* state row of the wave's row 0 (forward-only)  */
-  int alen, n_sums;
-  int t_score, a_score, t_feed, a_feed;
-};
-constexpr int TS_WAVES = 4;
-// Where the feed half of the k_texts_*, k_seqs_step and k_automaton_step kernels takes state row r's hidden values from, stated once: from hid0 in a
-// wave's first feed (`first`) when the call has one -- the hidden row of the net, which every row then starts from --,
-// else from the row's own hidden row: what the forward pass before left there, or, with a null hid0 in the first feed,
-// the start state the host has put there (the _from calls, texts_api.c and sample_api.c).
-__device__ __forceinline__ const float *texts_feed_hidden(const View &v, int r, const float *hid0, bool first) {
-  return first && hid0 ? hid0 : v.b.hidden + (size_t)r * v.sh.H;
-}
-// The score half of k_texts_step and k_texts_trace, stated once: one wave scores one head of alen outputs at src.  The wave
-// builds the shift and the exponentials into ex (LDS, alen floats); behind the fence lane 0 takes their sum in the
-// reference's order, the likelihood of `target` (a symbol outside the head has no probability: the cap) and returns
-// capped log2 of it; the other lanes return 0.  `sum` != nullptr: every lane takes the sum -- the same LDS reads,
-// broadcast -- and leaves it there for the caller's divisions.  The caller fences before the wave's next head rewrites ex.
-__device__ __forceinline__ float texts_score_head(const float *src, float *ex, int alen, int lane, int target, float *sum) {
-  const float adj = softmax_shift_of(src, alen, lane);
-  for (int i = lane; i < alen; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
-  FenceOneWave{}();
-  if (sum) {
-    *sum = ordered_sum(ex, alen);
-    return lane == 0 ? capped_log2f_dev(target < alen ? ex[target] / *sum : 0.0f) : 0.0f;
-  }
-  if (lane == 0) {
-    const float e = target < alen ? ex[target] / ordered_sum(ex, alen) : 0.0f;
-    return capped_log2f_dev(e);
-  }
-  return 0.0f;
-}
-__global__ __launch_bounds__(64 * TS_WAVES) void k_texts_step(View v, TextsStep p) {
-  extern __shared__ float tex[]; /* [TS_WAVES][alen rounded up to 4] exponentials */
-  __shared__ float red[4];
-  const RamdShape &s = v.sh;
-  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned char *text = p.text + p.off[j];
-  if (j < p.a_score && p.t_score >= p.skip[j]) {
-    const int target = text[p.t_score + 1];
-    float *ex = tex + wave * ((p.alen + 3) & ~3);
-    for (int c = wave; c < p.n_sums; c += TS_WAVES) {
-      const float l = texts_score_head(v.b.out + (size_t)r * s.O + (size_t)c * p.alen, ex, p.alen, lane, target, nullptr);
-      if (lane == 0) p.acc[(size_t)j * p.n_sums + c] += (double)l;
-      FenceOneWave{}(); /* before this wave's next head rewrites ex */
-    }
-  }
-  if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
-    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_ONE_HOT, text[p.t_feed],
-                       nullptr, red);
-}
-
-// The one launch between two forward passes of rnn_amd_trace_texts (texts_api.c): k_texts_step with the floats it adds
-// handed back one by one.  The feed half is k_texts_step's.  The score half scores every row at every step (there is no
-// skip) and, instead of adding into a double, lane 0 of the head's wave stores the float at trace[off_tr[j] + t_score *
-// n_sums + c]; with `guess` the wave also takes softmax_best_guess's pick (badmaths.h:113-141: the largest likelihood after
-// the division, the lowest index among equals) -- every lane offers ex[i] / sum for its outputs in ascending order, lanes
-// beyond alen offer nothing -- and lane 0 stores it as a byte at the same index.  Row j is scored at every t < len_j - 1,
-// so every traced entry is written exactly once, by one writer: no atomics and no memset of the trace.
-struct TextsTrace {
-  const unsigned char *text;        /* the wave's texts behind one another            */
-  const unsigned long long *off;    /* [rows] where row j's text starts               */
-  const unsigned long long *off_tr; /* [rows] where row j's trace starts, in entries  */
-  float *trace;                     /* the wave's log2 likelihoods                    */
-  unsigned char *guess;             /* the wave's best guesses, or nullptr            */
-  const float *hid0;                /* the hidden row of the first feed, or nullptr   */
-  int row0;                         /* state row of the wave's row 0 (forward-only)   */
-  int alen, n_sums;
-  int t_score, a_score, t_feed, a_feed;
-};
-__global__ __launch_bounds__(64 * TS_WAVES) void k_texts_trace(View v, TextsTrace p) {
-  extern __shared__ float tex[]; /* [TS_WAVES][alen rounded up to 4] exponentials */
-  __shared__ float red[4];
-  const RamdShape &s = v.sh;
-  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const unsigned char *text = p.text + p.off[j];
-  if (j < p.a_score) {
-    const int target = text[p.t_score + 1];
-    float *ex = tex + wave * ((p.alen + 3) & ~3);
-    const size_t at = p.off_tr[j] + (size_t)p.t_score * p.n_sums;
-    for (int c = wave; c < p.n_sums; c += TS_WAVES) {
-      const float *src = v.b.out + (size_t)r * s.O + (size_t)c * p.alen;
-      if (p.guess) {
-        float sum;
-        const float l = texts_score_head(src, ex, p.alen, lane, target, &sum);
-        BestGuess best;
-        for (int i = lane; i < p.alen; i += 64) best.offer(ex[i] / sum, i);
-        wave_best_guess(best);
-        if (lane == 0) {
-          p.trace[at + c] = l;
-          p.guess[at + c] = (unsigned char)best.i;
-        }
-      } else {
-        const float l = texts_score_head(src, ex, p.alen, lane, target, nullptr);
-        if (lane == 0) p.trace[at + c] = l;
-      }
-      FenceOneWave{}(); /* before this wave's next head rewrites ex (the guess's reads of it have returned) */
-    }
-  }
-  if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
-    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_ONE_HOT, text[p.t_feed],
-                       nullptr, red);
-}
-
-// The one launch between two forward passes of rnn_amd_run_sequences (seqs_api.c): a wave of dense feature sequences on
-// forward-only state rows, one workgroup of 256 threads per row, the rows' frames of the current segment staged behind
-// one another (seqs_plan.h: row j's frame i at in[(off[j] + i) * input_size], its answers at ans[(off[j] + i) *
-// output_size], its winners at win[(off[j] + i) * n_groups]; t_score and t_feed count within the segment).  Two halves:
-//   score frame t_score, rows [0, a_score): emit_opinions' loop body (gstclassify.c:2273-2280) on the output row the
-//     forward pass just left.  A wave per class group, the groups shared out over the waves, lane-strided so that a group
-//     may be wider than the wave: softmax of out[goff[g] .. + gsize[g]) (badmaths.h:71-111: the shift, fast_expf, the sum in
-//     the reference's order), every lane stores ex[i] / sum for its classes -- what softmax_best_guess stores, negated
-//     back -- and offers it to the best guess (badmaths.h:113-141: the largest after the division, the lowest index among
-//     equals), which lane 0 stores as a byte when winners are wanted.  The columns in no group (gap[n_gap], in ascending
-//     order; with no groups every column) are copied raw by the whole workgroup.  Every entry has one writer and is
-//     written once: no atomics and no memset.
-//   feed frame t_feed, rows [0, a_feed): the input row of the next forward pass -- assemble_input_row with the staged
-//     frame as the dense row, the emergency soft clip included; the hidden values as the text kernels take them
-//     (texts_feed_hidden).
-// a_score == 0: the first launch of a segment, which only feeds; a_feed == 0: its last, which only scores.
-struct SeqsStep {
-  const float *in;               /* the segment's staged frames                    */
-  float *ans;                    /* the segment's answers                          */
-  unsigned char *win;            /* the segment's winners, or nullptr              */
-  const unsigned long long *off; /* [rows] where row j's frames start, in frames   */
-  const int *goff, *gsize;       /* [n_groups] the class groups                    */
-  const int *gap;                /* [n_gap] the columns in no group                */
-  const float *hid0;             /* the hidden row of the first feed, or nullptr   */
-  int row0;                      /* state row of the wave's row 0 (forward-only)   */
-  int n_groups, n_gap, stride;   /* stride: a wave's floats of LDS                 */
-  int t_score, a_score, t_feed, a_feed;
-};
-__global__ __launch_bounds__(64 * TS_WAVES) void k_seqs_step(View v, SeqsStep p) {
-  extern __shared__ float tex[]; /* [TS_WAVES][stride] exponentials */
-  __shared__ float red[4];
-  const RamdShape &s = v.sh;
-  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const size_t at = (size_t)p.off[j];
-  if (j < p.a_score) {
-    const float *out = v.b.out + (size_t)r * s.O;
-    const size_t slot = at + (size_t)p.t_score;
-    float *dst = p.ans + slot * (size_t)s.output_size;
-    for (int c = threadIdx.x; c < p.n_gap; c += 64 * TS_WAVES) dst[p.gap[c]] = out[p.gap[c]];
-    float *ex = tex + wave * p.stride;
-    for (int g = wave; g < p.n_groups; g += TS_WAVES) {
-      const int o = p.goff[g], n = p.gsize[g];
-      const float *src = out + o;
-      const float adj = softmax_shift_of(src, n, lane);
-      for (int i = lane; i < n; i += 64) ex[i] = fast_expf_dev(src[i] + adj);
-      FenceOneWave{}();
-      const float sum = ordered_sum(ex, n);
-      BestGuess best;
-      for (int i = lane; i < n; i += 64) { /* (consecutive lanes, consecutive floats) */
-        const float e = ex[i] / sum;
-        dst[o + i] = e;
-        best.offer(e, i);
-      }
-      if (p.win) {
-        wave_best_guess(best);
-        if (lane == 0) p.win[slot * (size_t)p.n_groups + g] = (unsigned char)best.i;
-      }
-      FenceOneWave{}(); /* before this wave's next group rewrites ex */
-    }
-  }
-  if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
-    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_DENSE, 0,
-                       p.in + (at + (size_t)p.t_feed) * (size_t)s.input_size, red);
-}
-
-// The one launch between two forward passes of rnn_amd_run_automaton (automaton_api.c): rnnca's fill_frame
-// (gstrnnca.c:805-831) with a forward-only state row per cell, all width * height of them in lock step.  One workgroup of
-// 256 threads per cell (assemble_input_row's), the rule from automaton_rule.h, two halves:
-//   paint (paint != nullptr; not in a call's first launch): the cell's three outputs, which the forward pass just left in
-//     its out row, through the level rule into the cell's byte of the three planes of the frame at `paint`.  Three threads,
-//     a byte each: one writer per byte, no atomics and no memset.
-//   feed (feed != 0; not in a call's last launch): the cell's dense input row into LDS -- the levels of its neighbours in
-//     the frame before, the position -- and assemble_input_row with it, the emergency soft clip included; the hidden values
-//     as the text kernels take them (texts_feed_hidden).
-// A cell's feed needs its neighbours' levels of the very frame this launch paints, and those bytes are other workgroups'
-// writes of this launch: reading them back would be a race.  So the feed half does not read the frame: it reads the
-// neighbours' OUT rows, which no workgroup of this launch writes, and applies the same level function -- at most
-// len_y + 2 * len_c small evaluations per cell, and the same byte as the one painted because the rule is stated once.
-// Only a call's first launch (seed != nullptr) gathers bytes: the seed frame's, which no launch writes.
-struct AutomatonStep {
-  AutomatonRule g;            /* the grid; the offset lists are device arrays            */
-  const unsigned char *seed;  /* [3][cells] the frame the first feed gathers from, or nullptr: from the out rows */
-  unsigned char *paint;       /* [3][cells] the frame to paint, or nullptr                */
-  const float *hid0;          /* the hidden row of the first feed, or nullptr             */
-  int row0;                   /* state row of cell 0 (forward-only)                       */
-  int feed;
-};
-struct AutomatonExp {
-  __device__ __forceinline__ float operator()(float x) const { return fast_expf_dev(x); }
-};
-struct AutomatonSeedLevels { /* the frame before is bytes in memory */
-  const unsigned char *frame;
-  int cells;
-  __device__ __forceinline__ unsigned char operator()(int plane, int cell) const {
-    return frame[(size_t)plane * cells + cell];
-  }
-};
-struct AutomatonOutLevels { /* the frame before is what the cells' out rows paint */
-  const float *out; /* cell 0's out row */
-  int O;
-  __device__ __forceinline__ unsigned char operator()(int plane, int cell) const {
-    return automaton_level(out[(size_t)cell * O + plane], AutomatonExp{});
-  }
-};
-__global__ __launch_bounds__(256) void k_automaton_step(View v, AutomatonStep p) {
-  extern __shared__ float cell_in[]; /* [input_size] the cell's dense input row */
-  __shared__ float red[4];
-  const RamdShape &s = v.sh;
-  const int j = blockIdx.x, r = p.row0 + j;
-  const int cells = p.g.width * p.g.height;
-  const float *out0 = v.b.out + (size_t)p.row0 * s.O;
-  if (p.paint && threadIdx.x < 3)
-    p.paint[(size_t)threadIdx.x * cells + j] = automaton_level(out0[(size_t)j * s.O + threadIdx.x], AutomatonExp{});
-  if (p.feed) { /* (the whole workgroup: barriers) */
-    const int cx = j % p.g.width, cy = j / p.g.width;
-    if (p.seed) {
-      const AutomatonSeedLevels level = {p.seed, cells};
-      for (int i = threadIdx.x; i < s.input_size; i += 256) cell_in[i] = automaton_input(p.g, cx, cy, i, level);
-    } else {
-      const AutomatonOutLevels level = {out0, s.O};
-      for (int i = threadIdx.x; i < s.input_size; i += 256) cell_in[i] = automaton_input(p.g, cx, cy, i, level);
-    }
-    __syncthreads();
-    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_DENSE, 0, cell_in, red);
-  }
-}
-
-struct SampleWave { /* sample_rule.h's team: the 64 lanes of one wave */
-  int l;
-  __device__ __forceinline__ int lane() const { return l; }
-  __device__ __forceinline__ int stride() const { return 64; }
-  __device__ __forceinline__ void extremes(float &lo, float &hi) const { wave_minmax(lo, hi); }
-  __device__ __forceinline__ void fence() const { FenceOneWave{}(); }
-};
-struct SampleExp {
-  __device__ __forceinline__ float operator()(float x) const { return fast_expf_dev(x); }
-};
-struct SampleRand64 {
-  DevRng &g;
-  __device__ __forceinline__ unsigned long long operator()() { return dev_rand64(g); }
-};
-// The draw half of k_texts_continue: the whole of wave 0 calls it for a row that is not done.  The wave turns the row's
-// slice of the output row into the distribution in sdist (LDS, alen floats); lane 0 draws from it with rng[j], stores the
-// pick as symbol `idx` of the row's text, the count idx + 1 and the generator, and sets done[j] (1: the pick was
-// stop_point, 2: the draw met the attempt cap and nothing was stored).  Returns, in lane 0, the pick if the row runs on,
-// else -1; in the other lanes -1.
-__device__ __forceinline__ int texts_draw_and_store(const View &v, int r, int j, int lane, float *sdist, DevRng *rng,
-                                                    unsigned char *text, int *len, int *done, int alen, int head,
-                                                    int max_len, int idx, int stop_point, float bias) {
-  const float *score = v.b.out + (size_t)r * v.sh.O + (size_t)head * alen;
-  const bool greedy = bias >= SAMPLE_GREEDY_BIAS;
-  if (!greedy) sample_distribution(sdist, score, alen, bias, SampleExp{}, SampleWave{lane});
-  int hot = -1;
-  if (lane == 0) {
-    int pick;
-    if (greedy) {
-      pick = sample_greedy(score, alen);
-    } else {
-      DevRng g = rng[j];
-      SampleRand64 draw = {g};
-      pick = sample_draw(sdist, alen, draw);
-      rng[j] = g;
-    }
-    if (pick == SAMPLE_FAILED) {
-      done[j] = 2;
-    } else {
-      text[(size_t)j * max_len + idx] = (unsigned char)pick;
-      len[j] = idx + 1;
-      if (pick == stop_point) done[j] = 1;
-      else hot = pick;
-    }
-  }
-  return hot;
-}
-
-// The one launch between two forward passes of rnn_amd_continue_texts and rnn_amd_sample_texts (sample_api.c): N prompts
-// continued by one net side by side, a state row each, the rows ordered by prompt length + max_len, longest first
-// (texts_plan.h), so that the rows still running are a prefix.  The sampler's rows are one-symbol prompts: `first` is set,
-// every row's plen is 1 and its prompt symbol first[j], an int that may lie above 255.  One workgroup of 256 threads per
-// row (assemble_input_row's); what launch t is for a row -- feeding prompt symbol t, drawing text index t - plen, or
-// nothing -- is continue_rule.h's answer for the row's plen:
-//   prompt: the one-hot of the row's prompt symbol on the row's hidden values, at t == 0 on hid0's (texts_feed_hidden).  No
-//     draw, no generator.
-//   draw (a row that is not done): texts_draw_and_store -- wave 0 turns the row's slice of the output row,
-//     out[r][head * alen .. + alen), into the distribution in LDS (sample_rule.h, the wave as the team, lane-strided
-//     loops); lane 0 draws from it with the row's own generator -- p.rng, owned by the call, not b.rng -- and stores the
-//     symbol, the count and the generator.  The stop symbol ends the row (done 1), a draw that met the attempt cap fails
-//     it (done 2); its text and length are fixed from then on.  bias >= SAMPLE_GREEDY_BIAS: no draw, no generator.  The
-//     pick is fed unless it was the text's last index, the stop symbol, or a failure.
-// The symbol reaches the workgroup through LDS behind a barrier.  A row that is done or idle is not fed: its input row
-// stays what it was and the forward passes that follow recompute what they computed.  Every word has one writer: no
-// atomics.
-struct TextsContinue {
-  const unsigned char *prompt;   /* the wave's prompts behind one another             */
-  const unsigned long long *off; /* [rows] where row j's prompt starts                */
-  const int *plen;               /* [rows] its length, at least 1                     */
-  const int *first;              /* [rows] the rows' one-symbol prompts, or nullptr   */
-  DevRng *rng;                   /* [rows] the rows' generators                       */
-  unsigned char *text;           /* [rows][max_len] the symbols drawn                 */
-  int *len;                      /* [rows] how many                                   */
-  int *done;                     /* [rows] 0 running, 1 stopped, 2 failed             */
-  const float *hid0;             /* the hidden row of the first feed, or nullptr      */
-  int row0;                      /* state row of the wave's row 0 (forward-only)      */
-  int alen, head, max_len, t, stop_point;
-  float bias;
-};
-__global__ __launch_bounds__(256) void k_texts_continue(View v, TextsContinue p) {
-  extern __shared__ float sdist[]; /* [alen] the row's distribution */
-  __shared__ float red[4];
-  __shared__ int hot_sh; /* the symbol to feed, or -1 */
-  const RamdShape &s = v.sh;
-  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const ContinueStep st = continue_step(p.first ? 1 : p.plen[j], p.max_len, p.t); /* (the same in every thread) */
-  if (wave == 0) {
-    int hot = -1;
-    if (st.what == CONTINUE_PROMPT) {
-      hot = p.first ? p.first[j] : p.prompt[p.off[j] + st.index];
-    } else if (st.what == CONTINUE_DRAW && p.done[j] == 0) { /* (the same word in every lane: the wave takes one side) */
-      hot = texts_draw_and_store(v, r, j, lane, sdist, p.rng, p.text, p.len, p.done, p.alen, p.head, p.max_len, st.index,
-                                 p.stop_point, p.bias);
-    }
-    if (lane == 0) hot_sh = st.feeds ? hot : -1;
-  }
-  __syncthreads();
-  const int hot = hot_sh;
-  if (hot >= 0) /* (the whole workgroup: assemble_input_row has barriers) */
-    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, st.on_hid0), RAMD_IN_ONE_HOT, hot, nullptr,
-                       red);
 }
 
 // rnnca's loss (gstrnnca.c:701-714, train_net): fast_sigmoid_array(answer, answer, n) IN
@@ -1130,124 +771,6 @@ extern "C" void ramd_launch_multi_xent_accumulate(ramd_stream_t st_, const RamdS
   View v = make_view(sh, b);
   RAMD_LAUNCH(k_multi_xent_accumulate, dim3(n_classes), dim3(64), (size_t)alphabet_len * sizeof(float), st,
               v, row, alphabet_len, acc, count_it);
-}
-
-// What the launchers of the batched calls' kernels share.  The kernels write forward-only input rows (the automaton's also
-// reads every cell's out row): rows row0 .. row0 + rows are such rows, or abort naming `who`
-static void forward_rows_or_abort(const char *who, const RamdShape *sh, int row0, long long rows) {
-  if (rows < 1 || row0 < sh->Scap || row0 + rows > sh->Scap + sh->Fcap) {
-    fprintf(stderr, "librecur_amd: %s: rows %d .. %lld are not forward-only state rows\n", who, row0, row0 + rows);
-    abort();
-  }
-}
-// `floats` floats of LDS for KERNEL's softmax over `outputs` outputs, in bytes: they fit, or abort; above 64 KiB the
-// kernel's limit is raised
-template <auto KERNEL>
-static size_t softmax_lds_or_abort(size_t floats, int outputs) {
-  const size_t shm = floats * sizeof(float);
-  if (shm > 160 * 1024 - 64) {
-    fprintf(stderr, "librecur_amd: a softmax over %d outputs does not fit the LDS\n", outputs);
-    abort();
-  }
-  if (shm > 64 * 1024) raise_lds_limit<KERNEL>(160 * 1024 - 64);
-  return shm;
-}
-
-extern "C" void ramd_launch_texts_step(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
-                                       const unsigned char *text, const unsigned long long *off, const int *skip,
-                                       double *acc, const float *hid0, int alphabet_len, int n_sums, int t_score,
-                                       int a_score, int t_feed, int a_feed) {
-  const int rows = a_score > a_feed ? a_score : a_feed;
-  if (rows < 1) return;
-  forward_rows_or_abort("ramd_launch_texts_step", sh, row0, rows);
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  const size_t shm = softmax_lds_or_abort<k_texts_step>((size_t)TS_WAVES * ((alphabet_len + 3) & ~3), alphabet_len);
-  TextsStep p = {text, off, skip, acc, hid0, row0, alphabet_len, n_sums, t_score, a_score, t_feed, a_feed};
-  RAMD_LAUNCH(k_texts_step, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
-}
-
-extern "C" void ramd_launch_texts_trace(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
-                                        const unsigned char *text, const unsigned long long *off,
-                                        const unsigned long long *off_tr, float *trace, unsigned char *guess,
-                                        const float *hid0, int alphabet_len, int n_sums, int t_score, int a_score,
-                                        int t_feed, int a_feed) {
-  const int rows = a_score > a_feed ? a_score : a_feed;
-  if (rows < 1) return;
-  forward_rows_or_abort("ramd_launch_texts_trace", sh, row0, rows);
-  if (alphabet_len < 1 || n_sums < 1 || (size_t)n_sums * alphabet_len > (size_t)sh->O || (a_score > 0 && t_score < 0)) {
-    fprintf(stderr, "librecur_amd: ramd_launch_texts_trace: %d heads of %d outputs in a row of %d, step %d\n", n_sums,
-            alphabet_len, sh->O, t_score);
-    abort();
-  }
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  const size_t shm = softmax_lds_or_abort<k_texts_trace>((size_t)TS_WAVES * ((alphabet_len + 3) & ~3), alphabet_len);
-  TextsTrace p = {text, off, off_tr, trace, guess, hid0, row0, alphabet_len, n_sums, t_score, a_score, t_feed, a_feed};
-  RAMD_LAUNCH(k_texts_trace, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
-}
-
-extern "C" void ramd_launch_seqs_step(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
-                                      const float *in, const unsigned long long *off, float *ans, unsigned char *win,
-                                      int n_groups, int largest, const int *goff, const int *gsize, const int *gap,
-                                      int n_gap, const float *hid0, int t_score, int a_score, int t_feed, int a_feed) {
-  const int rows = a_score > a_feed ? a_score : a_feed;
-  if (rows < 1) return;
-  forward_rows_or_abort("ramd_launch_seqs_step", sh, row0, rows);
-  if (n_groups < 0 || n_gap < 0 || largest < 0 || largest > sh->output_size || n_gap > sh->output_size ||
-      (n_groups > 0 && (!goff || !gsize || largest < 1)) || (n_gap > 0 && !gap) || (win && n_groups < 1) ||
-      (a_score > 0 && (t_score < 0 || !ans)) || (a_feed > 0 && (t_feed < 0 || !in)) || !off) {
-    fprintf(stderr, "librecur_amd: ramd_launch_seqs_step: %d groups of up to %d and %d other columns in a row of %d, "
-                    "steps %d and %d\n", n_groups, largest, n_gap, sh->output_size, t_score, t_feed);
-    abort();
-  }
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  const int stride = (largest + 3) & ~3;
-  const size_t shm = softmax_lds_or_abort<k_seqs_step>((size_t)TS_WAVES * stride, largest);
-  SeqsStep p = {in, ans, win, off, goff, gsize, gap, hid0, row0, n_groups, n_gap, stride, t_score, a_score, t_feed, a_feed};
-  RAMD_LAUNCH(k_seqs_step, dim3(rows), dim3(64 * TS_WAVES), shm, st, v, p);
-}
-
-extern "C" void ramd_launch_automaton_step(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0,
-                                           const AutomatonRule *grid, const unsigned char *seed, unsigned char *paint,
-                                           const float *hid0, int feed) {
-  const long long cells = grid->width < 1 || grid->height < 1 ? 0 : (long long)grid->width * grid->height;
-  if (!paint && !feed) return;
-  forward_rows_or_abort("ramd_launch_automaton_step", sh, row0, cells); /* (a grid without a cell has no rows) */
-  if (grid->len_y < 0 || grid->len_c < 0 || (grid->len_y > 0 && !grid->offsets_y) || (grid->len_c > 0 && !grid->offsets_c) ||
-      automaton_input_size(grid) != sh->input_size || sh->output_size < 3) {
-    fprintf(stderr, "librecur_amd: ramd_launch_automaton_step: %d + 2 * %d + %d inputs for a net of %d, %d outputs\n",
-            grid->len_y, grid->len_c, grid->len_pos, sh->input_size, sh->output_size);
-    abort();
-  }
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  const size_t shm = (size_t)((sh->input_size + 3) & ~3) * sizeof(float);
-  if (shm > 64 * 1024) {
-    fprintf(stderr, "librecur_amd: a cell's %d inputs do not fit the LDS\n", sh->input_size);
-    abort();
-  }
-  AutomatonStep p = {*grid, seed, paint, hid0, row0, feed};
-  RAMD_LAUNCH(k_automaton_step, dim3((unsigned)cells), dim3(256), shm, st, v, p);
-}
-
-extern "C" void ramd_launch_texts_continue(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
-                                           const unsigned char *prompt, const unsigned long long *off, const int *plen,
-                                           const int *first, void *rng, unsigned char *text, int *len, int *done, const float *hid0,
-                                           int alphabet_len, int head, int max_len, int t, int stop_point, float bias) {
-  if (rows < 1) return;
-  forward_rows_or_abort("ramd_launch_texts_continue", sh, row0, rows);
-  if (alphabet_len < 1 || head < 0 || (size_t)(head + 1) * alphabet_len > (size_t)sh->O || t < 0 || max_len < 1) {
-    fprintf(stderr, "librecur_amd: ramd_launch_texts_continue: head %d of %d outputs in a row of %d, step %d, texts of %d\n",
-            head, alphabet_len, sh->O, t, max_len);
-    abort();
-  }
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  const size_t shm = softmax_lds_or_abort<k_texts_continue>((size_t)((alphabet_len + 3) & ~3), alphabet_len);
-  TextsContinue p = {prompt, off, plen, first, (DevRng *)rng, text, len, done, hid0, row0, alphabet_len, head, max_len, t, stop_point, bias};
-  RAMD_LAUNCH(k_texts_continue, dim3(rows), dim3(256), shm, st, v, p);
 }
 
 extern "C" void ramd_launch_sigmoid_mse_error(ramd_stream_t st_, const RamdShape *sh,

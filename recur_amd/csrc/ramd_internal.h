@@ -240,66 +240,100 @@ void ramd_launch_multi_softmax_error(ramd_stream_t st, const RamdShape *sh, cons
 void ramd_launch_multi_xent_accumulate(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
                                        int row, int alphabet_len, int n_classes, double *acc,
                                        int count_it);
-/* the launch between two forward passes of rnn_amd_run_texts, for a wave of texts on forward-only state rows row0 ...
- * (texts_plan.h's order): scores step t_score on the wave's first a_score rows (the log2 probability of text[t_score + 1]
- * added to acc[row][n_sums], one sum for the whole output row when n_sums == 1, else one per head of alphabet_len
- * outputs; rows with skip[row] > t_score left out) and builds the input rows of step t_feed for its first a_feed rows
- * (one-hot of text[t_feed] on the row's hidden values, or on hid0's when that is not NULL).  All pointers are device
- * pointers; off[row] is where the row's text starts in `text`.  a_score or a_feed may be 0. */
-void ramd_launch_texts_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
-                            const unsigned char *text, const unsigned long long *off, const int *skip, double *acc,
-                            const float *hid0, int alphabet_len, int n_sums, int t_score, int a_score, int t_feed,
-                            int a_feed);
-/* the launch between two forward passes of rnn_amd_trace_texts: ramd_launch_texts_step without skip and without sums --
- * the float it would add for row `row`, step t_score, head c is stored at trace[off_tr[row] + t_score * n_sums + c], and
- * with guess != NULL the head's best guess (softmax_best_guess: the largest likelihood, the lowest index among equals) as
- * a byte at the same index of guess.  Every entry has one writer and is written once; nothing else of either array is
- * touched. */
-void ramd_launch_texts_trace(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
-                             const unsigned char *text, const unsigned long long *off, const unsigned long long *off_tr,
-                             float *trace, unsigned char *guess, const float *hid0, int alphabet_len, int n_sums,
-                             int t_score, int a_score, int t_feed, int a_feed);
-/* the launch between two forward passes of rnn_amd_run_sequences, for a wave of dense sequences on forward-only state
- * rows row0 ... and one segment of their frames (seqs_plan.h; off[row] is where the row's frames start in the segment's
- * staging buffers, in frames; t_score and t_feed count within the segment): for the wave's first a_score rows the
- * answers of frame t_score into ans[(off[row] + t_score) * output_size ...] -- the softmax probability within its group
- * for a column of one of the n_groups class groups (goff, gsize; `largest` the largest size), the raw output for the
- * n_gap columns listed in gap -- and, with win != NULL, softmax_best_guess's pick per group as a byte at
- * win[(off[row] + t_score) * n_groups + group]; for its first a_feed rows the input row of the next forward pass from the
- * staged frame in[(off[row] + t_feed) * input_size ...] on the row's hidden values, or on hid0's when that is not NULL.
- * All pointers are device pointers.  a_score or a_feed may be 0.  Every entry has one writer and is written once. */
-void ramd_launch_seqs_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, const float *in,
-                           const unsigned long long *off, float *ans, unsigned char *win, int n_groups, int largest,
-                           const int *goff, const int *gsize, const int *gap, int n_gap, const float *hid0, int t_score,
-                           int a_score, int t_feed, int a_feed);
-/* the launch between two forward passes of rnn_amd_run_automaton, for the width * height cells of `grid`
- * (automaton_rule.h; its offset lists are device arrays, and with edges == 0 the caller has refused offsets the single
- * wrap does not bring back) on forward-only state rows row0 ..., cell c on row row0 + c: with paint != NULL the three
- * levels of every cell's outputs as bytes into the planes of the frame paint[3][cells]; with feed != 0 the input row of
- * every cell's next forward pass, from the levels of its neighbours -- gathered from the bytes of seed[3][cells], or with
- * a NULL seed made from the neighbours' out rows, which is the frame this launch paints -- on the row's hidden values, or
- * on hid0's when that is not NULL.  All pointers are device pointers.  Every byte has one writer. */
-struct AutomatonRule;
-void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
-                                const struct AutomatonRule *grid, const unsigned char *seed, unsigned char *paint,
-                                const float *hid0, int feed);
-/* the launch between two forward passes of rnn_amd_continue_texts and rnn_amd_sample_texts, launch t = 0 .. of a wave
- * of `rows` prompts on forward-only state rows row0 ... (texts_plan.h's order for prompt length + max_len): what it does
- * for a row is continue_rule.h's continue_step(plen[row], max_len, t) --
- *   the input row of the next pass from prompt symbol t (the row's prompt starts at prompt[off[row]]; on hid0's hidden
- *   values at t == 0 unless hid0 is NULL, else on the row's own: with a NULL hid0 the caller has put the rows' start
- *   states into their hidden rows), or
- *   the draw of text index t - plen[row] of a row that is not done, from head `head` of alphabet_len outputs of its
- *   output row (sample_rule.h: the biased clamped softmax, a draw with rng[row], or the best output when bias >= 100)
- *   into text[row][max_len], counted in len[row], with done[row] set (1: it was stop_point, 2: the draw failed), and --
- *   unless the index was the last -- the input row of the next pass from the one-hot of the pick, or
+/* ---- the batched forward-only calls (kernels_rows.hip) ----
+ * Each call has ONE launch between two forward passes of its rows, and each launch is handed one struct: the host fills it
+ * once per wave or segment and sets what changes per launch; the launcher checks it and the kernel takes it by value (the
+ * text scorer's: the fields of its form).  In all of them row0 is the state row of the wave's row 0, a forward-only row (texts_plan.h's order: the rows still running
+ * are a prefix), hid0 the hidden row every row's FIRST feed is built on -- NULL: on the row's own hidden values, as every
+ * later feed is (the caller has put the rows' start states there) --, and every pointer a device pointer. */
+
+/* rnn_amd_run_texts and rnn_amd_trace_texts (texts_api.c): N texts of different lengths through one net.  Two halves:
+ *   score step t_score, rows [0, a_score): what k_xent_accumulate / k_multi_xent_accumulate do -- softmax of the output
+ *     row (n_sums == 1), or of each of its n_sums heads of alen outputs (badmaths.h:71-111, the sum in the reference's
+ *     order), capped log2 of the probability of text[t_score + 1].  The sums form (trace == NULL) adds the float to
+ *     acc[row][n_sums], leaving out the rows with skip[row] > t_score.  The trace form has no skip: it stores the float at
+ *     trace[off_tr[row] + t_score * n_sums + head] and, with guess != NULL, the head's best guess (softmax_best_guess: the
+ *     largest likelihood, the lowest index among equals) as a byte at the same index of guess.  Row j is traced at every
+ *     t < len_j - 1, so every entry has one writer and is written once; nothing else of either array is touched.
+ *   feed step t_feed, rows [0, a_feed): the input row of the next forward pass -- the one-hot of text[t_feed]
+ *     (charmodel-helpers.h:16-33) on the hidden values.
+ * a_score == 0: a wave's first launch, which only feeds; a_feed == 0: its last, which only scores. */
+typedef struct RamdTextsStep {
+  const unsigned char *text;        /* the wave's texts behind one another            */
+  const unsigned long long *off;    /* [rows] where row j's text starts               */
+  const int *skip;                  /* sums: [rows] steps fed but not scored          */
+  double *acc;                      /* sums: [rows][n_sums] running sums              */
+  const unsigned long long *off_tr; /* trace: [rows] where row j's trace starts, in entries */
+  float *trace;                     /* trace: the wave's log2 likelihoods, or NULL: the sums form */
+  unsigned char *guess;             /* trace: the wave's best guesses, or NULL        */
+  const float *hid0;
+  int row0;
+  int alen, n_sums;
+  int t_score, a_score, t_feed, a_feed;
+} RamdTextsStep;
+void ramd_launch_texts_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdTextsStep *p);
+
+/* rnn_amd_run_sequences (seqs_api.c): a wave of dense feature sequences and one segment of their frames, staged behind
+ * one another (seqs_plan.h: row j's frame i at in[(off[j] + i) * input_size], its answers at ans[(off[j] + i) *
+ * output_size], its winners at win[(off[j] + i) * n_groups]; t_score and t_feed count within the segment).  Two halves:
+ *   score frame t_score, rows [0, a_score): the softmax probability within its group for a column of one of the n_groups
+ *     class groups, the raw output for the n_gap columns in no group (with no groups every column), and with win != NULL
+ *     softmax_best_guess's pick per group as a byte.  Every entry has one writer and is written once.
+ *   feed frame t_feed, rows [0, a_feed): the input row of the next forward pass from the staged frame.
+ * a_score == 0: the first launch of a segment, which only feeds; a_feed == 0: its last, which only scores. */
+typedef struct RamdSeqsStep {
+  const float *in;               /* the segment's staged frames                    */
+  float *ans;                    /* the segment's answers                          */
+  unsigned char *win;            /* the segment's winners, or NULL                 */
+  const unsigned long long *off; /* [rows] where row j's frames start, in frames   */
+  const int *goff, *gsize;       /* [n_groups] the class groups                    */
+  const int *gap;                /* [n_gap] the columns in no group, ascending     */
+  const float *hid0;
+  int row0;
+  int n_groups, n_gap;
+  union {
+    int largest;                 /* the host's: the largest group's size                                     */
+    int stride;                  /* the kernel's: a wave's floats of LDS, which the launcher writes over it in its own copy */
+  };
+  int t_score, a_score, t_feed, a_feed;
+} RamdSeqsStep;
+void ramd_launch_seqs_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdSeqsStep *p);
+
+/* rnn_amd_run_automaton (automaton_api.c): RamdAutomatonStep stands in automaton_rule.h, next to the rule it embeds */
+struct RamdAutomatonStep;
+void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
+                                const struct RamdAutomatonStep *p);
+
+/* rnn_amd_continue_texts and rnn_amd_sample_texts (sample_api.c): launch t = 0 .. of a wave of prompts, ordered by prompt
+ * length + max_len; the launch is for the wave's first `rows` rows.  What it does for a row is continue_rule.h's
+ * continue_step(plen[row], max_len, t) --
+ *   the input row of the next pass from prompt symbol t (the row's prompt starts at prompt[off[row]]; on hid0 at t == 0
+ *   unless that is NULL), no draw, no generator, or
+ *   the draw of text index t - plen[row] of a row that is not done, from head `head` of alen outputs of its output row
+ *   (sample_rule.h: the biased clamped softmax and a draw with the row's own generator rng[row] -- the call's, not
+ *   b->rng --, or the best output when bias >= SAMPLE_GREEDY_BIAS) into text[row][max_len], counted in len[row], with
+ *   done[row] set (1: it was stop_point, 2: the draw met the attempt cap) -- the row's text and length are fixed from then
+ *   on -- and, unless the index was the last, the stop symbol or a failure, the input row of the next pass from the
+ *   one-hot of the pick, or
  *   nothing.
  * first != NULL is the sampler's form: every row's prompt is the one symbol first[row] (an int: it may lie above 255),
- * and prompt, off and plen are not read.  All pointers are device pointers; rng is [rows] rand_ctx. */
-void ramd_launch_texts_continue(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int rows,
-                                const unsigned char *prompt, const unsigned long long *off, const int *plen,
-                                const int *first, void *rng, unsigned char *text, int *len, int *done, const float *hid0,
-                                int alphabet_len, int head, int max_len, int t, int stop_point, float bias);
+ * and prompt, off and plen are not read. */
+typedef struct RamdTextsContinue {
+  const unsigned char *prompt;   /* the wave's prompts behind one another             */
+  const unsigned long long *off; /* [rows] where row j's prompt starts                */
+  const int *plen;               /* [rows] its length, at least 1                     */
+  const int *first;              /* [rows] the rows' one-symbol prompts, or NULL      */
+  void *rng;                     /* [rows] rand_ctx: the rows' generators             */
+  unsigned char *text;           /* [rows][max_len] the symbols drawn                 */
+  int *len;                      /* [rows] how many                                   */
+  int *done;                     /* [rows] 0 running, 1 stopped, 2 failed             */
+  const float *hid0;
+  int row0;
+  int alen, head, max_len, t, stop_point;
+  float bias;
+  int rows;                      /* the launch's rows (the launcher's: a workgroup each) */
+} RamdTextsContinue;
+void ramd_launch_texts_continue(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdTextsContinue *p);
 /* rnnca's loss (gstrnnca.c:701-714): sigmoid in place on the first n outputs, slope * (target -
  * a) into o_error; targets is a device array [nrows][ld] */
 void ramd_launch_sigmoid_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,

@@ -256,6 +256,8 @@ struct TextsPlan;
 const float *ramd_rows_states_in(const RamdRows *rows, const struct TextsPlan *plan, int w, const float *h_in,
                                  float *h_state);
 void ramd_rows_states_out(const RamdRows *rows, int n, float *dst);
+/* the forward pass of the call's first nrows rows, whose input rows the launch before has built */
+void ramd_rows_forward(const RamdRows *rows, int nrows);
 
 /* set_api.c */
 void ramd_set_need_training(const RnnAmdSet *set, const char *what);

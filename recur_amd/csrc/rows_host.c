@@ -3,8 +3,10 @@
  * rnn_amd_run_automaton (automaton_api.c) each give every text, sequence or cell a forward-only state row of the engine's
  * own.  Stated once here: what all of them refuse about the net, the net's hidden row for the rows that never reach the
  * device, how a call opens the rows (ramd_rows_open), how start and final states travel between the caller's arrays and
- * the rows (ramd_rows_states_in / _out; which state belongs to which row stays texts_states.h's business), and the list
- * of a call's staging buffers, freed in one place (ramd_rows_host / _dev / _close). */
+ * the rows (ramd_rows_states_in / _out; which state belongs to which row stays texts_states.h's business), the forward
+ * pass of the rows that a step kernel has fed (ramd_rows_forward), and the list of a call's staging buffers, freed in one
+ * place (ramd_rows_host / _dev / _close).  The device side of the same calls is kernels_rows.hip. */
+#define RAMD_HIP_HOST 1
 #include "rnn_host.h"
 #include "texts_states.h"
 
@@ -85,6 +87,11 @@ void ramd_rows_states_out(const RamdRows *rows, int n, float *dst) {
   if (dst) {
     ramd_d2h(dst, rows->states, (size_t)n * rows->e->sh.H * sizeof(float));
   }
+}
+
+void ramd_rows_forward(const RamdRows *rows, int nrows) {
+  const RamdFwdCall call = {.row0 = rows->r0, .nrows = nrows, .rows_built = 1};
+  ramd_launch_forward(ramd_stream, &rows->e->sh, &rows->e->b, &call, NULL, NULL);
 }
 
 static void *remember(void **list, int *n, void *p) {

@@ -4,7 +4,7 @@
  * of one net -- the output row comes back, the host draws, the generator goes out again -- these give every text a
  * forward-only state row of the engine's own (rows_host.c) and a generator of its own in a buffer of the call's, and run
  * the rows together.  The rows are laid out by prompt length + max_len (texts_plan.h, as rnn_amd_run_texts lays out its
- * texts), and between two forward passes of the rows there is one launch (k_texts_continue, kernels_loss.hip) that feeds
+ * texts), and between two forward passes of the rows there is one launch (k_texts_continue, kernels_rows.hip) that feeds
  * a row its prompt or draws its next symbol on the device (sample_rule.h) and builds the input row of the next pass from
  * it, as continue_rule.h says.  There is ONE wave loop, continue_wave, and one body behind the refusals, draw_texts:
  * the sampler hands it its first symbols as ints (they may lie above 255, so they do not travel as prompt bytes) and
@@ -139,7 +139,6 @@ static int continue_wave(const RamdRows *rows, const TextsPlan *plan, int w, con
                          int *out_lens) {
   RamdEngine *e = rows->e;
   const RamdShape *s = &e->sh;
-  const int r0 = rows->r0;
   const TextsWave *wave = &plan->waves[w];
   const int n = wave->nrows;
   size_t at = 0;
@@ -163,16 +162,20 @@ static int continue_wave(const RamdRows *rows, const TextsPlan *plan, int w, con
   ramd_h2d(cb->d_rng, cb->h_rng, (size_t)n * sizeof(rand_ctx));
   HIP_OK(hipMemsetAsync(cb->d_len, 0, (size_t)n * sizeof(int), ramd_stream));
   HIP_OK(hipMemsetAsync(cb->d_done, 0, (size_t)n * sizeof(int), ramd_stream));
-  const float *hid0 = ramd_rows_states_in(rows, plan, w, cc->h_in, cb->h_state);
+  /* (hid0 stays: the kernel takes it at t == 0 alone, continue_rule.h's on_hid0; rows: the rows launch t is for, those
+   * that were fed after launch t - 1) */
+  RamdTextsContinue step = {.prompt = cb->d_prompt, .off = cb->d_off, .plen = cb->d_plen, .first = cb->d_first,
+                            .rng = cb->d_rng, .text = cb->d_text, .len = cb->d_len, .done = cb->d_done, .row0 = rows->r0,
+                            .rows = n, .alen = alen, .head = head, .max_len = max_len, .stop_point = stop_point, .bias = bias};
+  step.hid0 = ramd_rows_states_in(rows, plan, w, cc->h_in, cb->h_state);
   const int lead = plan->len[wave->row0] - max_len; /* the wave's longest row: its launches are the wave's */
-  int fed = n;                                      /* the rows launch t is for: those that were fed after launch t - 1 */
   for (int t = 0;; t++) {
     const ContinueStep st = continue_step(lead, max_len, t);
     if (st.what == CONTINUE_IDLE) {
       break;
     }
-    ramd_launch_texts_continue(ramd_stream, s, &e->b, r0, fed, cb->d_prompt, cb->d_off, cb->d_plen, cb->d_first, cb->d_rng,
-                               cb->d_text, cb->d_len, cb->d_done, hid0, alen, head, max_len, t, stop_point, bias);
+    step.t = t;
+    ramd_launch_texts_continue(ramd_stream, s, &e->b, &step);
     if (!st.feeds) { /* the longest row's last draw */
       break;
     }
@@ -188,9 +191,8 @@ static int continue_wave(const RamdRows *rows, const TextsPlan *plan, int w, con
         break;
       }
     }
-    const RamdFwdCall call = {.row0 = r0, .nrows = a, .rows_built = 1};
-    ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
-    fed = a;
+    ramd_rows_forward(rows, a);
+    step.rows = a;
   }
   ramd_d2h(cb->h_text, cb->d_text, (size_t)n * max_len);
   ramd_d2h(cb->h_len, cb->d_len, (size_t)n * sizeof(int));

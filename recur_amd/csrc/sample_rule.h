@@ -1,5 +1,5 @@
 /* sample_rule.h -- how the next symbol of a text is drawn from a row of scores, stated once: for k_texts_continue
- * (kernels_loss.hip), which runs it with one wave per row, and for any host compiler alone (tests/sample_rule_harness.cpp
+ * (kernels_rows.hip), which runs it with one wave per row, and for any host compiler alone (tests/sample_rule_harness.cpp
  * runs it under g++ against the oracle).  No HIP header is needed: under hipcc the functions are host and device
  * functions, elsewhere plain inline ones.
  *

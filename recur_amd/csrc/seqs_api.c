@@ -3,7 +3,7 @@
  * window's features, softmax_best_guess per class group) and, without groups, of a plain loop of rnn_opinion on dense rows
  * (rnnca, parrot).  It is texts_api.c with frames where that has symbols: every sequence gets a forward-only state row of
  * the engine's own, texts_plan.h orders the rows and cuts the waves, between two forward passes of the rows there is one
- * launch (k_seqs_step, kernels_loss.hip) that turns the outputs just computed into answers and winners and builds the
+ * launch (k_seqs_step, kernels_rows.hip) that turns the outputs just computed into answers and winners and builds the
  * input rows of the next pass, and the states travel as texts_states.h says.  What differs is the staging: a frame is
  * 4 * input_size bytes, so a wave runs in segments (seqs_plan.h) -- per segment the frames of the rows that still run go up
  * in one copy, the launches run, the answers and the winners come back in one copy each, and there is one
@@ -97,11 +97,13 @@ typedef struct SeqsBuffers {
 static void run_wave(const RamdRows *rows, const TextsPlan *plan, int w, const SeqsCall *c, const SeqsBuffers *sb) {
   RamdEngine *e = rows->e;
   const RamdShape *s = &e->sh;
-  const int r0 = rows->r0;
   const TextsWave *wave = &plan->waves[w];
   const int n = wave->nrows;
   const size_t in_w = (size_t)s->input_size, out_w = (size_t)s->output_size;
-  const float *hid0 = ramd_rows_states_in(rows, plan, w, c->h_in, sb->h_state);
+  RamdSeqsStep step = {.in = sb->d_in, .ans = sb->d_ans, .win = sb->d_win, .off = sb->d_off, .goff = c->d_goff,
+                       .gsize = c->d_gsize, .gap = c->d_gap, .row0 = rows->r0, .n_groups = c->n_groups, .n_gap = c->n_gap,
+                       .largest = c->largest};
+  step.hid0 = ramd_rows_states_in(rows, plan, w, c->h_in, sb->h_state); /* (the wave's first launch: t0 + i == 0) */
   const int n_segments = seqs_plan_segments(plan, w, c->F);
   for (int q = 0; q < n_segments; q++) {
     int t0, frames, live;
@@ -119,16 +121,17 @@ static void run_wave(const RamdRows *rows, const TextsPlan *plan, int w, const S
     }
     ramd_h2d(sb->d_in, sb->h_in, total * in_w * sizeof(float));
     ramd_h2d(sb->d_off, sb->h_off, (size_t)n * sizeof(unsigned long long));
-    int scored = 0; /* the rows whose frame i - 1 waits to be scored */
+    step.a_feed = 0;
     for (int i = 0; i <= frames; i++) {
-      const int a = i < frames ? texts_plan_active(plan, w, t0 + i) : 0;
-      ramd_launch_seqs_step(ramd_stream, s, &e->b, r0, sb->d_in, sb->d_off, sb->d_ans, sb->d_win, c->n_groups, c->largest,
-                            c->d_goff, c->d_gsize, c->d_gap, c->n_gap, t0 + i == 0 ? hid0 : NULL, i - 1, scored, i, a);
-      if (a) {
-        const RamdFwdCall call = {.row0 = r0, .nrows = a, .rows_built = 1};
-        ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
+      step.t_score = i - 1;
+      step.a_score = step.a_feed; /* the rows whose frame i - 1 waits to be scored */
+      step.t_feed = i;
+      step.a_feed = i < frames ? texts_plan_active(plan, w, t0 + i) : 0;
+      ramd_launch_seqs_step(ramd_stream, s, &e->b, &step);
+      step.hid0 = NULL;
+      if (step.a_feed) {
+        ramd_rows_forward(rows, step.a_feed);
       }
-      scored = a;
     }
     ramd_d2h(sb->h_ans, sb->d_ans, total * out_w * sizeof(float));
     if (c->winners) {

@@ -1,10 +1,10 @@
 /* texts_api.c -- many texts against one net in one batched device run (gnu11 C): rnn_amd_run_texts and
  * rnn_amd_run_texts_heads, the set form of rnn_amd_run_text / _heads (net_api.c), and rnn_amd_trace_texts, which hands
- * back per symbol what those add up (k_texts_trace in k_texts_step's place).  Where those feed one net a symbol per
+ * back per symbol what those add up (k_texts_step's trace form).  Where those feed one net a symbol per
  * launch sequence, these give every text a forward-only state row of the engine's own (opened, and the call's staging
  * buffers owned, by rows_host.c, which the other batched calls share) and run the rows together: which
  * text gets which row, in how many waves and with how many rows at each step is texts_plan.h's business; between two
- * forward passes of the rows there is one launch (k_texts_step, kernels_loss.hip) that scores the step just computed and
+ * forward passes of the rows there is one launch (k_texts_step, kernels_rows.hip) that scores the step just computed and
  * builds the input rows of the next.  The net the caller passes is read -- its weights, its hidden row -- and not written.
  * The public calls are the _from forms (rnn_amd_run_texts_from, rnn_amd_trace_texts_from): every text's start state from
  * the caller's h_in and its final state into the caller's h_out, either of them NULL for "the net's hidden row" and "not
@@ -68,7 +68,6 @@ static void run_wave(const RamdRows *rows, const TextsPlan *plan, int w, const u
                      int n_sums, const TextsBuffers *tb, const TextsWanted *want) {
   RamdEngine *e = rows->e;
   const RamdShape *s = &e->sh;
-  const int r0 = rows->r0;
   const TextsWave *wave = &plan->waves[w];
   const int n = wave->nrows;
   const int alen = alphabet_len ? alphabet_len : s->output_size;
@@ -91,22 +90,21 @@ static void run_wave(const RamdRows *rows, const TextsPlan *plan, int w, const u
     ramd_h2d(tb->d_off_tr, tb->h_off_tr, (size_t)n * sizeof(unsigned long long));
     d_guess = want->guess ? tb->d_trace + traced * sizeof(float) : NULL;
   }
-  const float *hid0 = ramd_rows_states_in(rows, plan, w, want->h_in, tb->h_state);
-  int scored = 0; /* a(t - 1): the rows whose step t - 1 waits to be scored */
+  /* (the sums form leaves trace NULL, and the launcher takes its form from that) */
+  RamdTextsStep step = {.text = tb->d_text, .off = tb->d_off, .skip = tb->d_skip, .acc = tb->d_acc, .off_tr = tb->d_off_tr,
+                        .trace = want->trace ? (float *)tb->d_trace : NULL, .guess = d_guess, .row0 = rows->r0, .alen = alen,
+                        .n_sums = n_sums};
+  step.hid0 = ramd_rows_states_in(rows, plan, w, want->h_in, tb->h_state);
   for (int t = 0; t <= wave->steps; t++) {
-    const int a = t < wave->steps ? texts_plan_active(plan, w, t) : 0;
-    if (!want->trace) {
-      ramd_launch_texts_step(ramd_stream, s, &e->b, r0, tb->d_text, tb->d_off, tb->d_skip, tb->d_acc, t == 0 ? hid0 : NULL,
-                             alen, n_sums, t - 1, scored, t, a);
-    } else {
-      ramd_launch_texts_trace(ramd_stream, s, &e->b, r0, tb->d_text, tb->d_off, tb->d_off_tr, (float *)tb->d_trace, d_guess,
-                              t == 0 ? hid0 : NULL, alen, n_sums, t - 1, scored, t, a);
+    step.t_score = t - 1;
+    step.a_score = step.a_feed; /* a(t - 1): the rows whose step t - 1 waits to be scored */
+    step.t_feed = t;
+    step.a_feed = t < wave->steps ? texts_plan_active(plan, w, t) : 0;
+    ramd_launch_texts_step(ramd_stream, s, &e->b, &step);
+    step.hid0 = NULL;
+    if (step.a_feed) {
+      ramd_rows_forward(rows, step.a_feed);
     }
-    if (a) {
-      const RamdFwdCall call = {.row0 = r0, .nrows = a, .rows_built = 1};
-      ramd_launch_forward(ramd_stream, s, &e->b, &call, NULL, NULL);
-    }
-    scored = a;
   }
   if (want->sums) {
     ramd_d2h(tb->h_acc, tb->d_acc, (size_t)n * n_sums * sizeof(double));

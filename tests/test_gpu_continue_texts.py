@@ -1,5 +1,5 @@
 """Many prompts continued by one net in one batched device run (rnn_amd_continue_texts, rnn_amd_char_continue_texts;
-recur_amd/csrc/sample_api.c, continue_rule.h, k_texts_continue in kernels_loss.hip) against the oracle.
+recur_amd/csrc/sample_api.c, continue_rule.h, k_texts_continue in kernels_rows.hip) against the oracle.
 
 The comparison is TEACHER-FORCED, as tests/test_gpu_sample_texts.py's is and for its reason: oracle stream k starts from the
 net's hidden row, is fed prompt[:-1] (sample_oracle.scores_of, the scores thrown away: rnn_char_prime's loop), and then

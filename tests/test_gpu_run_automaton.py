@@ -1,5 +1,5 @@
 """rnnca's automaton played on the device (rnn_amd_run_automaton; recur_amd/csrc/automaton_api.c, automaton_rule.h,
-k_automaton_step in kernels_loss.hip) against the oracle: an OracleSet with one stream per cell, the product's weights
+k_automaton_step in kernels_rows.hip) against the oracle: an OracleSet with one stream per cell, the product's weights
 copied in (both get the same seeded numpy weights), every stream starting from the product net's hidden row or from its
 h_in row, then per frame fill_frame's loop body (gstrnnca.c:805-831): the cell's inputs gathered by a numpy restatement
 of fill_net_inputs (the vectorised twin of test_automaton_rule.input_rows, held to it below), orc_opinion with noise 0,

@@ -1,5 +1,5 @@
 """Many dense feature sequences against one net in one batched device run (rnn_amd_run_sequences;
-recur_amd/csrc/seqs_api.c, seqs_plan.h, k_seqs_step in kernels_loss.hip) against the oracle: an OracleSet with one stream
+recur_amd/csrc/seqs_api.c, seqs_plan.h, k_seqs_step in kernels_rows.hip) against the oracle: an OracleSet with one stream
 per sequence, the product's weights copied in (both get the same seeded numpy weights), every stream starting from the
 product net's hidden row or from its h_in row, then per frame orc_opinion with noise 0 and per class group orc_softmax and
 orc_softmax_best_guess -- emit_opinions' loop body (gstclassify.c:2273-2280).  A sequence's expected answers are what

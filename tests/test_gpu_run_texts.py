@@ -1,5 +1,5 @@
 """Many texts against one net in one batched device run (rnn_amd_run_texts, rnn_amd_run_texts_heads,
-rnn_amd_char_cross_entropy_texts; recur_amd/csrc/texts_api.c, texts_plan.h, k_texts_step in kernels_loss.hip) against the
+rnn_amd_char_cross_entropy_texts; recur_amd/csrc/texts_api.c, texts_plan.h, k_texts_step in kernels_rows.hip) against the
 oracle: an OracleSet with one stream per text, the product net's weights copied in, every stream's hidden row set to the
 product net's hidden row, then orc_cross_entropy (charmodel-predict.c:62-80) per stream, times -(len - skip - 1) to undo
 its division.  The bar is the project's parity bar, |got - want| <= 1e-4 |want|; where nothing is scored the sum is

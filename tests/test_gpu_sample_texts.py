@@ -1,5 +1,5 @@
 """Many texts drawn from one net in one batched device run (rnn_amd_sample_texts, rnn_amd_char_confabulate_texts;
-recur_amd/csrc/sample_api.c, sample_rule.h, k_texts_continue in kernels_loss.hip) against the oracle.
+recur_amd/csrc/sample_api.c, sample_rule.h, k_texts_continue in kernels_rows.hip) against the oracle.
 
 A sampler is discontinuous: a probability that differs in its last bit can move one draw, and every symbol after it.  So
 the comparison is TEACHER-FORCED (tests/sample_oracle.py, replay): for text k an oracle stream starts from the net's hidden

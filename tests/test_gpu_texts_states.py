@@ -1,6 +1,6 @@
 """The batched text calls with a state per text (rnn_amd_run_texts_from, rnn_amd_trace_texts_from,
 rnn_amd_continue_texts_from, rnn_amd_char_score_and_continue_texts; recur_amd/csrc/texts_api.c, sample_api.c,
-texts_states.h, the null hid0 of the k_texts_* kernels in kernels_loss.hip) on the device.
+texts_states.h, the null hid0 of the k_texts_* kernels in kernels_rows.hip) on the device.
 
 Three kinds of claim, each with the check it can bear:
   * bit for bit, where two calls run the same launches on the same values: NULL states against the plain calls; the net's

@@ -1,6 +1,6 @@
 """Many texts traced symbol by symbol in one batched device run (rnn_amd_trace_texts; recur_amd/csrc/texts_api.c,
-texts_plan.h, k_texts_trace in kernels_loss.hip) against the oracle: an OracleSet with one stream per text, the product
-net's weights copied in, every stream starting from the product net's hidden row (test_gpu_run_texts.oracle_like), then
+texts_plan.h, k_texts_step's trace form in kernels_rows.hip) against the oracle: an OracleSet with one stream per text, the
+product net's weights copied in, every stream starting from the product net's hidden row (test_gpu_run_texts.oracle_like), then
 per step orc_one_hot_opinion, orc_softmax of each head, orc_capped_log2f of the target's likelihood and
 orc_softmax_best_guess.
 

@@ -11,7 +11,7 @@ for f in $(make -s -C recur_amd/csrc print-c-srcs | sed "s/\.c//g"); do
       -I/opt/rocm/include -c recur_amd/csrc/$f.c -o build/asan/$f.o
 done
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fsanitize=address,undefined -o build/asan/librecur_amd.so $(for f in $(make -s -C recur_amd/csrc print-c-srcs | sed "s/\.c//g"); do echo build/asan/$f.o; done) \
-    build/obj/kernels_forward.o build/obj/kernels_loss.o build/obj/kernels_chain.o build/obj/kernels_bptt.o build/obj/kernels_apply.o build/obj/kernels_support.o -Wl,-rpath,/opt/rocm/lib -lm -ldl
+    build/obj/kernels_forward.o build/obj/kernels_loss.o build/obj/kernels_rows.o build/obj/kernels_chain.o build/obj/kernels_bptt.o build/obj/kernels_apply.o build/obj/kernels_support.o -Wl,-rpath,/opt/rocm/lib -lm -ldl
 export RECUR_AMD_LIB=$root/build/asan/librecur_amd.so
 export LD_PRELOAD="$(gcc -print-file-name=libasan.so):$(gcc -print-file-name=libubsan.so)"
 export ASAN_OPTIONS=detect_leaks=0:halt_on_error=0 UBSAN_OPTIONS=print_stacktrace=1
