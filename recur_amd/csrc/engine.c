@@ -328,31 +328,18 @@ RamdEngine *ramd_engine_new(RecurNN *owner) {
   e->ih_size = (size_t)owner->ih_size;
   e->ho_size = (size_t)owner->ho_size;
   e->host_valid = RNN_AMD_WEIGHTS | RNN_AMD_MOMENTUMS | RNN_AMD_DELTAS;
-  e->sp_adopted = -1;
+  noise_ahead_reset(&e->ahead);
   e->next = g_engines;
   g_engines = e;
   return e;
 }
 
-hipStream_t ramd_side_stream = NULL; /* noise_speculate's stream */
 static void engine_free_device(RamdEngine *e) {
   if (!e->dev_ready) {
     return;
   }
   RamdBuffers *b = &e->b;
-  if ((e->sp[0].pending || e->sp[1].pending) && ramd_side_stream) {
-    HIP_OK(hipStreamSynchronize(ramd_side_stream)); /* it writes into the buffers freed below */
-  }
-  for (int k = 0; k < 2; k++) {
-    e->sp[k].pending = 0;
-    ramd_dev_free(e->sp[k].noise);
-    ramd_dev_free(e->sp[k].states);
-    e->sp[k].noise = NULL;
-    e->sp[k].states = NULL;
-  }
-  e->sp_adopted = -1;
-  b->noise_spec = NULL;
-  b->rng_spec = NULL;
+  ramd_noise_ahead_free_device(e);
   ramd_dev_free(b->ih_w); ramd_dev_free(b->ho_w); ramd_dev_free(b->ih_m); ramd_dev_free(b->ho_m);
   ramd_dev_free(b->ih_aux); ramd_dev_free(b->ho_aux); ramd_dev_free(e->delta_own);
   ramd_dev_free(b->arena); ramd_dev_free(b->hidden); ramd_dev_free(b->out); ramd_dev_free(b->o_error);
@@ -400,12 +387,7 @@ void ramd_engine_delete(RamdEngine *e) {
     ramd_dsync();
   }
   engine_free_device(e);
-  if (e->spec_go) { /* noise_speculate's hand-over events */
-    HIP_OK(hipEventDestroy((hipEvent_t)e->spec_go));
-    HIP_OK(hipEventDestroy((hipEvent_t)e->sp[0].done));
-    HIP_OK(hipEventDestroy((hipEvent_t)e->sp[1].done));
-    e->spec_go = e->sp[0].done = e->sp[1].done = NULL;
-  }
+  ramd_noise_ahead_destroy(e);
   /* clones may outlive the net that owns the weights (text-predict.c:654-656 deletes the
    * training set, then its confab and validation clones): detach them so that their own
    * rnn_delete_net finds no engine instead of a freed one */
@@ -492,13 +474,10 @@ int ramd_state_row(const RamdEngine *e, const RamdPriv *p) {
 /* -------------------------------------------- host <-> device: one stream -- */
 
 /* A generator of this engine has been written from the host (a caller's draw, a per-net call's upload): nothing that was
- * generated ahead from the device's states can be right any more.  (The version numbers of the two-ahead buffers are
+ * generated ahead from the device's states can be right any more.  (The counts the two-ahead slots are stamped with are
  * PREDICTED -- one pass and one loss on -- so a different sequence of the same length, an upload instead of the loss,
- * would have been accepted: ADVICE.md round 4.) */
-void ramd_rng_written_from_host(RamdEngine *e) {
-  e->rng_version++;
-  e->sp[0].pending = e->sp[1].pending = 0;
-}
+ * would have been accepted had this only counted: ADVICE.md round 4.) */
+void ramd_rng_written_from_host(RamdEngine *e) { noise_ahead_host_write(&e->ahead); }
 
 void ramd_stream_copy(RamdEngine *e, RecurNN *net, int to_device) {
   RamdPriv *p = ramd_priv(net);

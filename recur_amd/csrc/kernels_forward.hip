@@ -110,8 +110,8 @@ __global__ void k_presynaptic_noise(View v, int row0, int nrows, float deviation
 }
 
 /* The same values without touching anything: out[j][1..H) and the generator state after them
- * (see noise_speculate in set_api.c: runs on a second stream while the rest of the previous
- * generation is still being computed) */
+ * (noise_ahead.c: runs on a second stream while the rest of the previous generation is still being
+ * computed; noise_ahead.h says when a pass may take them) */
 /* src / tclass / skip: the forms for the multi-head step -- start from the states an earlier pass left (`src`: the ones
  * the pass before adopted, or the ones the speculation before this one wrote) and first make the draws the multi-head
  * loss makes from the stream's generator in between, one per head other than the stream's own
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256) void k_fwd_finalize(View v, int row0, int nrow
 
 // the same for k_fwd_fused's result (one plane of sums for the columns inside its tiles, per-tile partial sums
 // [tn][nrows][4] for the last four columns of h_size): the set calls that go on to a generic output layer, where
-// k_text_top is not there to do it.  with_spec: the presynaptic noise generated ahead (noise_speculate) is added here
+// k_text_top is not there to do it.  with_spec: the presynaptic noise generated ahead (noise_ahead.c) is added here
 // and its generator states adopted (k_noise_apply's work).
 __global__ __launch_bounds__(256) void k_fwd_finalize_fused(View v, int row0, int nrows, int tn, int with_spec, int nmain) {
   const RamdShape &s = v.sh;

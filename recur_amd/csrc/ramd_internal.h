@@ -1,5 +1,5 @@
 /* ramd_internal.h -- private interface between the gnu11 C host code
- * (engine.c, net_api.c, set_api.c, exchange.c, rnn_init.c, rnn_io.c) and the
+ * (engine.c, net_api.c, set_api.c, noise_ahead.c, exchange.c, rnn_init.c, rnn_io.c) and the
  * HIP kernels and their launchers (kernels_*.hip).
  *
  * The C side owns residency, coherence and call order: what lives where, when
@@ -81,9 +81,9 @@ typedef struct RamdBuffers {
   /* ring position shared by every training stream of the current call, or -1
    * when they differ (set by the host before each launch) */
   int uniform_idx;
-  /* presynaptic noise generated ahead of its forward pass (see noise_speculate in set_api.c):
-   * [n][H] values and the generator states after them; noise_spec_use: the next forward adds
-   * these and adopts the states instead of running the generators */
+  /* presynaptic noise generated ahead of its forward pass (noise_ahead.c, which sets these for one
+   * pass and clears them behind it): [n][H] values and the generator states after them;
+   * noise_spec_use: the next forward adds these and adopts the states instead of running the generators */
   float *noise_spec;
   void *rng_spec;
   int noise_spec_use;
@@ -163,7 +163,7 @@ typedef struct RamdHandover {
 } RamdHandover;
 /* The pass: fwd_plan.h says which kernels, this enqueues them.  `seam` (or NULL) is called with `ctx` between the
  * hidden layer's end and the output layer where the hidden layer was the fused launch with its own finishing kernel,
- * and nowhere else (set_api.c: the multi-head step starts the next pass's noise there). */
+ * and nowhere else (set_api.c: the multi-head step offers the next pass's noise to noise_ahead.c there). */
 RamdHandover ramd_launch_forward(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdFwdCall *call,
                                  void (*seam)(void *ctx), void *ctx);
 /* the bottom layer's share of rnn_bptt_calc_deltas (recur-nn.c:377-382, 750-757) for
@@ -347,8 +347,10 @@ void ramd_set_delta_half_hook(void (*hook)(void *ctx, int half, size_t first_flo
 /* whether the last ramd_launch_calc_deltas also rebuilt the h_error / i_error images (reads and clears) */
 int ramd_calc_wrote_images(void);
 /* up to 12 word-wise copies (nwords[g] 32-bit words from src[g] to dst[g]) in one launch */
-/* the noise of the next forward pass of rows [row0, row0 + nrows), from the generators' current
- * states, into b->noise_spec / b->rng_spec; the generators themselves are not touched */
+/* the noise of a coming forward pass of rows [row0, row0 + nrows) into out_noise and the generator states after it
+ * into out_states (one of noise_ahead.c's slots), from the generators' current states or -- src_states != NULL -- from
+ * those, a loss's draws on: one per head of n_classes but the row's own loss_classes[row], or `skip` draws; the
+ * generators themselves are not touched */
 void ramd_launch_noise_speculate(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
                                  float noise, float *out_noise, void *out_states, const void *src_states,
                                  const int *loss_classes, int n_classes, int skip);

@@ -8,6 +8,7 @@
 #include <math.h>
 #include "recur_amd.h"
 #include "ramd_internal.h"
+#include "noise_ahead.h"
 
 #define RAMD_MAGIC 0x444d4152u /* "RAMD" */
 #define RAMD_HDR_FLOATS 16     /* 64-byte private header in front of net->mem */
@@ -16,6 +17,16 @@
 #define RAMD_MAX(a, b) (((a) >= (b)) ? (a) : (b))
 
 struct RamdEngine;
+
+/* noise_ahead.c's device side of noise_ahead.h's two slots: [Scap][H] values and [Scap] generator states each, the
+ * event that says slot k is filled (done[k]) and the one that orders the side stream's launches behind the main stream's
+ * work (go); all made on first use */
+typedef struct RamdNoiseAheadDev {
+  float *noise[2];
+  void *states[2];
+  void *done[2]; /* hipEvent_t */
+  void *go;      /* hipEvent_t */
+} RamdNoiseAheadDev;
 
 /* Lives in the first 64 bytes of the block net->mem points at.  The public
  * struct has no spare field (its layout is ABI), and no caller of the
@@ -81,25 +92,10 @@ typedef struct RamdEngine {
   /* rnn_bptt_clear_deltas was called and nothing has needed the zeros yet: an accumulating
    * calc_deltas that follows simply does not accumulate (ramd_deltas_materialize otherwise) */
   int deltas_zero_pending;
-  /* noise generated ahead (noise_speculate): valid while nothing else has moved the device's
-   * generators since (rng_version) */
-  unsigned long rng_version;
-  /* Two passes' worth of buffers: sp[k] holds (or is being filled with) the noise of one coming pass and the generator
-   * states after it; sp_head is the one the NEXT forward pass takes.  `version`: rng_version as it must stand when that
-   * pass begins; `assumed_classes` != 0: generated before the multi-head loss in front of it had its classes -- on the
-   * assumption that every stream's own class is one of that many heads, checked when the loss comes (multi_loss). */
-  struct {
-    float *noise;
-    void *states;
-    void *done; /* hipEvent_t */
-    int pending, row0, n, assumed_classes;
-    unsigned long version;
-    float dev;
-  } sp[2];
-  int sp_head;
-  int sp_adopted;        /* the buffer the set's last forward pass took its noise and states from, or -1 */
-  int mclass_in_range;   /* every stream's class of the last multi-head upload is one of the heads */
-  void *spec_go;         /* hipEvent_t */
+  /* presynaptic noise generated ahead of its forward pass: whether a pass may take it (noise_ahead.h, the rule), and
+   * the two slots' device buffers and hand-over events (noise_ahead.c) */
+  NoiseAhead ahead;
+  RamdNoiseAheadDev ahead_dev;
   int scalars_dev_valid; /* device mef/ih_scale newer than the host structs */
   /* this engine hosts ONE SHARD of a training set spread over the ranks of the process group
    * (rnn_amd_new_training_set_shard, rnn_amd_set_shard, or a training set opened after
@@ -126,9 +122,6 @@ struct RnnAmdSet {
   int fwd_only; /* the set is made of forward-only clones (no bptt): opinion calls only */
   int global_first, global_count;
   int counts_shard;   /* this set made the engine's streams a shard when it was opened (RamdEngine.sharded_sets counts it) */
-  /* > 0 during the multi-head step's forward pass: the number of heads whose leak decisions follow the pass, for the
-   * early noise speculation (noise_speculate_from); -1 once that has been launched */
-  int early_spec_classes;
 };
 
 static inline RamdPriv *ramd_priv(const RecurNN *net) {
@@ -142,8 +135,15 @@ static inline RamdPriv *ramd_priv(const RecurNN *net) {
 
 /* the rows' top backprop is no longer the one that was done with the loss (RamdEngine.top_done) */
 static inline void ramd_top_done_clear(RamdEngine *e) { e->top_done = 0; }
+/* ... and it has just been done with the loss, for rows [row0, row0 + n); masked: for the streams of top_done_mask only */
+static inline void ramd_top_done_set(RamdEngine *e, int row0, int n, int masked) {
+  e->top_done = 1;
+  e->top_done_row0 = row0;
+  e->top_done_n = n;
+  e->top_done_masked = masked;
+}
 
-/* The host files that call the HIP runtime themselves (engine.c, net_api.c, set_api.c, exchange.c) define
+/* The host files that call the HIP runtime themselves (engine.c, net_api.c, set_api.c, noise_ahead.c, exchange.c) define
  * RAMD_HIP_HOST before they include this header. */
 #ifdef RAMD_HIP_HOST
 #define __HIP_PLATFORM_AMD__ 1
@@ -160,7 +160,7 @@ static inline void ramd_top_done_clear(RamdEngine *e) { e->top_done = 0; }
   } while (0)
 
 extern hipStream_t ramd_stream;        /* engine.c: the library's stream (rnn_amd_use_device) */
-extern hipStream_t ramd_side_stream;   /* engine.c: noise_speculate's stream (set_api.c), or NULL */
+extern hipStream_t ramd_side_stream;   /* noise_ahead.c: the stream the noise is generated ahead on, or NULL */
 extern hipEvent_t ramd_half_summed[2]; /* exchange.c: a half's sum over the ranks has arrived (ramd_delta_half_ready) */
 #endif
 
@@ -261,6 +261,18 @@ void ramd_rows_forward(const RamdRows *rows, int nrows);
 
 /* set_api.c */
 void ramd_set_need_training(const RnnAmdSet *set, const char *what);
+
+/* noise_ahead.c: the presynaptic noise of the next forward pass, generated ahead on the side stream (the decisions are
+ * noise_ahead.h's, RamdEngine.ahead; the events that touch no device are called on that directly) */
+/* the pass of state rows [r0, r0 + n) at `level` that the caller launches next: where it may take what was generated ahead
+ * it waits for it and b.noise_spec / rng_spec / noise_spec_use say so; ramd_noise_ahead_pass_done clears them behind it */
+void ramd_noise_ahead_pass(RamdEngine *e, int r0, int n, float level);
+void ramd_noise_ahead_pass_done(RamdEngine *e);
+int ramd_noise_ahead_adopted(const RamdEngine *e); /* the set's last pass took its noise from a slot */
+/* the set's next pass may be generated for now: noise_ahead_offer's loss_classes, and its launches carried out */
+void ramd_noise_ahead_offer(RnnAmdSet *set, int loss_classes);
+void ramd_noise_ahead_free_device(RamdEngine *e); /* with the device image: the slots' buffers */
+void ramd_noise_ahead_destroy(RamdEngine *e);     /* with the engine: the events */
 
 /* exchange.c: the all-reduce overlapped with the weight-delta GEMM, for set_step (set_api.c) */
 void ramd_delta_half_ready(void *ctx, int half, size_t first_float, size_t n_floats);

@@ -1,7 +1,9 @@
 /* set_api.c -- the batched API: an RnnAmdSet drives all the streams of a training set (or a set of forward-only
  * clones) through one launch sequence per call (include/recur_amd.h; gnu11 C).  Forward passes, the losses, the delta
- * call, the presynaptic noise generated ahead, the multi-head and text calls, and the generations as ONE call
- * (set_step).  The exchange between ranks that a step may end with is exchange.c's.
+ * call, the multi-head and text calls, and the generations as ONE call (set_step).  The presynaptic noise of the next
+ * pass is generated ahead by noise_ahead.c (whether a pass may take it: noise_ahead.h); here are only the places where a
+ * pass asks for it, where it is offered, and where the loss and the classes are reported.  The exchange between ranks
+ * that a step may end with is exchange.c's.
  */
 #define RAMD_HIP_HOST 1
 #include "rnn_host.h"
@@ -165,109 +167,28 @@ void rnn_amd_set_advance(RnnAmdSet *set) {
    * launch of its own for rnn_bptt_advance's three integer operations per stream */
 }
 
-/* The presynaptic noise of the NEXT forward pass of this set, generated now on a second stream.
- * A stream's generator is a sequential recurrence -- 3 x (h_size - 1) dependent steps per pass,
- * one lane per stream, 0.2 ms for 1028 values whatever the number of streams -- so the only
- * way to take it off the generation's critical path is to run it beside something else: it is
- * launched as soon as the last draw before the next pass has been made (the multi-head loss's
- * leak decisions, or the pass itself in the text step) and runs beside the whole backward
- * pass.  It reads the generators and leaves them alone; the forward pass adds the values and
- * adopts the generator states that go with them (k_noise_apply) provided nothing has moved the
- * generators in between (rng_version: uploads of a generator, other passes, other losses),
- * otherwise it generates as before and the speculated values are dropped. */
-/* loss_classes > 0: the early form for the multi-head step, called between the forward pass and the loss.  When that
- * pass adopted the speculated states they still sit in b.rng_spec, which the loss does not touch: the generator is
- * started from there, `loss_classes` heads' worth of leak decisions on (one draw per head other than the stream's
- * own, whatever the outcome), beside the output layer and the loss instead of after them -- at 1024 / 256 / 73 x 50
- * the generator (0.31 ms beside the matrix kernels) had become the generation's critical path. */
-static void noise_speculate_from(RnnAmdSet *set, int loss_classes) {
-  RamdEngine *e = set->eng;
-  const float noise = set->nets[0]->presynaptic_noise;
-  static int enabled = -1, two_ahead = -1;
-  if (enabled < 0) {
-    const char *env = getenv("RECUR_AMD_NOISE_AHEAD");
-    enabled = !(env && atoi(env) == 0);
-    two_ahead = !(env && atoi(env) == 1); /* (1: one pass ahead only) */
-  }
-  if (noise == 0.0f || e->sh.bI || set->fwd_only || !enabled) {
-    return;
-  }
-  if (!ramd_side_stream) {
-    HIP_OK(hipStreamCreateWithFlags(&ramd_side_stream, hipStreamNonBlocking));
-    ramd_note_side_stream();
-  }
-  if (!e->spec_go) {
-    HIP_OK(hipEventCreateWithFlags((hipEvent_t *)&e->spec_go, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags((hipEvent_t *)&e->sp[0].done, hipEventDisableTiming));
-    HIP_OK(hipEventCreateWithFlags((hipEvent_t *)&e->sp[1].done, hipEventDisableTiming));
-  }
-  for (int k = 0; k < 2; k++) {
-    if (!e->sp[k].noise) {
-      e->sp[k].noise = ramd_dev_alloc((size_t)e->sh.Scap * e->sh.H * sizeof(float));
-      e->sp[k].states = ramd_dev_alloc((size_t)e->sh.Scap * sizeof(rand_ctx));
-    }
-  }
-  const int r0 = set->row0;
-  int launched = 0;
-  /* the next pass (buffer sp_head), unless an earlier call has started it already */
-  int k = e->sp_head;
-  if (!e->sp[k].pending) {
-    const int early = loss_classes > 0 && e->sp_adopted >= 0;
-    if (loss_classes > 0 && !early) {
-      return; /* (between the pass and the loss only the adopted states are safe to start from) */
-    }
-    HIP_OK(hipEventRecord((hipEvent_t)e->spec_go, ramd_stream)); /* the draws made so far, the buffers' last readers */
-    HIP_OK(hipStreamWaitEvent(ramd_side_stream, (hipEvent_t)e->spec_go, 0));
-    ramd_launch_noise_speculate(ramd_side_stream, &e->sh, &e->b, r0, set->n, noise, e->sp[k].noise, e->sp[k].states,
-                                early ? e->sp[e->sp_adopted].states : NULL, early ? e->d_mclass + r0 : NULL,
-                                early ? loss_classes : 0, 0);
-    HIP_OK(hipEventRecord((hipEvent_t)e->sp[k].done, ramd_side_stream));
-    e->sp[k].pending = 1;
-    e->sp[k].version = e->rng_version + (early ? 1 : 0); /* (the loss that follows counts as one move) */
-    e->sp[k].row0 = r0;
-    e->sp[k].n = set->n;
-    e->sp[k].dev = noise;
-    e->sp[k].assumed_classes = 0;
-    launched = 1;
-  }
-  /* ... and, in the multi-head step, the pass after it: from the states the first one leaves, past the draws of a
-   * loss whose classes nobody has yet -- one per head but the stream's own, so on the assumption that every stream's own
-   * class is one of the heads (multi_loss checks it when it comes and drops what was built on it otherwise).  The
-   * generator then runs a whole generation ahead and is off the critical path even where it is as long as the
-   * generation (32 streams per GPU). */
-  const int k2 = k ^ 1;
-  if (two_ahead && loss_classes > 0 && e->sp[k].pending && !e->sp[k2].pending && e->sp[k].row0 == r0 &&
-      e->sp[k].n == set->n && e->sp[k].dev == noise) {
-    if (!launched) {
-      HIP_OK(hipEventRecord((hipEvent_t)e->spec_go, ramd_stream)); /* buffer k2's last reader: the pass just made */
-      HIP_OK(hipStreamWaitEvent(ramd_side_stream, (hipEvent_t)e->spec_go, 0));
-    }
-    ramd_launch_noise_speculate(ramd_side_stream, &e->sh, &e->b, r0, set->n, noise, e->sp[k2].noise, e->sp[k2].states,
-                                e->sp[k].states, NULL, 0, loss_classes - 1);
-    HIP_OK(hipEventRecord((hipEvent_t)e->sp[k2].done, ramd_side_stream));
-    e->sp[k2].pending = 1;
-    e->sp[k2].version = e->sp[k].version + 2; /* one more pass and one more loss on */
-    e->sp[k2].row0 = r0;
-    e->sp[k2].n = set->n;
-    e->sp[k2].dev = noise;
-    e->sp[k2].assumed_classes = loss_classes;
-  }
-}
-static void noise_speculate(RnnAmdSet *set) { noise_speculate_from(set, 0); }
+/* The multi-head step's offer to generate the next pass's noise between its forward pass and its loss of `classes` heads
+ * (noise_ahead.c): made where the pass has its seam -- from the fused hidden layer's end on, beside the output layer and
+ * the loss -- or else right behind the pass, and only when the pass took its own noise from a slot.  offered: it has been
+ * made, so the loss makes none of its own. */
+typedef struct EarlyOffer {
+  RnnAmdSet *set;
+  int classes, offered;
+} EarlyOffer;
 
-/* the multi-head step: the next pass's noise from the fused hidden layer's end on, beside the output layer and the loss */
-static void early_speculate(void *ctx) {
-  RnnAmdSet *set = ctx;
-  if (set->early_spec_classes > 0 && set->eng->sp_adopted >= 0) {
-    noise_speculate_from(set, set->early_spec_classes);
-    set->early_spec_classes = -1; /* done */
+static void early_offer(void *ctx) {
+  EarlyOffer *o = ctx;
+  if (!o->offered && ramd_noise_ahead_adopted(o->set->eng)) {
+    ramd_noise_ahead_offer(o->set, o->classes);
+    o->offered = 1;
   }
 }
 
 /* want (RAMD_FWD_*): the whole pass, or stop after the hidden layer's sums and leave them for ramd_launch_text_top /
- * ramd_launch_dense_top; returns what was left (nothing otherwise) */
-static RamdHandover set_forward(RnnAmdSet *set, int mode, const float *d_dense, int ld, int text_i,
-                                float *outputs, int advance, int want) {
+ * ramd_launch_dense_top; returns what was left (nothing otherwise).  early (or NULL): the multi-head step's offer, made at
+ * the pass's seam where it has one */
+static RamdHandover set_forward_seam(RnnAmdSet *set, int mode, const float *d_dense, int ld, int text_i,
+                                     float *outputs, int advance, int want, EarlyOffer *early) {
   RamdEngine *e = set->eng;
   ramd_top_done_clear(e);
   ramd_engine_need_dev(e, RNN_AMD_WEIGHTS);
@@ -291,26 +212,8 @@ static RamdHandover set_forward(RnnAmdSet *set, int mode, const float *d_dense, 
     e->b.dense_inputs = 0;
   }
   float noise = set->nets[0]->presynaptic_noise;
-  if (noise != 0.0f) {
-    /* values generated ahead for exactly this pass, and nothing has touched the generators since? */
-    const int k = e->sp_head;
-    e->b.noise_spec_use = e->sp[k].pending && e->sp[k].version == e->rng_version && e->sp[k].row0 == r0 &&
-                          e->sp[k].n == set->n && e->sp[k].dev == noise && !e->sh.bI;
-    e->sp_adopted = -1;
-    if (e->b.noise_spec_use) {
-      HIP_OK(hipStreamWaitEvent(ramd_stream, (hipEvent_t)e->sp[k].done, 0));
-      e->b.noise_spec = e->sp[k].noise;
-      e->b.rng_spec = e->sp[k].states;
-      e->sp[k].pending = 0;
-      e->sp_head = k ^ 1; /* (the other buffer: the pass after this one, if it has been started) */
-      e->sp_adopted = k;
-    } else {
-      e->sp[0].pending = e->sp[1].pending = 0; /* nothing that was started fits: the second one hangs on the first */
-    }
-    e->rng_version++; /* this pass moves the generators, either way */
-  } else {
-    e->sp_adopted = -1;
-  }
+  /* values generated ahead for exactly this pass, and nothing has touched the generators since? */
+  ramd_noise_ahead_pass(e, r0, set->n, noise);
   for (int j = 1; j < set->n; j++) {
     if (set->nets[j]->presynaptic_noise != noise) {
       fprintf(stderr, "librecur_amd: the nets of a set must share presynaptic_noise\n");
@@ -321,14 +224,19 @@ static RamdHandover set_forward(RnnAmdSet *set, int mode, const float *d_dense, 
   const RamdFwdCall call = {.row0 = r0, .nrows = set->n, .mode = mode, .dense = d_dense, .ld = ld, .text_i = text_i,
                             .global_first = set->global_first, .global_count = set->global_count, .advance = advance,
                             .noise = noise, .fwd_only = set->fwd_only, .want = want};
-  const RamdHandover left = ramd_launch_forward(ramd_stream, &e->sh, &e->b, &call, early_speculate, set);
-  e->b.noise_spec_use = 0;
+  const RamdHandover left = ramd_launch_forward(ramd_stream, &e->sh, &e->b, &call, early ? early_offer : NULL, early);
+  ramd_noise_ahead_pass_done(e);
   set_streams_dev_wrote(set);
   if (outputs) {
     ramd_d2h(outputs, e->b.out + (size_t)r0 * e->sh.O, (size_t)set->n * e->sh.O * sizeof(float));
     ramd_dsync();
   }
   return left;
+}
+
+static RamdHandover set_forward(RnnAmdSet *set, int mode, const float *d_dense, int ld, int text_i,
+                                float *outputs, int advance, int want) {
+  return set_forward_seam(set, mode, d_dense, ld, text_i, outputs, advance, want, NULL);
 }
 
 void rnn_amd_set_opinion(RnnAmdSet *set, const float *inputs, int ld_inputs, float *outputs) {
@@ -500,6 +408,64 @@ void rnn_amd_set_calc_deltas(RnnAmdSet *set, int accumulate, RecurErrorRange *ra
   set_calc_deltas(set, accumulate, ranges, active, 0, NULL, 0, NULL);
 }
 
+/* the staging buffer of the losses' targets and class groups (d_group) has room for `bytes` */
+static void group_room(RamdEngine *e, size_t bytes) {
+  if (bytes > e->d_group_bytes) {
+    ramd_dsync();
+    ramd_dev_free(e->d_group);
+    e->d_group = ramd_dev_alloc(bytes);
+    e->d_group_bytes = bytes;
+  }
+}
+
+/* The class groups of gstclassify's loss on the device, for its launch: every group lies within the outputs (or the call
+ * aborts), then one staging block -- offsets, sizes, targets, then the weights (or NULL) -- whose uploads are queued and
+ * leave with the caller's next flush; `inputs` (or NULL): the call's dense input rows, which travel in front of them.
+ * trained (or NULL): a stream is trained if any of its groups has a usable target. */
+typedef struct ClassGroups {
+  const int *offset, *size, *targets;
+  const float *weight;
+  int largest; /* the largest group's size */
+} ClassGroups;
+
+static ClassGroups class_groups_stage(RnnAmdSet *set, const float *inputs, int ld_inputs, int n_groups,
+                                      const int *group_offset, const int *group_size, const int *targets,
+                                      const float *error_weight, u8 *trained) {
+  RamdEngine *e = set->eng;
+  const RamdShape *s = &e->sh;
+  int largest = 1;
+  for (int i = 0; i < n_groups; i++) {
+    if (group_offset[i] < 0 || group_size[i] < 1 || group_offset[i] + group_size[i] > s->output_size) {
+      fprintf(stderr, "librecur_amd: class group %d (%d + %d) outside the %d outputs\n", i, group_offset[i],
+              group_size[i], s->output_size);
+      abort();
+    }
+    largest = RAMD_MAX(largest, group_size[i]);
+  }
+  const size_t ints = (size_t)2 * n_groups + (size_t)set->n * n_groups;
+  group_room(e, ints * sizeof(int) + (error_weight ? (size_t)s->output_size * sizeof(float) : 0));
+  int *d = (int *)e->d_group;
+  ClassGroups g = {d, d + n_groups, d + 2 * n_groups, NULL, largest};
+  if (inputs) {
+    ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), s->input_size * sizeof(float), set->n, 0);
+  }
+  ramd_upload_q(d, group_offset, n_groups * sizeof(int));
+  ramd_upload_q(d + n_groups, group_size, n_groups * sizeof(int));
+  ramd_upload_q(d + 2 * n_groups, targets, (size_t)set->n * n_groups * sizeof(int));
+  if (error_weight) {
+    g.weight = (float *)(d + ints);
+    ramd_upload_q((float *)(d + ints), error_weight, (size_t)s->output_size * sizeof(float));
+  }
+  for (int j = 0; trained && j < set->n; j++) {
+    trained[j] = 0;
+    for (int i = 0; i < n_groups; i++) {
+      int t = targets[(size_t)j * n_groups + i];
+      trained[j] |= (t >= 0 && t < group_size[i]);
+    }
+  }
+  return g;
+}
+
 /* gstclassify's loss for the whole set (gstclassify.c:2070-2119), see recur_amd.h */
 void rnn_amd_set_grouped_softmax_error(RnnAmdSet *set, int n_groups, const int *group_offset,
                                        const int *group_size, const int *targets,
@@ -507,52 +473,16 @@ void rnn_amd_set_grouped_softmax_error(RnnAmdSet *set, int n_groups, const int *
   RamdEngine *e = set->eng;
   ramd_set_need_training(set, "rnn_amd_set_grouped_softmax_error");
   ramd_top_done_clear(e);
-  const RamdShape *s = &e->sh;
-  int largest = 1;
-  for (int i = 0; i < n_groups; i++) {
-    if (group_offset[i] < 0 || group_size[i] < 1 || group_offset[i] + group_size[i] > s->output_size) {
-      fprintf(stderr, "librecur_amd: class group %d (%d + %d) outside the %d outputs\n", i,
-              group_offset[i], group_size[i], s->output_size);
-      abort();
-    }
-    largest = RAMD_MAX(largest, group_size[i]);
-  }
   set_streams_to_dev(set);
-  /* one staging block: offsets, sizes, targets, then the weights */
-  size_t ints = (size_t)2 * n_groups + (size_t)set->n * n_groups;
-  size_t bytes = ints * sizeof(int) + (error_weight ? (size_t)s->output_size * sizeof(float) : 0);
-  if (bytes > e->d_group_bytes) {
-    ramd_dsync();
-    ramd_dev_free(e->d_group);
-    e->d_group = ramd_dev_alloc(bytes);
-    e->d_group_bytes = bytes;
-  }
-  int *d = (int *)e->d_group;
-  ramd_upload_q(d, group_offset, n_groups * sizeof(int));
-  ramd_upload_q(d + n_groups, group_size, n_groups * sizeof(int));
-  ramd_upload_q(d + 2 * n_groups, targets, (size_t)set->n * n_groups * sizeof(int));
-  float *dw = NULL;
-  if (error_weight) {
-    dw = (float *)(d + ints);
-    ramd_upload_q(dw, error_weight, (size_t)s->output_size * sizeof(float));
-  }
-  if (trained) { /* a stream is trained if any of its groups has a usable target */
-    for (int j = 0; j < set->n; j++) {
-      trained[j] = 0;
-      for (int i = 0; i < n_groups; i++) {
-        int t = targets[(size_t)j * n_groups + i];
-        trained[j] |= (t >= 0 && t < group_size[i]);
-      }
-    }
-    /* the caller hands these flags to rnn_amd_set_calc_deltas next (gstclassify.c:2120-2127): they travel with this
-     * call's uploads, and that call finds them in place (active_mask_to_dev) */
-    if (set->n % 4 == 0 && !set->fwd_only) {
-      active_mask_to_dev(e, trained, set->n, 1);
-    }
+  const ClassGroups g = class_groups_stage(set, NULL, 0, n_groups, group_offset, group_size, targets, error_weight, trained);
+  /* the caller hands the flags to rnn_amd_set_calc_deltas next (gstclassify.c:2120-2127): they travel with this call's
+   * uploads, and that call finds them in place (active_mask_to_dev) */
+  if (trained && set->n % 4 == 0 && !set->fwd_only) {
+    active_mask_to_dev(e, trained, set->n, 1);
   }
   ramd_mail_in_flush();
-  ramd_launch_grouped_softmax_error(ramd_stream, s, &e->b, set->row0, set->n, n_groups, largest, d,
-                                    d + n_groups, d + 2 * n_groups, dw);
+  ramd_launch_grouped_softmax_error(ramd_stream, &e->sh, &e->b, set->row0, set->n, n_groups, g.largest, g.offset, g.size,
+                                    g.targets, g.weight);
   set_streams_dev_wrote(set);
 }
 
@@ -587,32 +517,18 @@ static int multi_heads(RamdEngine *e, int alphabet_len) {
   return n_classes;
 }
 
-/* the loss after the opinion: b.target holds each stream's next symbol */
-static void mclass_note(RamdEngine *e, const int *target_class, int n, int n_classes) {
-  int ok = 1;
-  for (int j = 0; j < n; j++) {
-    ok &= target_class[j] >= 0 && target_class[j] < n_classes;
-  }
-  e->mclass_in_range = ok;
-}
-
+/* the loss after the opinion: b.target holds each stream's next symbol.  offered: the early offer to generate the next
+ * pass's noise has been made (multi_step_deltas) */
 static void multi_loss(RnnAmdSet *set, const int *target_class, int alphabet_len, int n_classes,
-                       float leakage, int speculated) {
+                       float leakage, int offered) {
   RamdEngine *e = set->eng;
   e->mheads_alen = alphabet_len;
   e->b.mheads_alen = alphabet_len;
-  e->rng_version++; /* the leak decisions are draws from the streams' generators */
   if (target_class) {
     ramd_upload(e->d_mclass + set->row0, target_class, set->n * sizeof(int));
-    mclass_note(e, target_class, set->n, n_classes);
+    noise_ahead_classes(&e->ahead, target_class, set->n, n_classes);
   }
-  /* noise that was generated past THIS loss before its classes were known */
-  for (int k = 0; k < 2; k++) {
-    if (e->sp[k].pending && e->sp[k].assumed_classes && e->sp[k].version == e->rng_version &&
-        (e->sp[k].assumed_classes != n_classes || !e->mclass_in_range)) {
-      e->sp[0].pending = e->sp[1].pending = 0; /* (the other one hangs on it, or is the pass in between: redone) */
-    }
-  }
+  noise_ahead_loss(&e->ahead, n_classes); /* the leak decisions are draws from the streams' generators */
   /* u64 threshold = leakage * UINT64_MAX (charmodel-multi-predict.c:27): float arithmetic */
   float tf = leakage * (float)UINT64_MAX;
   unsigned long long threshold = tf >= 18446744073709551615.0f ? UINT64_MAX : (unsigned long long)tf;
@@ -621,8 +537,8 @@ static void multi_loss(RnnAmdSet *set, const int *target_class, int alphabet_len
                                   e->d_mranges + (size_t)set->row0 * MULTI_RANGE_STRIDE,
                                   MULTI_RANGE_STRIDE);
   set_streams_dev_wrote(set);
-  if (!speculated) {
-    noise_speculate(set); /* the next draws are the next forward pass's noise */
+  if (!offered) {
+    ramd_noise_ahead_offer(set, 0); /* the next draws are the next forward pass's noise */
   }
 }
 
@@ -648,18 +564,13 @@ static void multi_step_deltas(RnnAmdSet *set, const int *hot, const int *next, c
   ramd_upload_q(e->b.hot + set->row0, hot, set->n * sizeof(int));
   if (target_class) {
     ramd_upload_q(e->d_mclass + set->row0, target_class, set->n * sizeof(int));
-    mclass_note(e, target_class, set->n, n_classes);
+    noise_ahead_classes(&e->ahead, target_class, set->n, n_classes);
   }
   ramd_upload(e->b.target + set->row0, next, set->n * sizeof(int));
-  set->early_spec_classes = set->fwd_only ? 0 : n_classes; /* (early_speculate takes it up where the pass has its seam) */
-  set_forward(set, RAMD_IN_ONE_HOT, NULL, 0, 0, NULL, 1, RAMD_FWD_WHOLE);
-  int early = set->early_spec_classes < 0;
-  set->early_spec_classes = 0;
-  if (!early && e->sp_adopted >= 0 && !set->fwd_only) {
-    noise_speculate_from(set, n_classes);
-    early = 1;
-  }
-  multi_loss(set, NULL, alphabet_len, n_classes, leakage, early);
+  EarlyOffer early = {set, n_classes, 0};
+  set_forward_seam(set, RAMD_IN_ONE_HOT, NULL, 0, 0, NULL, 1, RAMD_FWD_WHOLE, &early);
+  early_offer(&early); /* (a pass without the seam) */
+  multi_loss(set, NULL, alphabet_len, n_classes, leakage, early.offered);
   multi_calc_deltas(set, accumulate, defer);
 }
 void rnn_amd_set_multi_step_deltas(RnnAmdSet *set, const int *hot, const int *next,
@@ -716,12 +627,7 @@ void rnn_amd_set_sigmoid_mse_error(RnnAmdSet *set, const float *targets, int ld,
   }
   set_streams_to_dev(set);
   size_t bytes = (size_t)set->n * n * sizeof(float);
-  if (bytes > e->d_group_bytes) {
-    ramd_dsync();
-    ramd_dev_free(e->d_group);
-    e->d_group = ramd_dev_alloc(bytes);
-    e->d_group_bytes = bytes;
-  }
+  group_room(e, bytes);
   ramd_upload_rows(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n);
   ramd_launch_sigmoid_mse_error(ramd_stream, &e->sh, &e->b, set->row0, set->n, n, (const float *)e->d_group,
                                 n);
@@ -746,12 +652,7 @@ void rnn_amd_set_opinion_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld
   }
   ramd_set_need_training(set, "rnn_amd_set_opinion_sigmoid_mse");
   size_t bytes = (size_t)set->n * n * sizeof(float);
-  if (bytes > e->d_group_bytes) {
-    ramd_dsync();
-    ramd_dev_free(e->d_group);
-    e->d_group = ramd_dev_alloc(bytes);
-    e->d_group_bytes = bytes;
-  }
+  group_room(e, bytes);
   /* inputs and targets leave together with the ring indices (set_forward's flush) */
   ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), e->sh.input_size * sizeof(float), set->n, 0);
   ramd_upload_rows_q(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n, 0);
@@ -762,10 +663,7 @@ void rnn_amd_set_opinion_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld
     abort();
   }
   set_streams_dev_wrote(set);
-  e->top_done = 1;
-  e->top_done_row0 = set->row0;
-  e->top_done_n = set->n;
-  e->top_done_masked = 0;
+  ramd_top_done_set(e, set->row0, set->n, 0);
 }
 
 void rnn_amd_set_opinion_grouped_softmax(RnnAmdSet *set, const float *inputs, int ld_inputs, int n_groups,
@@ -779,50 +677,17 @@ void rnn_amd_set_opinion_grouped_softmax(RnnAmdSet *set, const float *inputs, in
     return;
   }
   ramd_set_need_training(set, "rnn_amd_set_opinion_grouped_softmax");
-  for (int i = 0; i < n_groups; i++) {
-    if (group_offset[i] < 0 || group_size[i] < 1 || group_offset[i] + group_size[i] > s->output_size) {
-      fprintf(stderr, "librecur_amd: class group %d (%d + %d) outside the %d outputs\n", i, group_offset[i],
-              group_size[i], s->output_size);
-      abort();
-    }
-  }
-  size_t ints = (size_t)2 * n_groups + (size_t)set->n * n_groups;
-  size_t bytes = ints * sizeof(int) + (error_weight ? (size_t)s->output_size * sizeof(float) : 0);
-  if (bytes > e->d_group_bytes) {
-    ramd_dsync();
-    ramd_dev_free(e->d_group);
-    e->d_group = ramd_dev_alloc(bytes);
-    e->d_group_bytes = bytes;
-  }
-  int *d = (int *)e->d_group;
-  ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), s->input_size * sizeof(float), set->n, 0);
-  ramd_upload_q(d, group_offset, n_groups * sizeof(int));
-  ramd_upload_q(d + n_groups, group_size, n_groups * sizeof(int));
-  ramd_upload_q(d + 2 * n_groups, targets, (size_t)set->n * n_groups * sizeof(int));
-  float *dw = NULL;
-  if (error_weight) {
-    dw = (float *)(d + ints);
-    ramd_upload_q(dw, error_weight, (size_t)s->output_size * sizeof(float));
-  }
-  for (int j = 0; j < set->n; j++) { /* a stream is trained if any of its groups has a usable target */
-    trained[j] = 0;
-    for (int i = 0; i < n_groups; i++) {
-      int t = targets[(size_t)j * n_groups + i];
-      trained[j] |= (t >= 0 && t < group_size[i]);
-    }
-  }
+  const ClassGroups g = class_groups_stage(set, inputs, ld_inputs, n_groups, group_offset, group_size, targets, error_weight,
+                                           trained);
   active_mask_to_dev(e, trained, set->n, 1); /* (for the delta call that follows: travels with the rest) */
   const RamdHandover left = set_forward(set, RAMD_IN_DENSE, e->d_dense, s->input_size, 0, NULL, 0, RAMD_FWD_FOR_DENSE_TOP);
-  if (!ramd_launch_dense_top(ramd_stream, s, &e->b, set->row0, set->n, left, NULL, 0, 0, n_groups, d, d + n_groups,
-                             d + 2 * n_groups, dw)) {
+  if (!ramd_launch_dense_top(ramd_stream, s, &e->b, set->row0, set->n, left, NULL, 0, 0, n_groups, g.offset, g.size,
+                             g.targets, g.weight)) {
     fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_grouped_softmax: the top launch declined a shape it had accepted\n");
     abort();
   }
   set_streams_dev_wrote(set);
-  e->top_done = 1;
-  e->top_done_row0 = set->row0;
-  e->top_done_n = set->n;
-  e->top_done_masked = 1;
+  ramd_top_done_set(e, set->row0, set->n, 1);
   if (!e->top_done_mask) {
     e->top_done_mask = ramd_zalloc((size_t)e->sh.Scap + 4);
   }
@@ -868,12 +733,12 @@ static void char_step_deltas(RnnAmdSet *set, int i, RamdPendingDelta *defer) {
   if (ramd_text_top_ok(&e->sh)) {
     /* advance + hidden layer, then output layer, loss and top backprop in one launch */
     const RamdHandover left = set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_FOR_TEXT_TOP);
-    noise_speculate(set); /* no draws between this pass's noise and the next one's */
+    ramd_noise_ahead_offer(set, 0); /* no draws between this pass's noise and the next one's */
     ramd_launch_text_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, left);
     set_calc_deltas(set, 0, NULL, NULL, RAMD_TOP_DONE, NULL, 0, defer);
   } else {
     set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_WHOLE); /* advance + one-hot opinion */
-    noise_speculate(set);
+    ramd_noise_ahead_offer(set, 0);
     ramd_launch_softmax_error(ramd_stream, &e->sh, &e->b, set->row0, set->n);
     set_calc_deltas(set, 0, NULL, NULL, 0, NULL, 0, defer);
   }

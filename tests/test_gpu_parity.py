@@ -833,7 +833,7 @@ def _one_generation_from_device_state(amd, kw, prepare=None, elem_floor=1e-2):
 
 def test_noise_generated_ahead_is_dropped_when_a_generator_moves(amd):
     """The set calls generate the presynaptic noise of the NEXT forward pass on a second stream
-    right after the current one (noise_speculate).  If the caller reseeds a stream's generator
+    right after the current one (noise_ahead.c).  If the caller reseeds a stream's generator
     in between (net->rng is public: recur-nn.h:158-186), the values generated ahead came from
     the old state and must not be used: every generation is compared with the oracle, generator
     states bit for bit, across such a reseeding and across a host round trip without one."""
