@@ -142,7 +142,7 @@ static inline CalcPlan ramd_plan_calc_deltas(const RamdShape *sh, const RamdBuff
    * h_size <= 128 and i_size <= 256 (text-predict's default 99 hidden units: 100 x 142): the matrix lives in the
    * workgroup's registers; larger nets take the launch-per-step route */
   p.nx = sh->I - sh->hidden_size;
-  p.nxp = (p.nx + 3) & ~3;
+  p.nxp = ramd_nxp(sh);
   p.tn = (sh->hidden_size + CN - 1) / CN;
   p.small_lds = (size_t)(128 + 256 + 256 + 20 + ((sh->D + 3) & ~3) + (size_t)sh->D * sh->I) * sizeof(float);
   p.small = nrows == 1 && !active && row0 < sh->Scap && sh->H <= 256 && env_int("RECUR_AMD_BPTT_SMALL", 1) && sh->H <= 128 &&

@@ -9,7 +9,8 @@
 //   chain     E_i[S x I]  = E_h[S x H] . W_ih^T   per BPTT step (recur-nn.c:338-376)
 //   delta     dW[I x H]   = sum_t X_t^T . diag(c_t) . E_h,t      (recur-nn.c:344-356, 738)
 // kernels_forward.hip holds the first, kernels_chain.hip the second, kernels_bptt.hip the third with
-// the rest of rnn_bptt_calc_deltas, kernels_loss.hip the callers' loss functions on the device, kernels_rows.hip
+// the rest of rnn_bptt_calc_deltas (its kernels by stage in k_bptt_top.h, k_bptt_extras.h, k_delta_direct.h,
+// k_delta_dma.h, k_bptt_small.h; the launchers in the .hip), kernels_loss.hip the callers' loss functions on the device, kernels_rows.hip
 // the batched forward-only calls' one launch between two forward passes,
 // kernels_apply.hip rnn_apply_learning and the conditioning helpers.
 #pragma once
@@ -177,6 +178,69 @@ __device__ __forceinline__ float block_sum_256(float v, float *red) {
   __syncthreads();
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
+
+// ---- the top layer backwards (recur-nn.c:156-228, 719-721): what its forms in k_bptt_top.h and the text step's top
+// launches (kernels_loss.hip) share, each rule stated once.  More of them, used by k_bptt_top.h alone, are there.
+
+/* The 64 head bits the multi-head loss leaves behind stream j's range list (RAMD_HEADBITS_AT): bit c, the stream trained head c. */
+__device__ __forceinline__ unsigned long long head_bits(const int *ranges, int j, int range_stride) {
+  return *reinterpret_cast<const unsigned long long *>(ranges + (size_t)j * range_stride + RAMD_HEADBITS_AT);
+}
+__device__ __forceinline__ void head_bits_store(int *rg, unsigned long long bits) { /* rg: the stream's own list */
+  *reinterpret_cast<unsigned long long *>(rg + RAMD_HEADBITS_AT) = bits;
+}
+
+/* Which rows of error plane 0 stay zero whatever the row's value: the chain reads column 0 and the pad past
+ * hidden_size as zeros.  (A test and not a function of the value: a site's value is only formed where it is stored.) */
+__device__ __forceinline__ bool top_plane_zero(const RamdShape &s, int y) { return y == 0 || y > s.hidden_size; }
+
+/* The soft clip on a stream's sum of |e| (softclip_scale above h_size * MAX_TOP_ERROR_FACTOR, recur-nn.c:719-721):
+ * whether the error row is clipped (on), by what (scale, else 1) and the clipped sum; top_clip_store, by thread 0,
+ * leaves both sums for the control logic.  Two pieces, as the forms scale their rows between them.
+ * (Nothing in them can contract: they read the same under their callers' fp contract modes.) */
+struct TopClip {
+  float sum, scale, scaled;
+  bool on;
+};
+__device__ __forceinline__ TopClip top_clip(const RamdShape &s, float sum) {
+  const float halfmax = s.H * MAX_TOP_ERROR_FACTOR_F;
+  TopClip c = {sum, 1.0f, sum, sum > halfmax};
+  if (sum > halfmax) {
+    c.scale = soft_clip_dev(sum, halfmax);
+    c.scaled = c.scale * sum;
+  }
+  return c;
+}
+__device__ __forceinline__ void top_clip_store(const View &v, int r, const TopClip &c) {
+  if (threadIdx.x == 0) {
+    v.b.top_raw[r] = c.sum;
+    v.b.top_scaled[r] = c.scaled;
+  }
+}
+
+// ---- bptt->h_error (err_a) and bptt->i_error (err_b) as the reference leaves them after a stream's n executed steps:
+// its loop ping-pongs between the two buffers (recur-nn.c:384-386), zeroing element 0 and the pad of whichever one it
+// reads (334-337).  Columns 1 .. hidden_size of a step's error live in the planes (ehi), column 0 and the input columns
+// in ex.  Entry i of both images of stream r, from the planes of steps n (> 0) and n - 1:
+__device__ __forceinline__ void write_error_images(const View &v, int r, int n, int nxp, int i) {
+  const RamdShape &s = v.sh;
+  float *A = v.b.err_a + (size_t)r * s.I, *B = v.b.err_b + (size_t)r * s.I;
+  float *last_written = (n & 1) ? B : A; /* step n wrote it in full        */
+  float *last_read = (n & 1) ? A : B;    /* step n read it (and zeroed bits) */
+  const float *en = v.b.ehi + ((size_t)n * s.Scap + r) * s.I;
+  const float *ep = v.b.ehi + ((size_t)(n - 1) * s.Scap + r) * s.I;
+  const float *xn = v.b.ex + ((size_t)n * s.Scap + r) * nxp;
+  const float *xp = v.b.ex + ((size_t)(n - 1) * s.Scap + r) * nxp;
+  const int hs = s.hidden_size;
+  last_written[i] = (i == 0) ? xn[0] : (i <= hs) ? en[i] : xn[i - hs];
+  if (i < s.H) {
+    last_read[i] = (i == 0 || i > hs) ? 0.0f : ep[i];
+  } else if (n > 1) { /* the top error (n == 1) only covers h_size entries */
+    last_read[i] = xp[i - hs];
+  }
+}
+/* ... and so, while the images have not been rebuilt, the plane that holds err_a's columns 1 .. hidden_size */
+__device__ __forceinline__ int stale_plane(int n) { return (n & 1) ? n - 1 : n; }
 
 // The input row of one stream, by a workgroup of 256 threads: bias, the previous hidden values from `hid`, the real
 // inputs as `mode` says (recur-nn.c:104-112: kept, a dense row, or the one-hot of `hot`), the padding as it is (zero);

@@ -1,6 +1,6 @@
 // k_extras.h -- the chain "extras" (column 0 and the input columns of every step's error, recur-nn.c:338-376)
 // and the data-dependent control of bptt_and_accumulate_error (recur-nn.c:317-330, 383-413) as device
-// functions: shared by k_extras_control / k_bptt_control (kernels_bptt.hip) and by the tail of
+// functions: shared by k_extras_control / k_bptt_control (k_bptt_extras.h, in kernels_bptt.hip) and by the tail of
 // the one-launch chain (kernels_chain.hip), which runs them for its own streams without a launch of their own.
 #pragma once
 #include "k_common.h"

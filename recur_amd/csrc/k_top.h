@@ -286,23 +286,14 @@ __device__ __forceinline__ void top_add_stats(const View &v, int r, const float 
   v.b.stat_zero[r] += (int)tstat[3] / (double)v.sh.hidden_size;
 }
 // The sixteen waves' sums of |error| (tred, behind the caller's barrier) into the stream's total -- the same tree as
-// block_sum_256 within each group of four waves, then the four groups -- and the soft clip (recur-nn.c:719-721) on it.
+// block_sum_256 within each group of four waves, then the four groups -- and the soft clip on it (top_clip).
 // Thread 0 stores top_raw / top_scaled.  Returns whether the error row is clipped, and in `scale` by what.
 __device__ __forceinline__ bool top_soft_clip(const View &v, int r, const float *tred, float &scale) {
 #pragma clang fp contract(off)
   const float g0 = (tred[0] + tred[1]) + (tred[2] + tred[3]), g1 = (tred[4] + tred[5]) + (tred[6] + tred[7]);
   const float g2 = (tred[8] + tred[9]) + (tred[10] + tred[11]), g3 = (tred[12] + tred[13]) + (tred[14] + tred[15]);
-  const float sum = (g0 + g1) + (g2 + g3);
-  const float halfmax = v.sh.H * MAX_TOP_ERROR_FACTOR_F;
-  float scaled = sum;
-  scale = 1.0f;
-  if (sum > halfmax) {
-    scale = soft_clip_dev(sum, halfmax);
-    scaled = scale * sum;
-  }
-  if (threadIdx.x == 0) {
-    v.b.top_raw[r] = sum;
-    v.b.top_scaled[r] = scaled;
-  }
-  return sum > halfmax;
+  const TopClip clip = top_clip(v.sh, (g0 + g1) + (g2 + g3));
+  top_clip_store(v, r, clip);
+  scale = clip.scale;
+  return clip.on;
 }

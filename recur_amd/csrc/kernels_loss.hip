@@ -320,7 +320,7 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
   const bool clipped = top_soft_clip(v, r, tred, scale);
   float *dst = v.b.ehi + (size_t)r * s.I; /* step 0 plane */
   for (int q = 0, y = threadIdx.x; y < s.H; y += 1024, q++)
-    dst[y] = (y == 0 || y > s.hidden_size) ? 0.0f : clipped ? ev[q] * scale : ev[q];
+    dst[y] = top_plane_zero(s, y) ? 0.0f : clipped ? ev[q] * scale : ev[q];
   TT_STAMP(5);
   BND_MARK(g_bnd_top, 1);
 }
@@ -493,8 +493,8 @@ __global__ __launch_bounds__(1024) void k_text_top2(View v, int row0, int nrows,
   const float ea = (rowa && ya != 0 && shid[rowa ? ya : 0] != 0.0f) ? mine : 0.0f;
   const float eb = (rowb && yb != 0 && shid[rowb ? yb : 0] != 0.0f) ? last : 0.0f;
   float *dst = v.b.ehi + (size_t)r * s.I; /* step 0 plane */
-  if (rowa) dst[ya] = (ya == 0 || ya > s.hidden_size) ? 0.0f : ea;
-  if (rowb) dst[yb] = (yb == 0 || yb > s.hidden_size) ? 0.0f : eb;
+  if (rowa) dst[ya] = top_plane_zero(s, ya) ? 0.0f : ea;
+  if (rowb) dst[yb] = top_plane_zero(s, yb) ? 0.0f : eb;
   const float sum = wave_all(fabsf(ea) + fabsf(eb), OpAdd{});
   if (lane == 0) tred[seg] = sum;
   TT_STAMP(6);
@@ -502,8 +502,8 @@ __global__ __launch_bounds__(1024) void k_text_top2(View v, int row0, int nrows,
   TT_STAMP(4);
   float scale;
   if (top_soft_clip(v, r, tred, scale)) { /* rare (a hot net): the row once more, scaled */
-    if (rowa) dst[ya] = (ya == 0 || ya > s.hidden_size) ? 0.0f : ea * scale;
-    if (rowb) dst[yb] = (yb == 0 || yb > s.hidden_size) ? 0.0f : eb * scale;
+    if (rowa) dst[ya] = top_plane_zero(s, ya) ? 0.0f : ea * scale;
+    if (rowb) dst[yb] = top_plane_zero(s, yb) ? 0.0f : eb * scale;
   }
   TT_STAMP(5);
   BND_MARK(g_bnd_top, 1);
@@ -569,7 +569,7 @@ __global__ __launch_bounds__(64 * MS_WAVES) void k_multi_softmax_error(View v, i
       rg[2 * nr] = -1;
       rg[2 * nr + 1] = 0;
       if (range_stride >= RAMD_HEADBITS_AT + 2 && ncls <= 64) /* (k_ho_delta_heads reads these, not the ranges) */
-        *reinterpret_cast<unsigned long long *>(rg + RAMD_HEADBITS_AT) = bits;
+        head_bits_store(rg, bits);
       reinterpret_cast<DevRng *>(v.b.rng)[r] = g;
       ntrained = nt;
     }

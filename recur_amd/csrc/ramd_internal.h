@@ -29,6 +29,8 @@ typedef struct RamdShape {
    * b_out = input_size rectified outputs; bI, bO are its padded sizes, 0 without one */
   int b_in, b_out, bI, bO;
 } RamdShape;
+/* row length of RamdBuffers::ex: column 0 and the columns above hidden_size (the real inputs and the pad), whole float4s */
+static inline int ramd_nxp(const RamdShape *sh) { return (sh->I - sh->hidden_size + 3) & ~3; }
 
 /* Device arrays.  "state row" r addresses hidden/out: r < Scap is training
  * stream r, r >= Scap is forward-only stream r - Scap.
