@@ -802,6 +802,50 @@ int rnn_amd_continue_texts_from(RecurNN *net, const u8 *const *prompts, const in
 int rnn_amd_run_sequences(RecurNN *net, const float *const *inputs, const int *n_frames, int n_seqs, int ld_inputs,
                           int n_groups, const int *group_offset, const int *group_size, const float *h_in, float *h_out,
                           int segment_frames, float *const *answers, u8 *const *winners);
+/* Many TEXTS against one CLASSIFIER net in one batched device run: using a net that text-classify trained, and its
+ * validation score.  What is written for text k is what this loop writes on a forward-only clone c_k of `net`
+ * (text-classify-results.c:83-122; with classes, the validation block of rnn_char_classify_epoch,
+ * charmodel-classify.c:174-196):
+ *     for j in 0 .. lens[k] - 1:  raw = one_hot_opinion(c_k, texts[k][j], 0)          (no noise)
+ *         if j >= skips[k]:       softmax(p, raw, net->output_size)                   (all outputs as one group)
+ *             for every class c:  sums[k * output_size + c] += p[c];  sumsqs[k * output_size + c] += p[c] * p[c]
+ *             if classes[k] and cl = classes[k][j] is not 0xFF (charmodel.h's NO_CLASS):
+ *                 scores[k].error += 1 - p[cl];  scores[k].entropy -= capped_log2f(p[cl]);
+ *                 scores[k].correct += (softmax_best_guess's pick == cl);  scores[k].count += 1
+ * The softmax is badmaths.h:71-111's: the shift, fast_expf, the sum in index order, the division.  The product p[c] * p[c]
+ * is formed in float, as the reference forms it; every addition is in double where the reference adds in float.  The best
+ * guess is the largest probability after the division, the lowest index among equals (badmaths.h:113-141).
+ * Unlike the scorers (rnn_amd_run_texts), EVERY symbol is fed and, from skips[k] on, scored -- as the frames of
+ * rnn_amd_run_sequences are: c_k's state ends behind the text's last symbol, and the next call simply continues with the
+ * next chunk of the text (no overlap by one symbol).  sums, sumsqs and scores are SET by the call, not added to: a text
+ * run in chunks is the sum of its chunks' results.
+ * skips, classes, any classes[k], sumsqs and scores may be NULL (no skip; no symbol has a class; not wanted).  A text with
+ * skips[k] >= lens[k] is fed and never scored; a negative skip is 0.  A text of 0 symbols takes no row: its sums and score
+ * are zeros and its h_out is its start state; texts[k] and classes[k] of such a text may be NULL.
+ * States are the _from text calls': c_k starts from net's hidden row at the moment of the call (h_in NULL) or from h_in[k],
+ * a row of net->h_size floats laid out as net->hidden_layer whose elements [1, hidden_size] carry the state; h_out[k]
+ * (h_out may be NULL, or h_in) is c_k's hidden row after its last symbol.  A text cut into pieces run by successive calls
+ * joined through h_out -> h_in is the text run in one call (the states to the bit where the passes run with the same row
+ * counts, else to rounding; the sums to the grouping of their double additions).
+ * There is no noise and no generator is touched; `net` -- host and device copies, weights, hidden row, what it computes
+ * next -- is left exactly as it was.
+ * The rows go longest first in waves of up to 256 (the layout of rnn_amd_run_texts: len symbols are a scorer's text of
+ * len + 1).  Texts and class bytes go up whole, a byte per symbol; per wave there is one launch between two forward
+ * passes, one synchronisation, and one copy back of 2 * output_size + 4 eight-byte words per row.
+ * Returns 0; n_texts == 0 returns 0 and touches nothing; where every text is empty it returns 0 at once (zeros, h_out
+ * filled by the host) and asks for no device.  Returns -1 with a line on stderr and nothing computed, before anything
+ * needs a device: a NULL net; n_texts < 0; a net with a bottom layer (as rnn_amd_run_texts); a NULL texts, lens or sums
+ * with n_texts > 0; a lens[k] below 0; a NULL texts[k] of a text with a symbol; a symbol >= net->input_size; a class byte
+ * that is neither 0xFF nor < net->output_size. */
+typedef struct RnnAmdClassScore {
+  double error;      /* sum of 1 - p[class]                 */
+  double entropy;    /* sum of -capped_log2f(p[class])      */
+  long long correct; /* symbols whose best guess == class   */
+  long long count;   /* symbols that had a class            */
+} RnnAmdClassScore;
+int rnn_amd_classify_texts(RecurNN *net, const u8 *const *texts, const int *lens, const int *skips,
+                           const u8 *const *classes, int n_texts, const float *h_in, float *h_out, double *sums,
+                           double *sumsqs, RnnAmdClassScore *scores);
 /* RNNCA'S AUTOMATON played on the device, many frames in one run: the batched form of fill_frame (gstrnnca.c:805-831).
  * The grid is width * height cells, cell (cx, cy) at index cy * width + cx; a frame is three planes of that many bytes
  * (Y, Cb, Cr).  Every cell is a forward-only clone of `net`.  frames[t] is what fill_frame leaves in play_frame after its

@@ -151,6 +151,20 @@ double rnn_char_cross_entropy(RecurNN *net, RnnCharAlphabet *alphabet, const u8 
 int rnn_amd_char_cross_entropy_texts(RecurNN *net, RnnCharAlphabet *alphabet, const u8 *const *texts, const int *lens,
                                      int n_texts, int ignore_first, const u8 *prefix_text, int prefix_len,
                                      double *entropy);
+/* text-classify-results' figures (text-classify-results.c:83-122) for many raw texts in one batched device run
+ * (rnn_amd_classify_texts, recur_amd.h): texts[k] (bytes[k] bytes of text) is encoded as rnn_char_load_new_encoded_text
+ * encodes a file -- rnn_char_alloc_encoded_text: collapse, case and utf-8 as the alphabet says --, every text is run on its
+ * own from the state `net` has, the first ignore_start symbols of each fed and not scored, and `net` is left as it was.
+ * Per text k and class c, with n = len_k - ignore_start scored symbols (len_k the encoded length):
+ *     mean[k * output_size + c]   = sum / n
+ *     stddev[k * output_size + c] = sqrt(max(0, sumsq / n - mean * mean))
+ * of the class's softmax probability over those symbols, in double.  The clamp at 0 is a deliberate difference: the
+ * reference forms sumsq / n - m * m in float without one and prints NaN where rounding takes it below zero.  A text with
+ * no scored symbol (len_k <= ignore_start) gets zeros.  A negative ignore_start is 0.  stddev may be NULL.
+ * Returns 0 (n_texts == 0: at once), or -1 with a line on stderr and nothing computed: what rnn_amd_classify_texts
+ * refuses, a NULL alphabet, texts, bytes or mean with n_texts > 0, a NULL texts[k] or a negative bytes[k]. */
+int rnn_amd_char_classify_texts(RecurNN *net, RnnCharAlphabet *alphabet, const char *const *texts, const int *bytes,
+                                int n_texts, int ignore_start, double *mean, double *stddev);
 /* rnn_char_confabulate's passage n_texts times over in one batched device run (rnn_amd_sample_texts, recur_amd.h): every
  * passage starts from prev_char and the state `net` has, passage k draws with a generator seeded init_rand64(seeds[k]),
  * and `net` -- state and generator -- is left as it was.  Up to char_len symbols each, ending after stop_point if that is

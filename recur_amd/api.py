@@ -145,6 +145,10 @@ class Automaton(C.Structure):  # RnnAmdAutomaton (include/recur_amd.h)
                 ("offsets_c", c_int_p), ("len_c", C.c_int), ("len_pos", C.c_int), ("edges", C.c_int)]
 
 
+class ClassScore(C.Structure):  # RnnAmdClassScore (include/recur_amd.h)
+    _fields_ = [("error", C.c_double), ("entropy", C.c_double), ("correct", C.c_longlong), ("count", C.c_longlong)]
+
+
 # flags / enums (include/recur_amd.h)
 FLAG_OWN_BPTT = 1
 FLAG_OWN_WEIGHTS = 2
@@ -269,7 +273,9 @@ AMD_API = {
                                            C.POINTER(c_float_p), C.POINTER(c_u8_p)]),
     "rnn_amd_run_sequences": (C.c_int, [NetP, C.POINTER(c_float_p), c_int_p, C.c_int, C.c_int, C.c_int, c_int_p, c_int_p,
                                         c_float_p, c_float_p, C.c_int, C.POINTER(c_float_p), C.POINTER(c_u8_p)]),
-    "rnn_amd_automaton_parse_offsets": (C.c_int, [C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, C.c_int]),
+    "rnn_amd_classify_texts": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, c_int_p, C.POINTER(c_u8_p), C.c_int, c_float_p,
+                                         c_float_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(ClassScore)]),
+    "rnn_amd_automaton_parse_offsets": (C.c_int,[C.c_char_p, c_int_p, c_int_p, c_int_p, c_int_p, C.c_int]),
     "rnn_amd_run_automaton": (C.c_int, [NetP, C.POINTER(Automaton), c_u8_p, C.c_int, c_float_p, c_float_p, C.c_int, c_u8_p]),
     "rnn_amd_continue_texts_from": (C.c_int, [NetP, C.POINTER(c_u8_p), c_int_p, C.POINTER(C.c_uint64), C.POINTER(RandCtx),
                                               C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, c_float_p, c_float_p,
@@ -450,7 +456,9 @@ CHAR_API = {
     "rnn_char_cross_entropy": (C.c_double, [NetP, AlphaP, c_u8_p, C.c_int, C.c_int, c_u8_p, C.c_int]),
     "rnn_amd_char_cross_entropy_texts": (C.c_int, [NetP, AlphaP, C.POINTER(c_u8_p), c_int_p, C.c_int, C.c_int, c_u8_p,
                                                    C.c_int, C.POINTER(C.c_double)]),
-    "rnn_amd_char_confabulate_texts": (C.c_int, [NetP, AlphaP, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_float, C.c_int,
+    "rnn_amd_char_classify_texts": (C.c_int, [NetP, AlphaP, C.POINTER(C.c_char_p), c_int_p, C.c_int, C.c_int,
+                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "rnn_amd_char_confabulate_texts": (C.c_int,[NetP, AlphaP, C.POINTER(C.c_uint64), C.c_int, C.c_int, C.c_float, C.c_int,
                                                  C.c_int, C.POINTER(C.c_char_p), C.c_int, c_int_p]),
     "rnn_amd_char_continue_texts": (C.c_int, [NetP, AlphaP, C.POINTER(C.c_char_p), c_int_p, C.POINTER(C.c_uint64), C.c_int,
                                               C.c_int, C.c_float, C.c_int, C.POINTER(C.c_char_p), C.c_int, c_int_p]),

@@ -16,6 +16,7 @@
  * erewhon curve through this function and the net's log) and tests/test_charmodel.py.
  */
 #include "char_host.h"
+#include "classify_rule.h"
 
 /* ------------------------------------------------------------ cross entropy -- */
 
@@ -64,6 +65,63 @@ int rnn_amd_char_cross_entropy_texts(RecurNN *net, RnnCharAlphabet *alphabet, co
   for (int k = 0; r == 0 && k < n_texts; k++) {
     entropy[k] = entropy[k] / -(double)(lens[k] - skip - 1);
   }
+  return r;
+}
+
+/* text-classify-results' mean and standard deviation per text and class, all texts in one batched device run: the texts
+ * encoded as a file's is, rnn_amd_classify_texts, then classify_rule.h's finish */
+int rnn_amd_char_classify_texts(RecurNN *net, RnnCharAlphabet *alphabet, const char *const *texts, const int *bytes,
+                                int n_texts, int ignore_start, double *mean, double *stddev) {
+  const char *who = "rnn_amd_char_classify_texts";
+  if (!net || n_texts < 0 || (n_texts > 0 && (!alphabet || !texts || !bytes || !mean))) {
+    fprintf(stderr, "librecur_amd: %s: a NULL argument for %d texts\n", who, n_texts);
+    return -1;
+  }
+  if (n_texts == 0) {
+    return 0;
+  }
+  for (int k = 0; k < n_texts; k++) {
+    if (!texts[k] || bytes[k] < 0) {
+      fprintf(stderr, "librecur_amd: %s: text %d is NULL or has %d bytes\n", who, k, texts[k] ? bytes[k] : 0);
+      return -1;
+    }
+  }
+  const size_t n_out = (size_t)net->output_size;
+  u8 **enc = calloc((size_t)n_texts, sizeof(u8 *));
+  int *lens = calloc((size_t)n_texts, sizeof(int));
+  int *skips = calloc((size_t)n_texts, sizeof(int));
+  double *sumsqs = calloc((size_t)n_texts * n_out, sizeof(double));
+  int *lut = rnn_char_new_char_lut(alphabet);
+  int r = -1;
+  if (!enc || !lens || !skips || !sumsqs || !lut) {
+    fprintf(stderr, "librecur_amd: %s: out of memory\n", who);
+    goto done;
+  }
+  for (int k = 0; k < n_texts; k++) {
+    enc[k] = rnn_char_alloc_encoded_text(alphabet, texts[k], bytes[k], &lens[k], lut, false);
+    skips[k] = ignore_start;
+  }
+  r = rnn_amd_classify_texts(net, (const u8 *const *)enc, lens, skips, NULL, n_texts, NULL, NULL, mean, sumsqs, NULL);
+  for (int k = 0; r == 0 && k < n_texts; k++) {
+    const int n = classify_scored_count(lens[k], ignore_start);
+    for (size_t c = 0; c < n_out; c++) {
+      double m, sd;
+      classify_finish(mean[k * n_out + c], sumsqs[k * n_out + c], n, &m, &sd);
+      mean[k * n_out + c] = m;
+      if (stddev) {
+        stddev[k * n_out + c] = sd;
+      }
+    }
+  }
+done:
+  for (int k = 0; enc && k < n_texts; k++) {
+    free(enc[k]);
+  }
+  free(enc);
+  free(lens);
+  free(skips);
+  free(sumsqs);
+  free(lut);
   return r;
 }
 

@@ -1,8 +1,9 @@
 // kernels_rows.hip -- what the batched forward-only calls share on the device, as rows_host.c holds what they share on the
 // host: the one launch between two forward passes of rnn_amd_run_texts and _trace_texts (texts_api.c: k_texts_step),
 // rnn_amd_sample_texts and _continue_texts (sample_api.c: k_texts_continue), rnn_amd_run_sequences (seqs_api.c:
-// k_seqs_step) and rnn_amd_run_automaton (automaton_api.c: k_automaton_step), and their launchers.  Every text, sequence or
-// cell has a forward-only state row of the engine's own, one workgroup per row, and the kernels have one shape: a score,
+// k_seqs_step), rnn_amd_classify_texts (classify_texts_api.c: k_classify_step) and rnn_amd_run_automaton (automaton_api.c:
+// k_automaton_step), and their launchers.  Every text, sequence or cell has a forward-only state row of the engine's own,
+// one workgroup per row, and the kernels have one shape: a score,
 // paint or draw half on what the forward pass just left in the row's out row, then a feed half that builds the row's next
 // input row through assemble_input_row (k_common.h), on the hidden values texts_feed_hidden names.  What a launch is
 // handed -- its fields and its contract -- stands once, above its struct in ramd_internal.h (the automaton's in
@@ -13,6 +14,7 @@
 #include "sample_rule.h"
 #include "continue_rule.h"
 #include "automaton_rule.h"
+#include "classify_rule.h"
 #pragma clang fp contract(off)
 
 constexpr int TS_WAVES = 4;
@@ -150,6 +152,58 @@ __global__ __launch_bounds__(64 * TS_WAVES) void k_seqs_step(View v, RamdSeqsSte
   if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
     assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_DENSE, 0,
                        p.in + (at + (size_t)p.t_feed) * (size_t)s.input_size, red);
+}
+
+// RamdClassifyStep's launch (ramd_internal.h), one workgroup of 256 threads per row.  The score half is the loop body of
+// text-classify-results.c:96-104 and of rnn_char_classify_epoch's validation (charmodel-classify.c:181-191) on the output
+// row the forward pass just left; which rows it is for is classify_rule.h's answer.  Wave 0 builds the softmax of ALL the
+// outputs as one group -- the shift and the exponentials into tex (LDS, lane-strided: output_size may exceed a wave), their
+// sum in the reference's order -- and, for a symbol with a class, the best guess (badmaths.h:113-141) and the row's score,
+// which lane 0 adds.  Behind the barrier the whole workgroup divides and adds: thread c's classes c, c + 256, ... into the
+// row's own doubles, the square formed in float as the reference forms it.  Every word has one writer: no atomics.
+__global__ __launch_bounds__(64 * TS_WAVES) void k_classify_step(View v, RamdClassifyStep p) {
+  extern __shared__ float tex[]; /* [output_size] exponentials */
+  __shared__ float red[4];
+  __shared__ float sum_sh;
+  const RamdShape &s = v.sh;
+  const int j = blockIdx.x, r = p.row0 + j, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const size_t at = (size_t)p.off[j];
+  /* (j < a_score: the plan's order has answered classify_fed; the same in every thread: the barrier is met by all) */
+  if (j < p.a_score && classify_skip_passed(p.skip[j], p.t_score)) {
+    const int n = s.output_size;
+    const float *out = v.b.out + (size_t)r * s.O;
+    double *acc = p.acc + (size_t)j * RAMD_CLASSIFY_ACC_WORDS(n);
+    if (wave == 0) {
+      wave_softmax_exps(out, tex, n, lane, FenceOneWave{});
+      const float sum = ordered_sum(tex, n);
+      const int cl = p.cls ? p.cls[at + (size_t)p.t_score] : CLASSIFY_NO_CLASS;
+      if (classify_has_class(cl)) { /* (the same byte in every lane) */
+        BestGuess best;
+        for (int i = lane; i < n; i += 64) best.offer(tex[i] / sum, i);
+        wave_best_guess(best);
+        if (lane == 0) {
+          const float e = tex[cl] / sum;
+          long long *counts = reinterpret_cast<long long *>(acc + 2 * (size_t)n + 2);
+          acc[2 * (size_t)n] += 1.0 - (double)e;
+          acc[2 * (size_t)n + 1] -= (double)capped_log2f_dev(e);
+          counts[0] += best.i == cl;
+          counts[1] += 1;
+        }
+      }
+      if (lane == 0) sum_sh = sum;
+    }
+    __syncthreads();
+    const float sum = sum_sh;
+    for (int c = threadIdx.x; c < n; c += 64 * TS_WAVES) {
+      const float e = tex[c] / sum;
+      const float sq = e * e;
+      acc[c] += (double)e;
+      acc[(size_t)n + c] += (double)sq;
+    }
+  }
+  if (j < p.a_feed) /* (the whole workgroup: assemble_input_row has barriers) */
+    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_ONE_HOT,
+                       p.text[at + (size_t)p.t_feed], nullptr, red);
 }
 
 // RamdAutomatonStep's launch (automaton_rule.h): rnnca's fill_frame (gstrnnca.c:805-831) with a forward-only state row per
@@ -343,6 +397,21 @@ extern "C" void ramd_launch_seqs_step(ramd_stream_t st, const RamdShape *sh, con
   p.stride = (largest + 3) & ~3; /* (over `largest`, in this copy) */
   const size_t shm = softmax_lds_or_abort<k_seqs_step>((size_t)TS_WAVES * p.stride, largest);
   RAMD_LAUNCH(k_seqs_step, dim3(rows), dim3(64 * TS_WAVES), shm, (hipStream_t)st, make_view(sh, b), p);
+}
+
+extern "C" void ramd_launch_classify_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
+                                          const RamdClassifyStep *p) {
+  const int rows = p->a_score > p->a_feed ? p->a_score : p->a_feed;
+  if (rows < 1) return;
+  forward_rows_or_abort("ramd_launch_classify_step", sh, p->row0, rows);
+  if (sh->output_size < 1 || !p->off || (p->a_score > 0 && (p->t_score < 0 || !p->acc || !p->skip)) ||
+      (p->a_feed > 0 && (p->t_feed < 0 || !p->text))) {
+    fprintf(stderr, "librecur_amd: ramd_launch_classify_step: %d outputs, steps %d and %d for %d and %d rows\n",
+            sh->output_size, p->t_score, p->t_feed, p->a_score, p->a_feed);
+    abort();
+  }
+  const size_t shm = softmax_lds_or_abort<k_classify_step>((size_t)((sh->output_size + 3) & ~3), sh->output_size);
+  RAMD_LAUNCH(k_classify_step, dim3(rows), dim3(64 * TS_WAVES), shm, (hipStream_t)st, make_view(sh, b), *p);
 }
 
 extern "C" void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,

@@ -301,6 +301,32 @@ typedef struct RamdSeqsStep {
 } RamdSeqsStep;
 void ramd_launch_seqs_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdSeqsStep *p);
 
+/* rnn_amd_classify_texts (classify_texts_api.c): N texts of different lengths through one classifier net, every symbol fed
+ * AND scored (the plan's text of len + 1: len forward passes, as the sequences').  Two halves:
+ *   score symbol t_score, rows [0, a_score) whose skip[row] <= t_score (classify_rule.h): the softmax of the row's
+ *     output_size outputs as ONE group (badmaths.h:71-111: the shift, fast_expf, the sum in index order, the division).
+ *     Row j's accumulators are RAMD_CLASSIFY_ACC_WORDS(output_size) 8-byte words at acc + j * that: output_size doubles
+ *     that p[c] is added to, output_size doubles that the float product p[c] * p[c] is added to, then -- for a symbol
+ *     whose class byte cl = cls[off[row] + t_score] is not 0xFF (cls NULL: no symbol has a class) -- a double that
+ *     1 - p[cl] is added to, a double that capped_log2f(p[cl]) is subtracted from, and two long longs: one counts the
+ *     symbols whose best guess (softmax_best_guess: the largest probability, the lowest index among equals) is cl, one
+ *     the symbols with a class.  The host zeroes them per wave; every word has one writer: no atomics.
+ *   feed symbol t_feed, rows [0, a_feed): the input row of the next forward pass -- the one-hot of text[t_feed] on the
+ *     hidden values.
+ * a_score == 0: a wave's first launch, which only feeds; a_feed == 0: its last, which only scores. */
+#define RAMD_CLASSIFY_ACC_WORDS(output_size) (2 * (size_t)(output_size) + 4)
+typedef struct RamdClassifyStep {
+  const unsigned char *text;     /* the wave's texts behind one another            */
+  const unsigned char *cls;      /* their class bytes at the same offsets, or NULL */
+  const unsigned long long *off; /* [rows] where row j's text starts               */
+  const int *skip;               /* [rows] symbols fed but not scored              */
+  double *acc;                   /* [rows][RAMD_CLASSIFY_ACC_WORDS] (above)        */
+  const float *hid0;
+  int row0;
+  int t_score, a_score, t_feed, a_feed;
+} RamdClassifyStep;
+void ramd_launch_classify_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdClassifyStep *p);
+
 /* rnn_amd_run_automaton (automaton_api.c): RamdAutomatonStep stands in automaton_rule.h, next to the rule it embeds */
 struct RamdAutomatonStep;
 void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,

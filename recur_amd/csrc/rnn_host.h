@@ -220,7 +220,7 @@ int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const 
                            int alphabet_len, const void *out);
 
 /* rows_host.c: what the batched calls on forward-only state rows share (texts_api.c, sample_api.c, seqs_api.c,
- * automaton_api.c) */
+ * classify_texts_api.c, automaton_api.c) */
 /* what all of them refuse about the net, without a device: a bottom layer, heads that do not divide the output row
  * (alphabet_len 0: no heads).  -1 with a message on stderr, else 0 */
 int ramd_texts_net_refused(const char *who, const RecurNN *net, int alphabet_len);

@@ -10,7 +10,9 @@ back the scorer's figures symbol by symbol (rnn_amd_trace_texts); ``run_texts_fr
 ``continue_texts_from`` are those with a start state per text and the final states handed back, as numpy arrays
 [n][h_size] (the rnn_amd_*_texts_from calls); ``run_sequences`` runs a list of dense feature sequences against one net in
 one batched call (rnn_amd_run_sequences): per frame the class groups' probabilities and winners, with states in and out
-in the same form; ``run_automaton`` plays rnnca's automaton from a seed frame on an ``AutomatonGeometry`` in one call
+in the same form; ``classify_texts`` runs a list of encoded texts against one classifier net in one batched call
+(rnn_amd_classify_texts): per text the sums and sums of squares of every class's probability and the score against the
+symbols' classes; ``run_automaton`` plays rnnca's automaton from a seed frame on an ``AutomatonGeometry`` in one call
 (rnn_amd_run_automaton): the frames as uint8 [n][3][height][width] and the cells' states, and ``parse_offsets`` expands an
 offset pattern (rnn_amd_automaton_parse_offsets).  ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
@@ -264,6 +266,43 @@ def run_sequences(lib, net, seqs, groups=None, h_in=None, want_out=True, in_plac
     assert not winners or all(np.all(a[int(f) * ng:] == 0xEE) for a, f in zip(win, frames)), "winners behind a sequence's last frame"
     return [(ans[k][:counts[k]].reshape(-1, osz).copy(),
              win[k][:int(frames[k]) * ng].reshape(-1, ng).copy() if winners else None) for k in range(n)], \
+        None if hout is None else hout[:n]
+
+
+def classify_texts(lib, net, texts, skips=None, classes=None, h_in=None, want_out=True, in_place=False):
+    """rnn_amd_classify_texts for a list of numpy uint8 arrays (a text may be empty): every symbol fed and, from the
+    text's skip on, the softmax over all outputs added up.  classes: None, or a list with, per text, None or a uint8 array
+    of the text's length (0xFF: the symbol has no class).  Returns (sums [n][output_size] float64, sumsqs the same,
+    scores as a structured array [n] with fields error, entropy (float64), correct, count (int64), h_out [n][h_size]
+    float32 or None with want_out=False).  h_in, want_out, in_place as in the _from text drivers.  The result arrays are
+    allocated with guard entries behind them, which must come back untouched."""
+    keep, ptrs, lens = text_pointers(texts)
+    n = len(keep)
+    osz = net.contents.output_size
+    sk = None if skips is None else np.ascontiguousarray(skips, dtype=np.int32)
+    assert sk is None or len(sk) == n
+    ckeep, cptrs = None, None
+    if classes is not None:
+        assert len(classes) == n
+        ckeep = [None if c is None else np.ascontiguousarray(c, dtype=np.uint8) for c in classes]
+        assert all(c is None or len(c) == len(t) for c, t in zip(ckeep, keep)), "a class byte per symbol"
+        cptrs = (rc.c_u8_p * max(n, 1))(*[rc.u8ptr(c) if c is not None and len(c) else None for c in ckeep])
+    sums = np.full(n * osz + TRACE_GUARD, np.nan)
+    sumsqs = np.full(n * osz + TRACE_GUARD, np.nan)
+    scores = np.full(n + 1, -7, np.dtype([("error", np.float64), ("entropy", np.float64), ("correct", np.int64),
+                                          ("count", np.int64)]))
+    assert scores.dtype.itemsize == C.sizeof(rc.ClassScore)
+    hin, hout, hip, hop = _states(net, n, h_in, want_out, in_place)
+    dp = C.POINTER(C.c_double)
+    r = lib.rnn_amd_classify_texts(net, ptrs, rc.iptr(lens), None if sk is None else rc.iptr(sk), cptrs, n, hip, hop,
+                                   sums.ctypes.data_as(dp), sumsqs.ctypes.data_as(dp),
+                                   scores.ctypes.data_as(C.POINTER(rc.ClassScore)))
+    if r != 0:
+        raise ValueError("rnn_amd_classify_texts refused the batch (see stderr)")
+    assert np.all(np.isnan(sums[n * osz:])) and np.all(np.isnan(sumsqs[n * osz:])), "sums behind the last text's"
+    assert scores[n]["count"] == -7 and scores[n]["error"] == -7, "a score behind the last text's"
+    assert not np.any(np.isnan(sums[:n * osz])) and not np.any(np.isnan(sumsqs[:n * osz])), "a sum was not written"
+    return sums[:n * osz].reshape(n, osz).copy(), sumsqs[:n * osz].reshape(n, osz).copy(), scores[:n].copy(), \
         None if hout is None else hout[:n]
 
 
