@@ -894,6 +894,51 @@ int rnn_amd_automaton_parse_offsets(const char *pattern, int *offsets_y, int *le
 int rnn_amd_run_automaton(RecurNN *net, const RnnAmdAutomaton *ca, const u8 *seed /* [3][height * width] */, int n_frames,
                           const float *h_in, float *h_out /* [height * width][h_size] */, int segment_frames,
                           u8 *frames /* [n_frames][3][height * width] */);
+/* PARROT'S PLAYER on the device, many closed-loop sequences in one run: the batched form of fill_audio_chunk's loop over
+ * the channels (gstparrot.c:556-583), in which every channel's dream net is fed its own last answer.  Sequence k is a
+ * forward-only clone c_k of `net` with a generator g_k and an input row x_k = first[k] (net->input_size floats, row stride
+ * ld_first):
+ *     for t in 0 .. n_frames - 1:
+ *         raw = rnn_opinion(c_k, x_k, 0)                                          (no presynaptic noise)
+ *         a[i] = fast_tanhf(raw[i]);  frames[t][k][i] = a[i]                      for every output i
+ *         x_k[i] = a[i] * (1.0f + noise * cheap_gaussian_noise(g_k))              for i = 0 .. output_size - 1, in index order
+ *     next[k] = x_k;  rng_out[k] = g_k;  h_out[k] = c_k's hidden row
+ * The answer is the next input, so net->input_size == net->output_size is required.  fast_tanhf is badmaths.h:55-68:
+ * -1.0f at x <= -4.97f, 1.0f at x >= 4.97f, else x * (135135 + x2 * (17325 + x2 * (378 + x2))) divided by
+ * 135135 + x2 * (62370 + x2 * (3150 + x2 * 28)), x2 = x * x, every operation one fp32 rounding; NaN stays NaN.  The noise
+ * product is rounded, then the sum, then the product with a[i] -- never a + a * g; with noise == 1.0f the line is
+ * gstparrot.c:576 to the bit.  The emergency soft clip of an input row (maybe_scale_inputs, recur-nn.c:68-81) belongs to
+ * rnn_opinion: x_k and next[k] are the values before it.
+ *   generators     g_k starts as rng_in[k], or with rng_in == NULL as init_rand64(seeds[k]): the continuer's _from
+ *                  convention.  rng_out may be NULL, or rng_in.
+ *   noise == 0.0f  nothing is drawn and no generator is touched: seeds and rng_in may both be NULL, next[k] is the last
+ *                  frame, and rng_out[k] is the start generator where the call names one (else it is not written).
+ *   states         exactly the _from calls': c_k starts from net's hidden row at the moment of the call (h_in NULL) or
+ *                  from h_in[k], a row of net->h_size floats laid out as net->hidden_layer whose elements
+ *                  [1, hidden_size] carry the state; h_out (NULL, or h_in) gets the hidden rows after the last frame.
+ *   cutting a run  a run cut into two calls, joined through next -> first (ld_first = input_size), h_out -> h_in and
+ *                  rng_out -> rng_in, is the uncut run bit for bit.
+ *   net            its host and device copies, hidden row and own generator are left exactly as they were.
+ *   the reference  one channel, with rng_in a copy of the shared generator and first the dream net's output row, is
+ *                  fill_audio_chunk's `answer` sequence.  Many channels differ from the reference only in that each has
+ *                  a generator of its own: the reference's single shared one serialises the channels.  MDCT synthesis,
+ *                  overlap-add and the s16 output (gstparrot.c:568-575) stay with the caller, on `frames`.
+ * All n_seqs rows run in lock step (there are no waves), between two forward passes one launch emits the frame and builds
+ * the next input rows -- the draws are made on the device too, on a second stream beside the forward passes, two frames
+ * ahead -- and the host is not visited per frame: the frames stay
+ * on the device and come back in one copy straight into `frames` with one synchronisation per SEGMENT of at most
+ * segment_frames frames (segment_frames <= 0: the default, the largest count whose floats stay within 16 MiB, at least 1;
+ * 64 frames of 256 channels of 256 bins).  The device buffer holds one segment.  The segment size changes no bit.  States,
+ * first, next and the generators each move in one copy each way.
+ * Returns 0; n_seqs == 0 or n_frames == 0 returns 0 at once and asks for no device: next = first, rng_out = the start
+ * generators and h_out = the start states are filled by the host.  Returns -1 with a line on stderr and nothing computed,
+ * before anything needs a device: a NULL net; n_seqs or n_frames < 0; net->input_size != net->output_size;
+ * ld_first < net->input_size; a net with a bottom layer (as rnn_amd_run_texts); a noise that is not finite; with
+ * n_seqs > 0, noise != 0 with both seeds and rng_in NULL, and with n_frames > 0 as well a NULL first or frames. */
+int rnn_amd_dream_sequences(RecurNN *net, const float *first /* [n_seqs][ld_first] */, int ld_first, int n_seqs,
+                            int n_frames, float noise, const u64 *seeds, const rand_ctx *rng_in, const float *h_in,
+                            float *h_out, int segment_frames, float *frames /* [n_frames][n_seqs][output_size] */,
+                            float *next /* [n_seqs][input_size] or NULL */, rand_ctx *rng_out /* [n_seqs] or NULL */);
 /* Block until all queued device work of the library has finished. */
 void rnn_amd_synchronize(void);
 

@@ -1,8 +1,9 @@
 // kernels_rows.hip -- what the batched forward-only calls share on the device, as rows_host.c holds what they share on the
 // host: the one launch between two forward passes of rnn_amd_run_texts and _trace_texts (texts_api.c: k_texts_step),
 // rnn_amd_sample_texts and _continue_texts (sample_api.c: k_texts_continue), rnn_amd_run_sequences (seqs_api.c:
-// k_seqs_step), rnn_amd_classify_texts (classify_texts_api.c: k_classify_step) and rnn_amd_run_automaton (automaton_api.c:
-// k_automaton_step), and their launchers.  Every text, sequence or cell has a forward-only state row of the engine's own,
+// k_seqs_step), rnn_amd_classify_texts (classify_texts_api.c: k_classify_step), rnn_amd_run_automaton (automaton_api.c:
+// k_automaton_step) and rnn_amd_dream_sequences (dream_api.c: k_dream_step), and their launchers.  Every text, sequence
+// or cell has a forward-only state row of the engine's own,
 // one workgroup per row, and the kernels have one shape: a score,
 // paint or draw half on what the forward pass just left in the row's out row, then a feed half that builds the row's next
 // input row through assemble_input_row (k_common.h), on the hidden values texts_feed_hidden names.  What a launch is
@@ -15,6 +16,7 @@
 #include "continue_rule.h"
 #include "automaton_rule.h"
 #include "classify_rule.h"
+#include "dream_rule.h"
 #pragma clang fp contract(off)
 
 constexpr int TS_WAVES = 4;
@@ -256,6 +258,55 @@ __global__ __launch_bounds__(256) void k_automaton_step(View v, RamdAutomatonSte
   }
 }
 
+// RamdDreamStep's launch (ramd_internal.h): parrot's player (fill_audio_chunk, gstparrot.c:556-583) with a forward-only
+// state row per sequence, all of them in lock step.  One workgroup of 256 threads per row (assemble_input_row's).  Thread
+// i, i + 256, .. applies dream_tanh to the row's own out[i], stores it at its place in the segment's buffer and forms
+// dream_next of it with the frame's draw gz[i][row] into LDS: the dense row that assemble_input_row takes, the emergency
+// soft clip included -- or, in a call's last launch, into the row of `next`.  The tanh that is fed is the one that was
+// emitted, from the thread's register: nothing another workgroup writes is read.
+__global__ __launch_bounds__(256) void k_dream_step(View v, RamdDreamStep p) {
+  extern __shared__ float dream_in[]; /* [input_size] the row's dense input row */
+  __shared__ float red[4];
+  const RamdShape &s = v.sh;
+  const int j = blockIdx.x, r = p.row0 + j, n = s.output_size;
+  if (p.first) { /* (the same in every thread: the whole workgroup, assemble_input_row has barriers) */
+    assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, p.hid0, true), RAMD_IN_DENSE, 0,
+                       p.first + (size_t)j * p.ld_first, red);
+    return;
+  }
+  const bool draws = dream_draws(p.noise);
+  const float *out = v.b.out + (size_t)r * s.O;
+  const float *gz = p.gz + j; /* the row's column of gz[output_size][rows] (not read without draws) */
+  float *emit = p.emit + (size_t)j * n;
+  float *dst = p.next ? p.next + (size_t)j * n : dream_in;
+  for (int i = threadIdx.x; i < n; i += 256) { /* (element i is read and written by this thread alone) */
+    const float a = dream_tanh(out[i]);
+    emit[i] = a;
+    dst[i] = draws ? dream_next(a, p.noise, gz[(size_t)i * p.rows]) : a;
+  }
+  if (p.next) return;
+  __syncthreads();
+  assemble_input_row(s, input_row(v, r, 0), texts_feed_hidden(v, r, nullptr, false), RAMD_IN_DENSE, 0, dream_in, red);
+}
+// One frame's draws of rnn_amd_dream_sequences, ahead of the launch that takes them (ramd_launch_dream_draw): a
+// generator is a recurrence -- 3 rand64 per value, one lane per row whatever the number of rows -- so it runs on the side
+// stream beside the forward passes, as the presynaptic noise does (noise_ahead.c).  Lane k of the grid is row k: n values
+// in index order into gz[0 .. n)[k] -- value-major, so that a wave's 64 lanes store 64 consecutive floats (row-major, 64
+// separate lines a store, measured the same: 58.1 against 57.2 us a frame, profiles/r13_dream_rate.txt) --, the generator
+// stored back.
+struct DreamGaussian {
+  Rng32 &r;
+  __device__ __forceinline__ float operator()() { return dev_cheap_gaussian_pair(r); }
+};
+__global__ __launch_bounds__(64) void k_dream_draw(DevRng *rng, float *gz, int rows, int n) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= rows) return;
+  Rng32 r32 = rng_split(rng[k]);
+  DreamGaussian gaussian = {r32};
+  dream_draw(gz + k, n, (size_t)rows, gaussian);
+  rng_join(rng[k], r32);
+}
+
 struct SampleWave { /* sample_rule.h's team: the 64 lanes of one wave */
   int l;
   __device__ __forceinline__ int lane() const { return l; }
@@ -432,6 +483,32 @@ extern "C" void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh
     abort();
   }
   RAMD_LAUNCH(k_automaton_step, dim3((unsigned)cells), dim3(256), shm, (hipStream_t)st, make_view(sh, b), *p);
+}
+
+extern "C" void ramd_launch_dream_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdDreamStep *p) {
+  if (p->rows < 1) return;
+  forward_rows_or_abort("ramd_launch_dream_step", sh, p->row0, p->rows);
+  if (sh->input_size != sh->output_size || sh->output_size < 1 || (p->first && p->ld_first < sh->input_size) ||
+      (!p->first && (!p->emit || (dream_draws(p->noise) && !p->gz)))) {
+    fprintf(stderr, "librecur_amd: ramd_launch_dream_step: %d inputs and %d outputs, first rows of %d floats, or a NULL "
+                    "frame or draw array\n", sh->input_size, sh->output_size, p->ld_first);
+    abort();
+  }
+  const size_t shm = (size_t)((sh->input_size + 3) & ~3) * sizeof(float);
+  if (shm > 64 * 1024) {
+    fprintf(stderr, "librecur_amd: a dream's %d inputs do not fit the LDS\n", sh->input_size);
+    abort();
+  }
+  RAMD_LAUNCH(k_dream_step, dim3(p->rows), dim3(256), shm, (hipStream_t)st, make_view(sh, b), *p);
+}
+
+extern "C" void ramd_launch_dream_draw(ramd_stream_t st, void *rng, float *gz, int rows, int n) {
+  if (rows < 1 || n < 1) return;
+  if (!rng || !gz) {
+    fprintf(stderr, "librecur_amd: ramd_launch_dream_draw: a NULL generator or draw array for %d rows of %d\n", rows, n);
+    abort();
+  }
+  RAMD_LAUNCH(k_dream_draw, dim3((rows + 63) / 64), dim3(64), 0, (hipStream_t)st, (DevRng *)rng, gz, rows, n);
 }
 
 extern "C" void ramd_launch_texts_continue(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,

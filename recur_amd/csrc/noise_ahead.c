@@ -29,12 +29,18 @@ static int ahead_mode(void) {
   return mode;
 }
 
-static void ahead_ensure_device(RamdEngine *e) {
-  RamdNoiseAheadDev *d = &e->ahead_dev;
+/* the side stream, made at its first use (dream_api.c draws a frame's noise ahead on it as well) */
+hipStream_t ramd_side_stream_ensure(void) {
   if (!ramd_side_stream) {
     HIP_OK(hipStreamCreateWithFlags(&ramd_side_stream, hipStreamNonBlocking));
     ramd_note_side_stream();
   }
+  return ramd_side_stream;
+}
+
+static void ahead_ensure_device(RamdEngine *e) {
+  RamdNoiseAheadDev *d = &e->ahead_dev;
+  ramd_side_stream_ensure();
   if (!d->go) {
     HIP_OK(hipEventCreateWithFlags((hipEvent_t *)&d->go, hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags((hipEvent_t *)&d->done[0], hipEventDisableTiming));

@@ -332,6 +332,34 @@ struct RamdAutomatonStep;
 void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
                                 const struct RamdAutomatonStep *p);
 
+/* rnn_amd_dream_sequences (dream_api.c): parrot's player (fill_audio_chunk, gstparrot.c:556-583) for `rows` sequences in
+ * lock step, sequence k on forward-only state row row0 + k, each fed its own last answer; the net has as many inputs as
+ * outputs.  The rule is dream_rule.h's.  Three kinds of launch:
+ *   a call's first (first != NULL): the input row of every row's first forward pass from its row of first[rows][ld_first],
+ *     on hid0's hidden values, or with a NULL hid0 on the row's own.  Nothing is emitted and no draw is read.
+ *   between two passes (first NULL, next NULL): emit -- dream_tanh of every output the pass just left in the row's out row
+ *     into emit[row][output_size], the frame's place in the segment's buffer -- and feed: dream_next of the same values,
+ *     with `noise` and, unless noise == 0, the frame's draws gz[output_size][rows] (ramd_launch_dream_draw's), as the
+ *     dense row of the next pass's input row, the soft clip included, on the row's own hidden values.
+ *   a call's last (next != NULL): the emit half, and the row dream_next gives into next[row][input_size] instead of the
+ *     input row.
+ * A workgroup reads its own row's out and hidden rows and draws and no other row's; every word has one writer: no
+ * atomics.  gz may be NULL where noise == 0.  All pointers are device pointers. */
+typedef struct RamdDreamStep {
+  const float *first; /* [rows][ld_first] the rows' first inputs, or NULL                   */
+  float *emit;        /* [rows][output_size] the frame to emit (first == NULL)              */
+  float *next;        /* [rows][input_size] the rows behind the last frame, or NULL         */
+  const float *gz;    /* [output_size][rows] the frame's draws, value-major                 */
+  const float *hid0;  /* the hidden row of the first feed, or NULL                          */
+  int ld_first;
+  int row0, rows;
+  float noise;
+} RamdDreamStep;
+void ramd_launch_dream_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdDreamStep *p);
+/* one frame's draws for it: n values of cheap_gaussian_noise per row, in index order, from the call's generators
+ * rng[rows] (rand_ctx; stored back) into gz[n][rows], value-major -- one lane per row, meant for a stream beside the forward pass */
+void ramd_launch_dream_draw(ramd_stream_t st, void *rng, float *gz, int rows, int n);
+
 /* rnn_amd_continue_texts and rnn_amd_sample_texts (sample_api.c): launch t = 0 .. of a wave of prompts, ordered by prompt
  * length + max_len; the launch is for the wave's first `rows` rows.  What it does for a row is continue_rule.h's
  * continue_step(plen[row], max_len, t) --

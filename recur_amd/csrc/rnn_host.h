@@ -161,6 +161,7 @@ static inline void ramd_top_done_set(RamdEngine *e, int row0, int n, int masked)
 
 extern hipStream_t ramd_stream;        /* engine.c: the library's stream (rnn_amd_use_device) */
 extern hipStream_t ramd_side_stream;   /* noise_ahead.c: the stream the noise is generated ahead on, or NULL */
+hipStream_t ramd_side_stream_ensure(void); /* noise_ahead.c: that stream, made at its first use */
 extern hipEvent_t ramd_half_summed[2]; /* exchange.c: a half's sum over the ranks has arrived (ramd_delta_half_ready) */
 #endif
 
@@ -220,7 +221,7 @@ int ramd_run_texts_refused(const char *who, const RecurNN *net, const u8 *const 
                            int alphabet_len, const void *out);
 
 /* rows_host.c: what the batched calls on forward-only state rows share (texts_api.c, sample_api.c, seqs_api.c,
- * classify_texts_api.c, automaton_api.c) */
+ * classify_texts_api.c, automaton_api.c, dream_api.c) */
 /* what all of them refuse about the net, without a device: a bottom layer, heads that do not divide the output row
  * (alphabet_len 0: no heads).  -1 with a message on stderr, else 0 */
 int ramd_texts_net_refused(const char *who, const RecurNN *net, int alphabet_len);

@@ -1,6 +1,7 @@
 /* rows_host.c -- what the batched forward-only calls share on the host (gnu11 C): rnn_amd_run_texts and _trace_texts
  * (texts_api.c), rnn_amd_sample_texts and _continue_texts (sample_api.c), rnn_amd_run_sequences (seqs_api.c),
- * rnn_amd_classify_texts (classify_texts_api.c) and rnn_amd_run_automaton (automaton_api.c) each give every text, sequence or cell a forward-only state row of the engine's
+ * rnn_amd_classify_texts (classify_texts_api.c), rnn_amd_run_automaton (automaton_api.c) and rnn_amd_dream_sequences
+ * (dream_api.c) each give every text, sequence or cell a forward-only state row of the engine's
  * own.  Stated once here: what all of them refuse about the net, the net's hidden row for the rows that never reach the
  * device, how a call opens the rows (ramd_rows_open), how start and final states travel between the caller's arrays and
  * the rows (ramd_rows_states_in / _out; which state belongs to which row stays texts_states.h's business), the forward

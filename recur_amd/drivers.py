@@ -14,7 +14,8 @@ in the same form; ``classify_texts`` runs a list of encoded texts against one cl
 (rnn_amd_classify_texts): per text the sums and sums of squares of every class's probability and the score against the
 symbols' classes; ``run_automaton`` plays rnnca's automaton from a seed frame on an ``AutomatonGeometry`` in one call
 (rnn_amd_run_automaton): the frames as uint8 [n][3][height][width] and the cells' states, and ``parse_offsets`` expands an
-offset pattern (rnn_amd_automaton_parse_offsets).  ``synthetic_text_np`` is the seeded symbol stream of
+offset pattern (rnn_amd_automaton_parse_offsets); ``dream_sequences`` runs parrot's player, many closed-loop sequences fed
+their own answers, in one call (rnn_amd_dream_sequences).  ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
 """
@@ -362,6 +363,41 @@ def run_automaton(lib, net, geometry, seed, n_frames, h_in=None, want_out=True, 
         hout = hout[:cells]
         assert not np.any(np.isnan(hout[:, 1:1 + net.contents.hidden_size])), "a state was not written"
     return frames[:count].reshape(n_frames, 3, g.height, g.width).copy(), hout
+
+
+def dream_sequences(lib, net, first, n_frames, noise=1.0, seeds=None, rng_in=None, h_in=None, segment_frames=0,
+                    want_out=True, in_place=False):
+    """rnn_amd_dream_sequences: n_frames frames of parrot's player for len(first) closed-loop sequences, every sequence a
+    forward-only clone of net fed its own last answer, from the rows of first (float32 [n][ld], ld >= input_size).
+    seeds: a uint64 per sequence; rng_in: a uint64 array [n][4] as the drivers return generators (seeds may then be
+    None); with noise == 0 both may be None.  Returns (frames float32 [n_frames][n][output_size], next float32
+    [n][input_size], h_out [n][h_size] float32 or None with want_out=False, rng_out uint64 [n][4]).  h_in, want_out and
+    in_place as in the _from text drivers; in_place also hands rng_in itself to the call as rng_out.  frames and next are
+    allocated with guard floats behind them (NaN), which must come back untouched."""
+    fr = np.ascontiguousarray(first, dtype=np.float32)
+    assert fr.ndim == 2, "first is [n][ld]"
+    n, ld = fr.shape
+    isz, osz = net.contents.input_size, net.contents.output_size
+    sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+    assert sd is None or len(sd) == n
+    gi = None
+    if rng_in is not None:
+        gi = rng_in if in_place else np.ascontiguousarray(rng_in, dtype=np.uint64)
+        assert gi.dtype == np.uint64 and gi.flags.c_contiguous and gi.shape == (n, 4), "generators are [n][4] uint64"
+    count = n_frames * n * osz
+    frames = np.full(count + TRACE_GUARD, np.nan, np.float32)
+    nxt = np.full(n * isz + TRACE_GUARD, np.nan, np.float32)
+    rng = gi if in_place and gi is not None else np.zeros((max(n, 1), 4), np.uint64)
+    hin, hout, hip, hop = _states(net, n, h_in, want_out, in_place)
+    r = lib.rnn_amd_dream_sequences(net, rc.fptr(fr), ld, n, n_frames, noise,
+                                    None if sd is None else sd.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                    None if gi is None else gi.ctypes.data_as(C.POINTER(rc.RandCtx)), hip, hop,
+                                    segment_frames, rc.fptr(frames), rc.fptr(nxt), rng.ctypes.data_as(C.POINTER(rc.RandCtx)))
+    if r != 0:
+        raise ValueError("rnn_amd_dream_sequences refused the call (see stderr)")
+    assert np.all(np.isnan(frames[count:])) and np.all(np.isnan(nxt[n * isz:])), "floats behind the last frame or row"
+    return frames[:count].reshape(n_frames, n, osz).copy(), nxt[:n * isz].reshape(n, isz).copy(), \
+        None if hout is None else hout[:n], rng[:n]
 
 
 class ApiSet:
