@@ -24,8 +24,11 @@
 //
 // The rows above the last whole 64-row tile (the input rows of a text net: 44 at the north star) need no K split
 // either: the error quad a workgroup has in registers anyway is four interleaved 16-column groups, and the 16 workgroups of a column tile (mt = 0 .. 15) each
-// take ONE (quarter of the rest rows mt / 4, column group mt % 4) pair for all of K: one more dword load and one more MFMA per 16,
-// the same 6 % as sharing the rest tile out by K would cost, and no partial planes to add up afterwards.  The
+// take ONE (quarter of the rest rows mt / 4, column group mt % 4) pair for all of K: two more dword loads and one more MFMA per 16,
+// the same 6 % as sharing the rest tile out by K would cost, and no partial planes to add up afterwards.  (The second
+// dword is the piece's column group of the error quad over again, at the quad's per-lane offset + mt % 4 floats: picked
+// out of the quad's registers by wave-uniform selects it cost three vector-ALU instructions and a hazard nop per
+// iteration, and an f32 MFMA occupies the vector ALU -- 2.8 us per launch; a load issues in the MFMAs' shadow.)  The
 // workgroup updates its 16 x 16 piece like its tile.  The columns outside 1 .. hidden_size (delta 0 there:
 // recur-nn.c:334-337) are the first and last column tiles' business, the top layer's update (45 k weights) is shared
 // out over all workgroups: with the momentum rule the launch leaves NOTHING for an optimiser launch.
@@ -113,18 +116,25 @@ template <int N> __device__ __forceinline__ void dd_wait4(dd_f4 &a, dd_f4 &b, fl
 template <int N> __device__ __forceinline__ void dd_wait5(dd_f4 &a, dd_f4 &b, float &c, float &d, float &e) {
   asm volatile("s_waitcnt vmcnt(%5)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e) : "n"(N));
 }
+template <int N> __device__ __forceinline__ void dd_wait6(dd_f4 &a, dd_f4 &b, float &c, float &d, float &e, float &f) {
+  asm volatile("s_waitcnt vmcnt(%6)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f) : "n"(N));
+}
+template <int N> __device__ __forceinline__ void dd_wait7(dd_f4 &a, dd_f4 &b, float &c, float &d, float &e, float &f, float &g) {
+  asm volatile("s_waitcnt vmcnt(%7)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g) : "n"(N));
+}
 /* Wait for EVERY load of the wave, with the ring's registers as operands: hipcc does not know that the loads of the
  * inline asm are asynchronous, and a register of the ring that it considers dead it hands to something else -- which
  * the load then overwrites when it lands (seen: the accumulators, moved into ring registers behind the loop, took
  * the values of the surplus loads of the last round).  As operands of this wait the registers are alive until it. */
-template <int P> __device__ __forceinline__ void dd_drain(const dd_f4 (&a)[P], const dd_f4 (&b)[P], const float (&c)[2][P], const float (&d)[P]) {
+template <int P> __device__ __forceinline__ void dd_drain(const dd_f4 (&a)[P], const dd_f4 (&b)[P], const float (&c)[2][P], const float (&s)[2][P], const float (&d)[P]) {
   static_assert(P == 5, "operand list");
   /* (inputs only: as tied operands hipcc copied the registers -- loads outstanding -- in front of the wait) */
   asm volatile("s_waitcnt vmcnt(0)"
                :
                : "v"(a[0]), "v"(a[1]), "v"(a[2]), "v"(a[3]), "v"(a[4]), "v"(b[0]), "v"(b[1]), "v"(b[2]), "v"(b[3]), "v"(b[4]),
                  "v"(c[0][0]), "v"(c[0][1]), "v"(c[0][2]), "v"(c[0][3]), "v"(c[0][4]), "v"(c[1][0]), "v"(c[1][1]), "v"(c[1][2]),
-                 "v"(c[1][3]), "v"(c[1][4]), "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(d[4])
+                 "v"(c[1][3]), "v"(c[1][4]), "v"(s[0][0]), "v"(s[0][1]), "v"(s[0][2]), "v"(s[0][3]), "v"(s[0][4]), "v"(s[1][0]), "v"(s[1][1]),
+                 "v"(s[1][2]), "v"(s[1][3]), "v"(s[1][4]), "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(d[4])
                : "memory");
 }
 template <int... Is, class F>
@@ -217,7 +227,7 @@ __device__ __forceinline__ void dd_body(const DdArgs &a, float *lds, PRE pre = P
   const int rg = (a.rest + RG - 1) / RG;
   int ri[NPW], rj[NPW], rrows[NPW]; /* (rrows: the group's rows that exist) */
   unsigned voff_r[NPW];
-  unsigned long long sel_lo[NPW], sel_hi[NPW]; /* register rj of a quad, by two wave-uniform masks (as ?: chains hipcc makes branches of it) */
+  unsigned voff_s[NPW]; /* column group rj of the error quad as a dword of its own: the quad's offset + rj floats */
 #pragma unroll
   for (int p = 0; p < NPW; p++) {
     const int pi = has_rest ? NPW * mt + p : 0;
@@ -228,8 +238,7 @@ __device__ __forceinline__ void dd_body(const DdArgs &a, float *lds, PRE pre = P
     const int c = lane & 15;
     const int rcol = rrows[p] > 0 ? 64 * a.tm - m0 + ri[p] * rg + (c < rrows[p] ? c : rrows[p] - 1) : 0;
     voff_r[p] = (unsigned)(((size_t)(lane >> 4) * I + rcol) * sizeof(float));
-    sel_lo[p] = (rj[p] & 1) ? ~0ull : 0ull;
-    sel_hi[p] = (rj[p] & 2) ? ~0ull : 0ull;
+    voff_s[p] = voff + (unsigned)(rj[p] * sizeof(float));
   }
   const unsigned voff_c = (unsigned)((lane >> 4) * sizeof(float));
 
@@ -253,7 +262,7 @@ __device__ __forceinline__ void dd_body(const DdArgs &a, float *lds, PRE pre = P
   }
 
   dd_f4 ra[P], re[P];
-  float rr[2][P], rcf[P]; /* (rr[1]: the second piece's loads, NPW == 2) */
+  float rr[2][P], rs[2][P], rcf[P]; /* (rr[1], rs[1]: the second piece's loads, NPW == 2) */
   /* The operands of this wave's iterations, in order: quad (step t, streams 4 within .. + 3), from quad q0 on in
    * steps of NW / 2.  The generator is scalar and branch-free (counters, selects and multiplies on the scalar ALU: it is
    * scheduled into the shadows of the MFMAs; a division would go through the vector ALU, a branch would end the
@@ -269,16 +278,18 @@ __device__ __forceinline__ void dd_body(const DdArgs &a, float *lds, PRE pre = P
     g_xb = a.x + (size_t)slot * a.plane + ro + m0;
     g_eb = a.e + (size_t)t * a.plane + ro + n0;
     g_cb = a.coef + (size_t)t * a.Scap + (g_within << 2);
-    g_within += ST;
-    const int wrap = g_within >= QPS ? 1 : 0;
-    g_within -= wrap ? QPS : 0;
-    g_t += wrap;
+    /* (the wrap by a sign mask, not by a compare: of `wrap = g_within >= QPS` hipcc kept a copy in a VGPR -- a
+     * v_cndmask_b32 per iteration, on the vector ALU that the f32 MFMAs occupy: 2.4 us per launch at the north star,
+     * profiles/NOTES_r07.md) */
+    const int over = g_within + ST - QPS, neg = over >> 31; /* over >= 0: the step's last quad is behind us */
+    g_within = over + (neg & QPS);
+    g_t += 1 + neg;
   };
   dd_f4 acc[4][4], racc[NPW];
 #pragma unroll
   for (int p = 0; p < NPW; p++) racc[p] = dd_f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int j = 0; j < P; j++) rr[1][j] = 0.0f;
+  for (int j = 0; j < P; j++) rr[1][j] = rs[1][j] = 0.0f;
 #pragma unroll
   for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -291,13 +302,16 @@ __device__ __forceinline__ void dd_body(const DdArgs &a, float *lds, PRE pre = P
     ra[j] = dd_load4<true>(g_xb, voff);
     re[j] = dd_load4<true>(g_eb, voff);
 #pragma unroll
-    for (int p = 0; p < NPW; p++) rr[p][j] = dd_load1<true>(g_xb, voff_r[p]);
+    for (int p = 0; p < NPW; p++) {
+      rr[p][j] = dd_load1<true>(g_xb, voff_r[p]);
+      rs[p][j] = dd_load1<true>(g_eb, voff_s[p]);
+    }
   });
   pre(); /* (its own loads are younger than the ring's: every counted wait below then waits for them too, never for less) */
   int ones;
   {
     DDIR_STAMP(1);
-    dd_flag_wait<(2 + NPW) * P>(fl_n, fl_s);
+    dd_flag_wait<(2 + 2 * NPW) * P>(fl_n, fl_s);
     DDIR_STAMP(2);
     DDIR_CLOCKS(0);
     bool ok = true;
@@ -312,35 +326,36 @@ __device__ __forceinline__ void dd_body(const DdArgs &a, float *lds, PRE pre = P
     constexpr bool ONES = decltype(ONESC)::value;
     dd_static_for<P>([&](auto JC) {
       constexpr int j = decltype(JC)::value;
-      constexpr int PER = 2 + NPW + (ONES ? 0 : 1); /* loads per iteration */
-      if constexpr (ONES && NPW == 1) dd_wait3<PER * (P - 1)>(ra[j], re[j], rr[0][j]);
-      else if constexpr (ONES) dd_wait4<PER * (P - 1)>(ra[j], re[j], rr[0][j], rr[1][j]);
-      else if constexpr (NPW == 1) dd_wait4<PER * (P - 1)>(ra[j], re[j], rr[0][j], rcf[j]);
-      else dd_wait5<PER * (P - 1)>(ra[j], re[j], rr[0][j], rr[1][j], rcf[j]);
+      constexpr int PER = 2 + 2 * NPW + (ONES ? 0 : 1); /* loads per iteration */
+      if constexpr (ONES && NPW == 1) dd_wait4<PER * (P - 1)>(ra[j], re[j], rr[0][j], rs[0][j]);
+      else if constexpr (ONES) dd_wait6<PER * (P - 1)>(ra[j], re[j], rr[0][j], rr[1][j], rs[0][j], rs[1][j]);
+      else if constexpr (NPW == 1) dd_wait5<PER * (P - 1)>(ra[j], re[j], rr[0][j], rs[0][j], rcf[j]);
+      else dd_wait7<PER * (P - 1)>(ra[j], re[j], rr[0][j], rr[1][j], rs[0][j], rs[1][j], rcf[j]);
       dd_f4 fa = ra[j], fe = re[j];
-      float fr[NPW];
+      float fr[NPW], fsel[NPW];
 #pragma unroll
-      for (int p = 0; p < NPW; p++) fr[p] = rr[p][j];
+      for (int p = 0; p < NPW; p++) {
+        fr[p] = rr[p][j];
+        fsel[p] = rs[p][j];
+      }
       if constexpr (!ONES) {
-        /* v_mul_legacy_f32: 0 * x is 0 for ANY x (a step past the break may hold inf), otherwise the IEEE product */
-        asm volatile("v_mul_legacy_f32 %0, %4, %0\n\tv_mul_legacy_f32 %1, %4, %1\n\t"
-                     "v_mul_legacy_f32 %2, %4, %2\n\tv_mul_legacy_f32 %3, %4, %3\n\ts_nop 1"
-                     : "+v"(fe[0]), "+v"(fe[1]), "+v"(fe[2]), "+v"(fe[3])
-                     : "v"(rcf[j]));
+        /* v_mul_legacy_f32: 0 * x is 0 for ANY x (a step past the break may hold inf), otherwise the IEEE product.
+         * (s_nop 1: two wait states between a vector-ALU write and the MFMA that reads the register -- hipcc puts ONE
+         * behind an inline-asm output: tools/isa_lint_async_loads.py checks it) */
+        if constexpr (NPW == 1)
+          asm volatile("v_mul_legacy_f32 %0, %5, %0\n\tv_mul_legacy_f32 %1, %5, %1\n\t"
+                       "v_mul_legacy_f32 %2, %5, %2\n\tv_mul_legacy_f32 %3, %5, %3\n\tv_mul_legacy_f32 %4, %5, %4\n\ts_nop 1"
+                       : "+v"(fe[0]), "+v"(fe[1]), "+v"(fe[2]), "+v"(fe[3]), "+v"(fsel[0])
+                       : "v"(rcf[j]));
+        else
+          asm volatile("v_mul_legacy_f32 %0, %6, %0\n\tv_mul_legacy_f32 %1, %6, %1\n\t"
+                       "v_mul_legacy_f32 %2, %6, %2\n\tv_mul_legacy_f32 %3, %6, %3\n\tv_mul_legacy_f32 %4, %6, %4\n\t"
+                       "v_mul_legacy_f32 %5, %6, %5\n\ts_nop 1"
+                       : "+v"(fe[0]), "+v"(fe[1]), "+v"(fe[2]), "+v"(fe[3]), "+v"(fsel[0]), "+v"(fsel[NPW - 1])
+                       : "v"(rcf[j]));
       }
       __builtin_amdgcn_sched_barrier(0);
       advance(); /* the slot's next tenant: its addresses, between the MFMAs */
-      float fsel[NPW];
-#pragma unroll
-      for (int p = 0; p < NPW; p++) {
-        float s01, s23;
-        asm("v_cndmask_b32 %0, %2, %3, %6\n\tv_cndmask_b32 %1, %4, %5, %6"
-            : "=&v"(s01), "=&v"(s23) : "v"(fe[0]), "v"(fe[1]), "v"(fe[2]), "v"(fe[3]), "s"(sel_lo[p]));
-        /* (s_nop 1: two wait states between a vector-ALU write and the MFMA that reads the register -- hipcc puts ONE
-         * behind an inline-asm output, and the second piece's MFMA directly behind its select then read the old value:
-         * tools/isa_lint_async_loads.py checks it) */
-        asm("v_cndmask_b32 %0, %1, %2, %3\n\ts_nop 1" : "=v"(fsel[p]) : "v"(s01), "v"(s23), "s"(sel_hi[p]));
-      }
 #pragma unroll
       for (int i = 0; i < 4; i++)
 #pragma unroll
@@ -357,7 +372,10 @@ __device__ __forceinline__ void dd_body(const DdArgs &a, float *lds, PRE pre = P
       ra[j] = dd_load4(g_xb, voff);
       re[j] = dd_load4(g_eb, voff);
 #pragma unroll
-      for (int p = 0; p < NPW; p++) rr[p][j] = dd_load1(g_xb, voff_r[p]);
+      for (int p = 0; p < NPW; p++) {
+        rr[p][j] = dd_load1(g_xb, voff_r[p]);
+        rs[p][j] = dd_load1(g_eb, voff_s[p]);
+      }
       if constexpr (!ONES) rcf[j] = dd_load1(g_cb, voff_c);
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -371,14 +389,14 @@ __device__ __forceinline__ void dd_body(const DdArgs &a, float *lds, PRE pre = P
 #endif
 #pragma unroll
     for (int j = 0; j < P; j++) rcf[j] = 0.0f;
-    dd_drain<P>(ra, re, rr, rcf); /* the surplus loads (a wait per path: one behind the join costs copies of the ring) */
+    dd_drain<P>(ra, re, rr, rs, rcf); /* the surplus loads (a wait per path: one behind the join costs copies of the ring) */
   } else {
     /* the rare launch (a stream was soft-clipped or stopped early): drop the ring and start over with the
-     * coefficients as a fourth load per iteration -- one round trip, instead of a first round with waits of its
+     * coefficients as one more load per iteration -- one round trip, instead of a first round with waits of its
      * own, whose code hipcc gave register copies between a load and its wait */
 #pragma unroll
     for (int j = 0; j < P; j++) rcf[j] = 0.0f;
-    dd_drain<P>(ra, re, rr, rcf);
+    dd_drain<P>(ra, re, rr, rs, rcf);
     g_t = g_t0;
     g_within = g_w0;
     dd_static_for<P>([&](auto JC) {
@@ -387,11 +405,14 @@ __device__ __forceinline__ void dd_body(const DdArgs &a, float *lds, PRE pre = P
       ra[j] = dd_load4<true>(g_xb, voff);
       re[j] = dd_load4<true>(g_eb, voff);
 #pragma unroll
-      for (int p = 0; p < NPW; p++) rr[p][j] = dd_load1<true>(g_xb, voff_r[p]);
+      for (int p = 0; p < NPW; p++) {
+        rr[p][j] = dd_load1<true>(g_xb, voff_r[p]);
+        rs[p][j] = dd_load1<true>(g_eb, voff_s[p]);
+      }
       rcf[j] = dd_load1<true>(g_cb, voff_c);
     });
     for (int i0 = 0; i0 < n_it; i0 += P) round(std::false_type{});
-    dd_drain<P>(ra, re, rr, rcf);
+    dd_drain<P>(ra, re, rr, rs, rcf);
   }
 
   // ---- the waves' tiles meet in LDS; every thread then owns float4s of the finished tile
