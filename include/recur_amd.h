@@ -386,7 +386,27 @@ void rnn_amd_set_put_o_error(RnnAmdSet *set, const float *o_error, int ld);
  * (badmaths.h:14-29, 71-141).  Per stream it adds the error of the target
  * class, log2(1 - that error) (capped, charmodel-helpers.h:11-13) and the
  * "winner == target" count into device accumulators read by
- * rnn_amd_set_read_stats. */
+ * rnn_amd_set_read_stats.
+ *
+ * ROWS THAT ARE NOT FINITE.  This holds for every loss of this part (the softmax, class-group, multi-head and sigmoid
+ * errors, the text steps, rnn_char_cross_entropy and rnn_char_multi_cross_entropy) and for the batched calls below
+ * (rnn_amd_run_texts and _heads, rnn_amd_trace_texts, rnn_amd_classify_texts, rnn_amd_run_sequences, their _from forms).
+ * The reference's fast_expf halves its argument's exponent in a loop that an infinity never leaves; the library's
+ * (csrc/fast_exp_rule.h) is the same function on every finite float and gives NaN for an argument that is not finite.
+ * An unbounded activation or a diverged net can overflow an output row, and rnn_amd_run_sequences takes the caller's
+ * floats, so:
+ *   - A softmax -- a head, a class group, a whole output row -- that contains an infinity or a NaN has no likelihoods.
+ *     Every float the call derives from it is NaN: its errors, likelihoods and log-likelihoods, and the per-text and
+ *     per-set sums they are added into (error, entropy, the cross entropies, sums and sums of squares).  The sigmoid of
+ *     an output that is not finite is NaN, and so is its error; it is elementwise and touches no other output.
+ *   - The integer by-products of such a softmax -- the best guess, a winner byte, `correct` -- are unspecified.  `count`
+ *     is not: the step is counted.
+ *   - Every other head, group, row, stream or text of the same call is untouched, bit for bit; outputs that take part in
+ *     no softmax or sigmoid (the columns of rnn_amd_run_sequences outside every group) are copied as they are.
+ *   - Every call returns.
+ * A NaN error row then spreads through the deltas into the weights, as it would on any path: the contract is about the
+ * call that meets the row.  The samplers (rnn_amd_sample_texts, rnn_amd_continue_texts) say below what they do with an
+ * output row without a total: the row ends at the attempt cap and the call returns -1. */
 void rnn_amd_set_softmax_error(RnnAmdSet *set, const int *target);
 
 /* == for every j with (active == NULL || active[j]):
@@ -623,6 +643,8 @@ void rnn_amd_run_text_heads(RecurNN *net, const u8 *text, int len, int skip, int
  * was.  The clones are state rows of the engine's own, not nets; the texts run side by side, longest first, in waves of
  * up to 256 rows with one device synchronisation per wave.
  * skips may be NULL (all zeros); a text with len < 2 scores 0.0; n_texts == 0 returns 0 and touches nothing.
+ * A text whose output row holds an infinity or a NaN at a scored step has a NaN sum; every other text is untouched and the
+ * call returns ("Rows that are not finite" at rnn_amd_set_softmax_error above -- it covers every batched call here).
  * Returns 0, or -1 with a message on stderr and nothing computed (checked before anything needs a device): n_texts < 0,
  * a NULL array with n_texts > 0, heads that do not divide the output row, a net with a bottom layer -- the layer has
  * ONE input buffer shared by every clone (recur-nn-init.c:345-346, charmodel-helpers.h:20-31), which leaves

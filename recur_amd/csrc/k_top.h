@@ -4,27 +4,14 @@
 // section 2; callable pieces are what folding the top layer into another launch needs.)
 #pragma once
 #include "k_common.h"
+#include "fast_exp_rule.h"
 #ifndef TT_STAMP /* (development stamps of the top launches: kernels_loss.hip defines them in a PC_STAMPS build) */
 #define TT_STAMP(i) do { } while (0)
 #endif
 
-// badmaths.h:14-29, kept operation for operation
-__device__ __forceinline__ float fast_expf_dev(float x) {
-#pragma clang fp contract(off)
-  int count = 0;
-  while (fabsf(x) > 0.2) {
-    x *= 0.125;
-    count++;
-  }
-  float a = ((x + 3) * (x + 3) + 3) / ((x - 3) * (x - 3) + 3);
-  while (count) {
-    a *= a;
-    a *= a;
-    a *= a;
-    count--;
-  }
-  return a;
-}
+// badmaths.h:14-29, kept operation for operation and ending on every float: fast_exp_rule.h.  An argument that is not
+// finite gives NaN, so a softmax with an infinity or a NaN in it has NaN likelihoods and every kernel below returns.
+__device__ __forceinline__ float fast_expf_dev(float x) { return fast_expf(x); }
 
 // ---- the softmax loss in pieces (charmodel-predict.c:18-27, badmaths.h:71-141).  Every loss kernel is built from these; what
 // differs between callers -- where the values lie, which reduction, which fence -- is an argument.  Each piece carries its

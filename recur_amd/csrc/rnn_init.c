@@ -6,6 +6,7 @@
  * reproducible by seed (recur-rng.h; recur-nn-init.c:382-742).
  */
 #include "rnn_host.h"
+#include "fast_exp_rule.h"
 #include <time.h>
 
 /* ---------------------------------------------------------------- PRNG -- */
@@ -70,21 +71,8 @@ float ramd_cheap_gaussian_noise(rand_ctx *x) {
   return (float)(a - 0xffff * 6) / (0xffff);
 }
 
-/* badmaths.h:14-29 */
-float ramd_fast_expf(float x) {
-  int count = 0;
-  while (fabsf(x) > 0.2) {
-    x *= 0.125;
-    count++;
-  }
-  float a = ((x + 3) * (x + 3) + 3) / ((x - 3) * (x - 3) + 3);
-  for (; count; count--) {
-    a *= a;
-    a *= a;
-    a *= a;
-  }
-  return a;
-}
+/* badmaths.h:14-29, ending on every float: fast_exp_rule.h */
+float ramd_fast_expf(float x) { return fast_expf(x); }
 
 /* ------------------------------------------------------------ flat init -- */
 

@@ -13,8 +13,19 @@ ih_w[1 + hidden_size + c, 1 + c] = 1 (symbol c's input row, hidden unit c's colu
 ho_w[1 + c, :] = row_c.  A stream that reads symbol c has the hidden layer bias + unit c and the output row row_c, bit for
 bit under any summation order: every other product is an exact zero.
 
-Never a NaN or an infinity in a row or a weight: fast_expf's scaling loop does not end on one (a hang on the device).
-`checked` asserts |logit| <= 1e4 on everything the catalogue hands out.
+`rows` hands out finite rows only, and `checked` asserts |logit| <= 1e4 on every one of them: they go to the oracle and to
+the compiled reference, whose fast_expf is badmaths.h's own -- its scaling loop does not end on an infinity (inf * 0.125
+is inf), so NO test may hand the oracle or a reference binary a row that is not finite.  The library's exponential
+(recur_amd/csrc/fast_exp_rule.h) is the same function on every finite float and ends on the others: an argument that is
+not finite gives a quiet NaN in no rounds.  What follows from that is the library's contract (include/recur_amd.h, "Rows
+that are not finite"): a softmax with an infinity or a NaN in it has no likelihoods -- every float derived from it is NaN;
+its integer by-products (best guess, `correct`) are unspecified, `count` is not -- every other head, group, row, stream or
+text of the same call is untouched bit for bit, and every call returns.  `nonfinite_rows` is the catalogue of such rows,
+for the library alone (tests/test_fast_exp_rule.py, tests/test_gpu_nonfinite_rows.py); `fast_expf` below restates the
+library's rule, which is the reference's wherever the reference returns.  `designed_nonfinite_weights` writes those rows
+into a net from FINITE weights (0 * inf is NaN and would poison every stream): the poisoned symbol's hidden unit is 2, its
+output weights +-2e38 where an infinity is wanted (one product overflows, under any summation order) and half the row
+elsewhere; for a NaN a second unit brings -inf against +inf.
 """
 import numpy as np
 
@@ -91,6 +102,40 @@ def rows(n, seed=0):
     return out
 
 
+def nonfinite_rows(n, seed=0):
+    """name -> float32 row of length n with an infinity or a NaN in it: the same base row and the same p, q as `rows`.  For
+    the library alone -- never for the oracle or a reference binary, whose exponential does not return on them.
+    `pos_inf_late` (n > 64) has its infinity at n - 1: a lane's second value, the last partial float4 and, for n > 128, past
+    the 128 values a wave holds in registers."""
+    b = base_row(n, seed)
+    p, q = n // 2, (n // 2 + 1) % n
+    out = {}
+
+    def put(name, *entries):
+        row = b.copy()
+        for pos, val in entries:
+            row[pos] = val
+        out[name] = row
+
+    put("pos_inf", (p, np.inf))
+    put("neg_inf", (p, -np.inf))
+    if n >= 2:
+        put("both", (p, np.inf), (q, -np.inf))
+    put("nan", (p, np.nan))
+    if n > 64:
+        put("pos_inf_late", (n - 1, np.inf))
+    return out
+
+
+def arrivals(row):
+    """what reaches the exponential from a row: -> (the shift's branch, the arguments row + shift); for a row of
+    `nonfinite_rows` some argument is infinite -- the loop that did not end -- or, for `nan`, a NaN"""
+    row = np.asarray(row, np.float32)
+    adj, branch = softmax_shift(*c_extremes(row))
+    with np.errstate(invalid="ignore"):
+        return branch, row + adj
+
+
 def sigmoid_arguments():
     g = np.linspace(-120.0, 120.0, 49).astype(np.float32)  # steps of 5: loop counts 0 (at 0) to 4
     p2 = F(0.2)
@@ -103,12 +148,14 @@ def sigmoid_arguments():
 # ------------------------------------------------------------------ the formulas, float32 as the C states them --
 
 def fast_expf(x):
-    """-> (values, loop counts); `fabsf(x) > 0.2` compares in double, as the C does"""
+    """-> (values, loop counts); `fabsf(x) > 0.2` compares in double, as the C does.  An argument that is not finite is NaN in
+    no rounds (fast_exp_rule.h: the reference's loop would not end on an infinity)"""
     x = np.array(x, np.float32, ndmin=1)
     count = np.zeros(x.shape, np.int64)
+    finite = np.isfinite(x)
     with np.errstate(over="ignore", under="ignore", invalid="ignore"):
         while True:
-            m = np.abs(x.astype(np.float64)) > 0.2
+            m = finite & (np.abs(x.astype(np.float64)) > 0.2)
             if not m.any():
                 break
             x[m] *= F(0.125)
@@ -118,12 +165,28 @@ def fast_expf(x):
             m = count > k
             for _ in range(3):
                 a[m] = a[m] * a[m]
+    a[~finite] = np.nan
     return a, count
 
 
 def fast_sigmoid(x):
-    with np.errstate(over="ignore", under="ignore"):
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
         return F(1) / (F(1) + fast_expf(-np.asarray(x, np.float32) * F(1))[0])
+
+
+def c_extremes(row):
+    """(lo, hi) as C's comparisons find them (badmaths.h:76-80: hi = MAX(hi, x), lo = MIN(lo, x) from row[0] on, the macros
+    being `hi >= x ? hi : x` and `lo < x ? lo : x`): a comparison with a NaN is false, so the NaN is taken and then given up
+    for the next value -- only one at the end of the row stays.  (The device's fminf / fmaxf pass over a NaN anywhere;
+    either way the NaN itself reaches the exponential and the row has no total.)"""
+    row = np.asarray(row, np.float32)
+    if not np.isnan(row).any():
+        return row.min(), row.max()
+    lo = hi = row[0]
+    for x in row[1:]:
+        hi = hi if hi >= x else x
+        lo = lo if lo < x else x
+    return lo, hi
 
 
 def softmax_shift(lo, hi, mutation=None):
@@ -149,7 +212,7 @@ MUTATIONS = ("ge_50", "no_lo", "no_min", "highest_tie", "cap_1e20")
 def softmax_best_guess(row, mutation=None):
     """the numpy restatement of orc_softmax_best_guess: -> (error row = -softmax, best index); `mutation` changes one rule"""
     row = np.asarray(row, np.float32)
-    adj, _ = softmax_shift(row.min(), row.max(), mutation)
+    adj, _ = softmax_shift(*c_extremes(row), mutation=mutation)
     with np.errstate(over="ignore", under="ignore", invalid="ignore"):
         ex, _ = fast_expf(row + adj)
         total = np.cumsum(ex, dtype=np.float32)[-1]  # in index order, as the reference's loop adds
@@ -182,7 +245,7 @@ def branch_of(row):
     """the shift branch ('none', 'hi', 'room', 'limited'), the largest fast_expf loop count, whether a likelihood is
     denormal, whether one is zero, and whether two entries tie for the best guess"""
     row = np.asarray(row, np.float32)
-    adj, branch = softmax_shift(row.min(), row.max())
+    adj, branch = softmax_shift(*c_extremes(row))
     _, count = fast_expf(row + adj)
     like = -softmax_best_guess(row)[0]
     return dict(branch=branch, loops=set(int(c) for c in count), denormal=bool(((like > 0) & (like < TINY)).any()),
@@ -246,6 +309,54 @@ def designed_weights(I, H, O, hidden_size, symbol_rows):
         ih[1 + hidden_size + c, 1 + c] = 1.0
         ho[1 + c, :len(row)] = checked(row)
     return ih, ho
+
+
+HUGE = F(2e38)  # twice it overflows: the one product that makes an infinity
+
+
+def designed_nonfinite_weights(I, H, O, hidden_size, symbol_rows):
+    """designed_weights for rows that may hold infinities and NaNs, from FINITE weights: a finite row is written as there.
+    A row that is not finite gets the input weight 2 (its hidden unit is 2) and half of every finite entry (exact: asserted),
+    +-2e38 where an infinity is wanted -- 2 * 2e38 overflows by itself, whatever it is added to or split from -- and for a
+    NaN a spare hidden unit of its own behind the symbols', lit by the same symbol, with -2e38 against +2e38.  Every other
+    stream multiplies those weights by an exact zero."""
+    ih, ho = np.zeros((I, H), np.float32), np.zeros((H, O), np.float32)
+    assert 1 + hidden_size + len(symbol_rows) <= I
+    spare = len(symbol_rows)
+    for c, row in enumerate(symbol_rows):
+        row = np.asarray(row, np.float32)
+        assert len(row) <= O
+        fine = np.isfinite(row)
+        if fine.all():
+            ih[1 + hidden_size + c, 1 + c] = 1.0
+            ho[1 + c, :len(row)] = checked(row)
+            continue
+        half = np.where(fine, row, 0) * F(0.5)
+        assert np.array_equal((half * F(2)).view(np.uint32), np.where(fine, row, 0).astype(np.float32).view(np.uint32))
+        half[np.isposinf(row)] = HUGE
+        half[np.isneginf(row)] = -HUGE
+        half[np.isnan(row)] = HUGE
+        ih[1 + hidden_size + c, 1 + c] = 2.0
+        ho[1 + c, :len(row)] = half
+        if np.isnan(row).any():
+            ih[1 + hidden_size + c, 1 + spare] = 2.0
+            ho[1 + spare, :len(row)] = np.where(np.isnan(row), -HUGE, F(0))
+            spare += 1
+    assert spare <= hidden_size, "a NaN needs a hidden unit of its own: hidden_size >= symbols + 1 per row with one"
+    assert np.isfinite(ih).all() and np.isfinite(ho).all()
+    return ih, ho
+
+
+def designed_forward(ih, ho, hidden_size, c):
+    """the written net's answer to symbol c, float32: -> (hidden row, output row).  No recurrence is written (the hidden
+    rows of ih are zero), so the input is the bias and the symbol alone; every product but the symbol's is an exact zero."""
+    x = np.zeros(ih.shape[0], np.float32)
+    x[0] = x[1 + hidden_size + c] = 1.0
+    with np.errstate(over="ignore", invalid="ignore"):
+        hid = np.maximum((x[:, None] * ih).sum(axis=0, dtype=np.float32), F(0))  # ReLU
+        hid[0] = 1.0  # the bias node
+        out = (hid[:, None] * ho).sum(axis=0, dtype=np.float32)
+    return hid, out
 
 
 def share_out(pairs, S):
