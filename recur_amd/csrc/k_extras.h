@@ -211,7 +211,9 @@ __device__ __forceinline__ void bptt_control_wave(const View &v, int r, int j, i
     if (flags & 64u) { /* RNN_NET_FLAG_BPTT_ADAPTIVE_MIN_ERROR */
       int depth_error = D / 4 - t;
       if (mef < MAX_MIN_ERROR_FACTOR_F && (min_error_gain != min_error_sum || depth_error < 0)) {
-        mef *= (float)(1.0f + depth_error * 1e-3);
+        /* the reference's product is a double's, rounded once (recur-nn.c:409: `1e-3` is a double); rounding the
+         * factor first lands one unit in the last place beside it in a third of the steps */
+        mef = (float)((double)mef * (1.0 + depth_error * 1e-3));
       }
       mef = (mef >= ABS_MIN_ERROR_FACTOR_F) ? mef : ABS_MIN_ERROR_FACTOR_F;
     }
