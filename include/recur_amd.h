@@ -517,6 +517,22 @@ typedef struct RnnAmdStats {
 /* Reads (and optionally clears) the device accumulators; synchronises. */
 void rnn_amd_set_read_stats(RnnAmdSet *set, RnnAmdStats *stats, int clear);
 
+/* FOR TESTS AND TOOLS: what the engine behind the set has put off until a later call needs it, as bits.  The library
+ * settles all of it by itself, whichever call comes next; no caller has to ask.  The query exists so that a test of one
+ * settlement route can tell that the state it means to settle was there.  It launches nothing, copies nothing and
+ * changes nothing.
+ *   RNN_AMD_DEFERRED_IH_PLANES  the last rnn_amd_set_calc_deltas (accumulate 0) left ih_delta as unsummed split-K planes
+ *   RNN_AMD_DEFERRED_HO_PLANES  ... and ho_delta
+ *   RNN_AMD_DEFERRED_CLEAR      an rnn_bptt_clear_deltas has not been carried out yet
+ *   RNN_AMD_DEFERRED_IMAGES     the h_error / i_error images of the last delta call's rows have not been rebuilt yet
+ *   RNN_AMD_DEFERRED_TOP_DONE   the top layer's backprop of exactly this set's rows has been done with their loss */
+#define RNN_AMD_DEFERRED_IH_PLANES 1
+#define RNN_AMD_DEFERRED_HO_PLANES 2
+#define RNN_AMD_DEFERRED_CLEAR 4
+#define RNN_AMD_DEFERRED_IMAGES 8
+#define RNN_AMD_DEFERRED_TOP_DONE 16
+int rnn_amd_set_deferred(const RnnAmdSet *set);
+
 /* ---- multi-GPU: one process per GPU, streams sharded, one all-reduce per generation ----
  * The reference sums the deltas of all streams in one process (recur-nn.c:724-739 over the
  * sharing of recur-nn-init.c:232-241); these calls distribute that sum.  rank 0 obtains an

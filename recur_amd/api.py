@@ -239,6 +239,7 @@ AMD_API = {
     "rnn_amd_set_replica_checksum": (C.c_uint64, [C.c_void_p, C.c_int, C.c_int]),
     "rnn_amd_set_char_step_fused": (None, [C.c_void_p, C.c_int, C.c_uint]),
     "rnn_amd_set_read_stats": (None, [C.c_void_p, C.POINTER(AmdStats), C.c_int]),
+    "rnn_amd_set_deferred": (C.c_int, [C.c_void_p]),
     "rnn_amd_set_external_delta": (None, [C.c_void_p, C.c_void_p]),
     "rnn_amd_set_char_step_deltas": (None, [C.c_void_p, C.c_int]),
     "rnn_amd_set_shard": (None, [C.c_void_p, C.c_int, C.c_int]),
@@ -299,6 +300,8 @@ AMD_API = {
 }
 RNN_AMD_WEIGHTS, RNN_AMD_MOMENTUMS, RNN_AMD_DELTAS, RNN_AMD_STREAM, RNN_AMD_ALL_STREAMS = 1, 2, 4, 8, 16
 RNN_AMD_EVERYTHING = 31
+# rnn_amd_set_deferred's bits (for tests and tools)
+DEFERRED_IH_PLANES, DEFERRED_HO_PLANES, DEFERRED_CLEAR, DEFERRED_IMAGES, DEFERRED_TOP_DONE = 1, 2, 4, 8, 16
 RNN_AMD_EXCHANGE_BLOB_BYTES = 256
 
 def _bind(lib, table, skip=()):

@@ -148,7 +148,8 @@ __global__ __launch_bounds__(1024) void k_bptt_small(View v, int r, int accumula
 #undef LDS_BARRIER
   if (wave == 0) {
     /* the steps that did not run left zeros, which end the scan of bptt_control_wave too */
-    bptt_control_wave(v, r, 0, lane, bptt_control_load(v, r, 0, nullptr), flags, es_sh, 1);
+    /* (leave_tail false: the images are written below, behind the barrier that completes the plane stores) */
+    bptt_control_wave(v, r, 0, lane, bptt_control_load(v, r, 0, nullptr), flags, es_sh, 1, false);
     if (lane == 0) {
       red[16] = v.b.ih_scale[r]; /* lane 0 wrote it */
       red[17] = __int_as_float(v.b.n_exec[r]);

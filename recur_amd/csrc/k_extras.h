@@ -168,8 +168,11 @@ __device__ __forceinline__ ControlIn bptt_control_load(const View &v, int r, int
   ci.live = !active || as_global(active)[j];
   return ci;
 }
+/* leave_tail: the caller's extras planes (ex) of this stream are complete and visible to this wave, and the caller does
+ * not write the error images itself: see the end */
 __device__ __forceinline__ void bptt_control_wave(const View &v, int r, int j, int lane, const ControlIn &ci,
-                                                  unsigned flags, const float *es_src, size_t es_stride) {
+                                                  unsigned flags, const float *es_src, size_t es_stride,
+                                                  bool leave_tail = true) {
   const RamdShape &s = v.sh;
   const int D = s.D;
   if (!ci.live) {
@@ -230,6 +233,17 @@ __device__ __forceinline__ void bptt_control_wave(const View &v, int r, int j, i
    * ih_scale into the rate (recur-nn.c:966-975) */
   const float cf = (flags & RAMD_IH_SCALE_IN_RATE) ? 1.0f : scale;
   for (int k = lane; k < D; k += 64) as_global(v.b.coef)[(size_t)k * s.Scap + r] = (k < n_exec) ? cf : 0.0f;
+  /* h_error's entries from h_size on, left at once.  They are the one part of a stream's error images that the NEXT
+   * run's images may depend on: a run of a single step leaves them as they were (write_error_images), and k_err_writeback
+   * is skipped between two delta calls over the same rows -- the entries of this run would then never have been
+   * written.  After two or more steps they are the input columns of the last i_error h_error held (stale_plane);
+   * k_err_writeback writes the same values again. */
+  if (leave_tail && n_exec > 1) {
+    const int nxp = (s.I - s.hidden_size + 3) & ~3; /* ramd_nxp */
+    const auto *x = as_global(v.b.ex) + ((size_t)stale_plane(n_exec) * s.Scap + r) * nxp;
+    auto *A = as_global(v.b.err_a) + (size_t)r * s.I;
+    for (int i = s.H + lane; i < s.I; i += 64) A[i] = x[i - s.hidden_size];
+  }
 }
 
 

@@ -86,6 +86,18 @@ void rnn_amd_set_drop(RnnAmdSet *set) {
 
 int rnn_amd_set_size(const RnnAmdSet *set) { return set->n; }
 
+/* for tests and tools (include/recur_amd.h): reads the engine's book-keeping, touches nothing */
+int rnn_amd_set_deferred(const RnnAmdSet *set) {
+  const RamdEngine *e = set->eng;
+  int bits = 0;
+  if (e->kept_live && e->kept.slab) bits |= RNN_AMD_DEFERRED_IH_PLANES;
+  if (e->kept_live && e->kept.ho_slab) bits |= RNN_AMD_DEFERRED_HO_PLANES;
+  if (e->deltas_zero_pending) bits |= RNN_AMD_DEFERRED_CLEAR;
+  if (e->err_pending) bits |= RNN_AMD_DEFERRED_IMAGES;
+  if (e->top_done && e->top_done_row0 == set->row0 && e->top_done_n == set->n) bits |= RNN_AMD_DEFERRED_TOP_DONE;
+  return bits;
+}
+
 void rnn_amd_set_shard(RnnAmdSet *set, int global_first, int global_count) {
   if (global_first < 0 || global_first + set->n > global_count) {
     fprintf(stderr, "librecur_amd: rnn_amd_set_shard(%d, %d) for a set of %d streams\n", global_first,
@@ -361,7 +373,11 @@ static void set_calc_deltas(RnnAmdSet *set, int accumulate, RecurErrorRange *ran
      * launcher sees to it (its per-head form reads them from the planes: no k_err_writeback launch) */
     extra_flags |= RAMD_IMAGES_PENDING;
     e->err_pending = 0;
-  } else if (e->err_pending && (d_ranges || e->err_row0 != set->row0 || e->err_nrows != set->n)) {
+  } else if (e->err_pending && (d_ranges || e->err_row0 != set->row0 || e->err_nrows != set->n ||
+                                (active && memchr(active, 0, (size_t)set->n)))) {
+    /* (the same rows, no ranges, every stream: this call's images replace the pending ones -- what they keep of the
+     * last run, h_error from h_size on behind a single step, bptt_control_wave has left already.  A stream the mask
+     * leaves out keeps its images whole: they are rebuilt first) */
     ramd_err_flush(e);
   }
   if (e->top_done && e->top_done_row0 == set->row0 && e->top_done_n == set->n && !d_ranges &&

@@ -112,7 +112,8 @@ CASES = {
                forms=dict(calc=dict(direct=0, dma=1, has_rest=1, extras="dense"), planes=dict(ho_gemm="planes_paired"),
                           summed=dict(ho_gemm="paired_summed"), calc_args=dict(dense_inputs=1),
                           chain=dict(wanted=1, uniform=1, seg0="0,32,1,0,32,0>240,1"), fwd=dict(hidden="fused"))),
-    # dense extras inside the chain launch, k_delta_direct with a 4-way K split, planes summed by k_apply
+    # dense extras inside the chain launch, k_delta_direct with a 4-way K split, its planes left for the update (here every
+    # step's snapshot sums them with k_delta_finalize; tests/settle_cases.py is where k_apply does)
     "h512": _c("dyadic", 16, 512, 16, 128, 5, one_hot=False,
                forms=dict(calc=dict(direct=1, direct_runs=1, dks=4, xc_req="dense"), planes=dict(ho_gemm="planes_paired"),
                           summed=dict(ho_gemm="paired_summed"), calc_args=dict(dense_inputs=1),
