@@ -404,6 +404,9 @@ void rnn_amd_set_put_o_error(RnnAmdSet *set, const float *o_error, int ld);
  *   - Every other head, group, row, stream or text of the same call is untouched, bit for bit; outputs that take part in
  *     no softmax or sigmoid (the columns of rnn_amd_run_sequences outside every group) are copied as they are.
  *   - Every call returns.
+ *   - Parrot's tanh loss (rnn_amd_set_tanh_error and the calls built on it) is the exception to the infinity rule: it
+ *     follows fast_tanhf, which clamps.  An infinite output becomes exactly +-1.0f, its slope 1 - a * a exactly 0 and its
+ *     error exactly 0 for a finite target; a NaN output gives a NaN answer and a NaN error.  Elementwise as well.
  * A NaN error row then spreads through the deltas into the weights, as it would on any path: the contract is about the
  * call that meets the row.  The samplers (rnn_amd_sample_texts, rnn_amd_continue_texts) say below what they do with an
  * output row without a total: the row ends at the attempt cap and the call returns -1. */
@@ -485,6 +488,54 @@ void rnn_amd_set_opinion_grouped_softmax(RnnAmdSet *set, const float *inputs, in
  * (rnn_amd_set_advance) if its trainer has a history, as the synthetic configs[4] driver does. */
 void rnn_amd_set_dense_step_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld,
                                         int n, int learning_style, float momentum);
+/* ---- parrot's trainer (gstparrot.c: train_net 464-477, maybe_learn 487-554) on the device ----
+ * The loss after an rnn_amd_set_opinion: for every stream the first n outputs become their fast_tanhf IN PLACE
+ * (badmaths.h:55-68, tanh_opinion) and o_error[i] = (1 - a * a) * (targets[j * ld + i] - a), operation for operation
+ * (csrc/parrot_rule.h: the square, the slope, the difference and the product are four fp32 roundings, none fused).
+ * Outputs and error columns from n on stay what they were; it works at any output size.  targets: host [n_nets][ld].
+ *
+ * STATISTICS.  Per stream-step the loss adds the sum over the n outputs of (target - a)^2 to `error` and 1 to `count`
+ * of rnn_amd_set_read_stats, so error / (count * n) is the mean squared error and a training loop has a progress figure
+ * without fetching anything per generation.  The order of that sum is the library's own (wave reductions, then the waves
+ * in order): it is held to a float64 restatement at 1e-4 relative, not bit for bit.
+ *
+ * OUTPUTS THAT ARE NOT FINITE follow fast_tanhf, and this DIFFERS from the sigmoid's rule above, where an infinity is
+ * NaN: an infinite output is clamped to +-1.0f, so its slope and its error are exactly 0 for a finite target; a NaN
+ * output gives a NaN answer and a NaN error (and a NaN `error` sum for its stream).  Both are elementwise: no other
+ * output, row or stream is touched, and every call returns.
+ *
+ * THE SUM OVER CHANNELS.  The plugin calls rnn_bptt_calc_deltas(net, 0, NULL) for every channel (gstparrot.c:475), which
+ * zeroes the sums each time: of n channels only the last one's deltas reach the update.  These calls SUM over all the
+ * streams of the set, as every other trainer here and in the reference does.  A set of ONE net is the plugin with one
+ * channel exactly; the overwrite is not emulated. */
+void rnn_amd_set_tanh_error(RnnAmdSet *set, const float *targets, int ld, int n);
+/* rnn_amd_set_opinion (outputs not fetched) + rnn_amd_set_tanh_error as ONE call.  Same results as the two calls; where
+ * the text top launch takes the shape (up to 256 outputs -- parrot's 256 bins --, no bottom layer, no presynaptic noise;
+ * RECUR_AMD_DENSE_TOP=0 switches it off) the hidden layer's activation, the output layer, the loss and the top layer's
+ * backprop share one launch, every output column a thread of its own, and the rnn_amd_set_calc_deltas that follows finds
+ * the top layer's backprop done.  Elsewhere it simply makes the two calls. */
+void rnn_amd_set_opinion_tanh_error(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld,
+                                    int n);
+/* maybe_learn's body for every channel at once, as ONE call: rnn_bptt_clear_deltas, then per stream rnn_bptt_advance
+ * (train_net advances; do NOT call rnn_amd_set_advance as well), the opinion of `inputs`, the loss against `targets`,
+ * rnn_bptt_calc_deltas SUMMED over the streams (see above), and rnn_apply_learning(nets[0], learning_style, momentum).
+ * The same results as rnn_bptt_clear_deltas + rnn_amd_set_advance + rnn_amd_set_opinion_tanh_error +
+ * rnn_amd_set_calc_deltas(set, 1, NULL, NULL) + rnn_apply_learning; knowing the update that follows, the weight-delta GEMM
+ * carries it out in its own epilogue where the rule is the momentum rule.  rnn_condition_net is the caller's. */
+void rnn_amd_set_dense_step_tanh(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld, int n,
+                                 int learning_style, float momentum);
+/* n_steps such generations from ONE block of frames: parrot's target at generation t is its input at generation t + 1.
+ * frames: host [n_steps + 1][n_nets][ld], ld >= max(input_size, n).  The block goes up once, into a buffer of the
+ * engine's that grows on demand and is freed with the engine; generation t is rnn_amd_set_dense_step_tanh's work with
+ * inputs frames[t] and targets frames[t + 1], read where they lie on the device, followed by rnn_condition_net(nets[0])
+ * when `condition` is not 0 (gstparrot.c:544-545).  There is no upload per generation and no synchronisation between the
+ * generations (the block's own upload is waited for where it is larger than the 1 MB mailbox; the conditioning's random
+ * damage, where the net's flags ask for it, draws on the host).  The last frame of a block is the first of the next: a
+ * caller chains blocks.  n_steps < 1, NULL frames, n outside the outputs or a too-small ld abort with a message (which
+ * blocks it takes is stated once, csrc/parrot_rule.h: parrot_block_refusal, and tested there without a device).  (A set with a bottom layer
+ * takes its rows from the host, generation by generation.) */
+void rnn_amd_set_dense_steps_tanh(RnnAmdSet *set, const float *frames, int ld, int n_steps, int n, int learning_style,
+                                  float momentum, int condition);
 /* fill_frame's step after the opinion (gstrnnca.c:813-814): fast_sigmoid in place on the first
  * n outputs of every net of the set (training or forward-only clones); outputs (host, n_nets x
  * o_size, may be NULL) receives the answer rows, which synchronises. */

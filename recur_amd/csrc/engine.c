@@ -370,6 +370,9 @@ static void engine_free_device(RamdEngine *e) {
   e->kept_live = 0;
   e->d_group = NULL;
   e->d_group_bytes = 0;
+  ramd_dev_free(e->d_frames);
+  e->d_frames = NULL;
+  e->d_frames_bytes = 0;
   e->d_mranges = NULL;
   e->d_mclass = NULL;
   free(e->lr_pushed);

@@ -11,6 +11,7 @@ __device__ unsigned long long g_tt_stamps[16];
 #endif
 #include "k_top.h"
 #include "fwd_plan.h"
+#include "parrot_rule.h"
 BND_DECL(g_bnd_top, ramd_bnd_top_stamps)
 #pragma clang fp contract(off)
 
@@ -70,16 +71,30 @@ extern "C" void ramd_top_stamps(unsigned long long *out) {
 #endif
 /* KIND: which loss sits between the output layer and the backprop -- 0: the text model's softmax against the stream's
  * next symbol; 1: rnnca's sigmoid + squared error (k_sigmoid_mse_error's arithmetic, gstrnnca.c:701-714); 2: gstclassify's
- * class groups (k_grouped_softmax_error's, gstclassify.c:2070-2119).  1 and 2 serve rnn_amd_set_opinion_sigmoid_mse /
- * _grouped_softmax: finalize + output layer + loss + top backprop of a dense-input generation in ONE launch instead of
- * four (7.4 + 12.0 + 4.9 + 9.8 us at 2048 / 512, 5.0 + 4.7 + 4.8 + 5.0 us at 512 / 128). */
+ * class groups (k_grouped_softmax_error's, gstclassify.c:2070-2119); 3: parrot's tanh + slope error (k_tanh_mse_error's,
+ * gstparrot.c:464-477, parrot_rule.h).  1 and 2 serve rnn_amd_set_opinion_sigmoid_mse / _grouped_softmax, 3 serves
+ * rnn_amd_set_opinion_tanh_error: finalize + output layer + loss + top backprop of a dense-input generation in ONE launch
+ * instead of four (7.4 + 12.0 + 4.9 + 9.8 us at 2048 / 512, 5.0 + 4.7 + 4.8 + 5.0 us at 512 / 128).  1 and 2 are one
+ * wave's work (o_size <= 64); 3 gives every column a thread of its own (o_size <= 256: parrot's 256 bins, waves 0 .. 3). */
 struct TopLoss {
-  const float *targets; /* 1: [nrows][ld] */
+  const float *targets; /* 1, 3: [nrows][ld] */
   int ld, n;
   int ngroups;          /* 2 */
   const int *goff, *gsize, *gt;
   const float *weight;
 };
+/* The progress figure of parrot's loss (parrot_rule.h: parrot_loss), per stream-step: a row's terms are added up by wave
+ * reductions over threads 0 .. 255 (thread x brings columns x, x + 256, ...), then the four waves' sums in order 0 .. 3.
+ * The order is the library's own: the figure is held to a float64 restatement, not bit for bit. */
+__device__ __forceinline__ float tanh_loss_wave_sum(float term) {
+  for (int off = 32; off > 0; off >>= 1) term += __shfl_down(term, off, 64);
+  return term;
+}
+__device__ __forceinline__ void tanh_loss_add_stats(const View &v, int r, const float *wsum) {
+  const float sum = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  v.b.stat_err[r] += (double)sum;
+  v.b.stat_count[r] += 1;
+}
 template <int KIND>
 __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, int fwd_ks, TopLoss tl) {
   extern __shared__ float tsh[];
@@ -111,7 +126,12 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
   constexpr int NB = 14; /* float4 in flight per lane and batch: 66 rows of a wave at 5 rows per instruction */
   int target = 0;
   float pad_oe = 0.0f, mse_target = 0.0f;
-  if (seg == 0) {
+  if constexpr (KIND == 3) { /* column x is thread x's: its target and its o_error pad */
+    if ((int)threadIdx.x < s.O) {
+      pad_oe = v.b.o_error[(size_t)r * s.O + threadIdx.x];
+      mse_target = (int)threadIdx.x < tl.n ? tl.targets[(size_t)blockIdx.x * tl.ld + threadIdx.x] : 0.0f;
+    }
+  } else if (seg == 0) {
     if constexpr (KIND == 0) target = v.b.target[r];
     const int pi = lane < s.O ? lane : 0; /* (o_size > 64: the later columns are read where they are used) */
     pad_oe = v.b.o_error[(size_t)r * s.O + pi];
@@ -252,6 +272,26 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
     }
     if (threadIdx.x == 0) trained_sh = 1;
     __syncthreads();
+  } else if constexpr (KIND == 3) { // k_tanh_mse_error: tanh in place on the first n outputs, (1 - a a) (target - a)
+    if (seg < 4) { /* (o_size <= 256: text_top_takes) */
+      const int x = threadIdx.x;
+      float term = 0.0f;
+      if (x < s.O) {
+        float oe = pad_oe; /* the rest of the error row stays what it was */
+        if (x < tl.n) {
+          const float a = dream_tanh(sout[x]);
+          v.b.out[(size_t)r * s.O + x] = a;
+          oe = parrot_error(a, mse_target);
+          v.b.o_error[(size_t)r * s.O + x] = oe;
+          term = parrot_loss(a, mse_target);
+        }
+        serr[x] = oe;
+      }
+      term = tanh_loss_wave_sum(term);
+      if (lane == 0) tstat[seg] = term;
+    }
+    __syncthreads();
+    if (threadIdx.x == 64) tanh_loss_add_stats(v, r, tstat); /* (beside the backprop, as the text loss's) */
   } else { // k_grouped_softmax_error, operation for operation, the outputs from LDS
     if (seg == 0) {
       float *err = v.b.o_error + (size_t)r * s.O;
@@ -690,6 +730,31 @@ __global__ void k_sigmoid_mse_error(View v, int row0, int nrows, int n, const fl
   v.b.o_error[(size_t)r * v.sh.O + i] = slope * (targets[(size_t)j * ld + i] - a);
 }
 
+// parrot's loss (gstparrot.c:464-477, train_net; parrot_rule.h): fast_tanhf IN PLACE on the first n outputs (tanh_opinion),
+// then o_error[i] = (1 - a a) (target - a).  One workgroup of four waves per stream, thread x taking columns x, x + 256, ...
+// at any o_size; outputs and error columns from n on stay what they were.  The row's sum of (target - a)^2 goes to the
+// set's statistics (tanh_loss_add_stats).
+__global__ __launch_bounds__(256) void k_tanh_mse_error(View v, int row0, int nrows, int n, const float *targets, int ld) {
+  __shared__ float wsum[4];
+  const int j = blockIdx.x;
+  if (j >= nrows) return;
+  const int r = row0 + j;
+  float *out = v.b.out + (size_t)r * v.sh.O;
+  float *err = v.b.o_error + (size_t)r * v.sh.O;
+  float term = 0.0f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float t = targets[(size_t)j * ld + i];
+    const float a = dream_tanh(out[i]);
+    out[i] = a;
+    err[i] = parrot_error(a, t);
+    term += parrot_loss(a, t);
+  }
+  term = tanh_loss_wave_sum(term);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = term;
+  __syncthreads();
+  if (threadIdx.x == 0) tanh_loss_add_stats(v, r, wsum);
+}
+
 // fill_frame's fast_sigmoid_array(answer, answer, 3) (gstrnnca.c:813-814) for state rows
 __global__ void k_sigmoid_outputs(View v, int r0, int nrows, int n) {
   int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -748,6 +813,24 @@ extern "C" int ramd_launch_dense_top(ramd_stream_t st_, const RamdShape *sh, con
   return 1;
 }
 
+/* the same launch with parrot's loss (k_text_top<3>): every column of up to 256 has a thread, so no o_size <= 64 cap; the
+ * switch is the dense top's own */
+extern "C" int ramd_dense_top_tanh_ok(const RamdShape *sh) {
+  return ramd_text_top_ok(sh) && env_int("RECUR_AMD_DENSE_TOP", 1);
+}
+
+extern "C" int ramd_launch_dense_top_tanh(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
+                                          RamdHandover left, const float *targets, int ld, int n) {
+  if (!ramd_dense_top_tanh_ok(sh)) return 0;
+  const int fwd_ks = handover_fwd_ks(left);
+  hipStream_t st = (hipStream_t)st_;
+  View v = make_view(sh, b);
+  size_t shm = (size_t)(sh->H + OUT_SEGS * 64 * 4 + (OUT_SEGS + 3) * sh->O) * sizeof(float);
+  TopLoss tl = {targets, ld, n, 0, NULL, NULL, NULL, NULL};
+  RAMD_LAUNCH(k_text_top<3>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
+  return 1;
+}
+
 extern "C" void ramd_launch_softmax_error(ramd_stream_t st_, const RamdShape *sh,
                                           const RamdBuffers *b, int row0, int nrows) {
   hipStream_t st = (hipStream_t)st_;
@@ -780,6 +863,13 @@ extern "C" void ramd_launch_sigmoid_mse_error(ramd_stream_t st_, const RamdShape
   View v = make_view(sh, b);
   RAMD_LAUNCH(k_sigmoid_mse_error, dim3((nrows * n + 255) / 256), dim3(256), 0, st, v, row0, nrows, n,
               targets, ld);
+}
+
+extern "C" void ramd_launch_tanh_mse_error(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
+                                           int n, const float *targets, int ld) {
+  hipStream_t st = (hipStream_t)st_;
+  View v = make_view(sh, b);
+  RAMD_LAUNCH(k_tanh_mse_error, dim3(nrows), dim3(256), 0, st, v, row0, nrows, n, targets, ld);
 }
 
 extern "C" void ramd_launch_sigmoid_outputs(ramd_stream_t st_, const RamdShape *sh,

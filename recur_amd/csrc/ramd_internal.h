@@ -204,6 +204,11 @@ void ramd_launch_text_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffe
 int ramd_launch_dense_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, RamdHandover left,
                           const float *targets, int ld, int n, int ngroups, const int *goff, const int *gsize, const int *gt,
                           const float *weight);
+/* the same launch with parrot's loss (k_text_top<3>: tanh in place on the first n outputs, (1 - a a) (target - a), the
+ * row's squared error into the statistics); a thread per column, so any o_size the text top takes (<= 256) */
+int ramd_dense_top_tanh_ok(const RamdShape *sh); /* (ramd_text_top_ok, RECUR_AMD_DENSE_TOP) */
+int ramd_launch_dense_top_tanh(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
+                               RamdHandover left, const float *targets, int ld, int n);
 /* o_error = onehot(target) - softmax(out) and statistics
  * (charmodel-predict.c:18-27, 299-304) */
 void ramd_launch_softmax_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
@@ -394,6 +399,10 @@ void ramd_launch_texts_continue(ramd_stream_t st, const RamdShape *sh, const Ram
  * a) into o_error; targets is a device array [nrows][ld] */
 void ramd_launch_sigmoid_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
                                    int row0, int nrows, int n, const float *targets, int ld);
+/* parrot's loss (gstparrot.c:464-477, parrot_rule.h): fast_tanhf in place on the first n outputs, (1 - a a) (target - a)
+ * into o_error, the row's sum of (target - a)^2 and one count into the statistics; targets is a device array [nrows][ld] */
+void ramd_launch_tanh_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, int n,
+                                const float *targets, int ld);
 /* fast_sigmoid_array in place on the first n outputs of state rows r0 .. r0 + nrows */
 void ramd_launch_sigmoid_outputs(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int r0,
                                  int nrows, int n);

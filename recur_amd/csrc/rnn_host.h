@@ -67,6 +67,8 @@ typedef struct RamdEngine {
   void *d_group;        /* staging of the class-group loss: offsets, sizes, targets, weights */
   size_t d_group_bytes;
   float *d_dense;       /* staging for dense inputs, [Scap+Fcap][input_size] */
+  float *d_frames;      /* rnn_amd_set_dense_steps_tanh's block of frames, [n_steps + 1][n_nets][ld]: grown on demand */
+  size_t d_frames_bytes;
   float *delta_own;     /* library-owned ih_delta||ho_delta                */
   int delta_external;
   /* The delta sums of the last set call, kept as the un-summed planes the GEMM left (in a workspace of their own)

@@ -7,6 +7,7 @@
  */
 #define RAMD_HIP_HOST 1
 #include "rnn_host.h"
+#include "parrot_rule.h"
 
 RnnAmdSet *rnn_amd_set_open(RecurNN **nets, int n_nets) {
   if (!nets || n_nets < 1) {
@@ -682,6 +683,85 @@ void rnn_amd_set_opinion_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld
   ramd_top_done_set(e, set->row0, set->n, 0);
 }
 
+/* Parrot's loss (train_net, gstparrot.c:464-477; parrot_rule.h).  The rows of inputs and targets are the caller's host
+ * rows, or (on_dev) lie on the device already, ld floats apart: the many-step call's block of frames */
+/* what every public call checks once, up front (the static forms below take checked arguments): a training set, targets,
+ * 1 <= n <= output_size and rows of at least n floats */
+static void tanh_check(const RnnAmdSet *set, const char *what, const float *targets, int ld, int n) {
+  ramd_set_need_training(set, what);
+  if (!targets || n < 1 || n > set->eng->sh.output_size || ld < n) {
+    fprintf(stderr, "librecur_amd: %s: targets %p over %d of %d outputs (ld %d)\n", what, (const void *)targets, n,
+            set->eng->sh.output_size, ld);
+    abort();
+  }
+}
+
+static void set_tanh_error(RnnAmdSet *set, const float *targets, int ld, int n, int on_dev) {
+  RamdEngine *e = set->eng;
+  ramd_top_done_clear(e);
+  set_streams_to_dev(set);
+  if (!on_dev) {
+    group_room(e, (size_t)set->n * n * sizeof(float));
+    ramd_upload_rows(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n);
+    targets = (const float *)e->d_group;
+    ld = n;
+  }
+  ramd_launch_tanh_mse_error(ramd_stream, &e->sh, &e->b, set->row0, set->n, n, targets, ld);
+  set_streams_dev_wrote(set);
+}
+
+void rnn_amd_set_tanh_error(RnnAmdSet *set, const float *targets, int ld, int n) {
+  tanh_check(set, "rnn_amd_set_tanh_error", targets, ld, n);
+  set_tanh_error(set, targets, ld, n, 0);
+}
+
+static int dense_top_tanh_ok(RnnAmdSet *set, const float *inputs) {
+  RamdEngine *e = set->eng;
+  return inputs && !set->fwd_only && !e->sh.bI && ramd_dense_top_tanh_ok(&e->sh) &&
+         set->nets[0]->presynaptic_noise == 0.0f && set->nets[0]->bptt;
+}
+
+/* (advance: rnn_bptt_advance first, as train_net does) */
+static void set_opinion_tanh_error(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld, int n,
+                                   int on_dev, int advance) {
+  RamdEngine *e = set->eng;
+  if (!dense_top_tanh_ok(set, inputs)) {
+    if (on_dev) { /* (never with a bottom layer: rnn_amd_set_dense_steps_tanh keeps such a set's frames on the host) */
+      set_forward(set, RAMD_IN_DENSE, inputs, ld_inputs, 0, NULL, advance, RAMD_FWD_WHOLE);
+    } else {
+      if (advance) {
+        rnn_amd_set_advance(set);
+      }
+      rnn_amd_set_opinion(set, inputs, ld_inputs, NULL);
+    }
+    set_tanh_error(set, targets, ld, n, on_dev);
+    return;
+  }
+  if (!on_dev) {
+    group_room(e, (size_t)set->n * n * sizeof(float));
+    /* inputs and targets leave together with the ring indices (set_forward's flush) */
+    ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), e->sh.input_size * sizeof(float), set->n, 0);
+    ramd_upload_rows_q(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n, 0);
+    inputs = e->d_dense;
+    ld_inputs = e->sh.input_size;
+    targets = (const float *)e->d_group;
+    ld = n;
+  }
+  const RamdHandover left = set_forward(set, RAMD_IN_DENSE, inputs, ld_inputs, 0, NULL, advance, RAMD_FWD_FOR_DENSE_TOP);
+  if (!ramd_launch_dense_top_tanh(ramd_stream, &e->sh, &e->b, set->row0, set->n, left, targets, ld, n)) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_tanh_error: the top launch declined a shape it had accepted\n");
+    abort();
+  }
+  set_streams_dev_wrote(set);
+  ramd_top_done_set(e, set->row0, set->n, 0);
+}
+
+void rnn_amd_set_opinion_tanh_error(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld,
+                                    int n) {
+  tanh_check(set, "rnn_amd_set_opinion_tanh_error", targets, ld, n);
+  set_opinion_tanh_error(set, inputs, ld_inputs, targets, ld, n, 0, 0);
+}
+
 void rnn_amd_set_opinion_grouped_softmax(RnnAmdSet *set, const float *inputs, int ld_inputs, int n_groups,
                                          const int *group_offset, const int *group_size, const int *targets,
                                          const float *error_weight, u8 *trained) {
@@ -779,21 +859,28 @@ static int one_rank_exchange_forced(void) {
  * generation with rnnca's loss (rnn_amd_set_dense_step_sigmoid_mse) */
 typedef struct {
   int i;                /* text position, or -1: dense, or -2: the multi-head step */
-  const float *inputs;  /* dense: host [n][ld_inputs] */
+  const float *inputs;  /* dense: [n][ld_inputs], the caller's host rows (with on_dev: device rows) */
   int ld_inputs;
-  const float *targets; /* host [n][ld], the first n_targets outputs */
+  const float *targets; /* [n][ld], host rows or (on_dev) device rows: the first n_targets outputs */
   int ld, n_targets;
+  int loss;             /* dense: STEP_LOSS_SIGMOID (rnnca's) or STEP_LOSS_TANH (parrot's) */
+  int advance;          /* dense, parrot's: rnn_bptt_advance in front, as train_net has it */
+  int on_dev;           /* dense, parrot's: inputs and targets are device rows (the many-step call's frames) */
   /* the multi-head step (rnn_amd_set_multi_step_deltas's arguments) */
   const int *hot, *next, *target_class;
   int alphabet_len;
   float leakage;
 } StepSpec;
+enum { STEP_LOSS_SIGMOID = 0, STEP_LOSS_TANH = 1 };
 
 static void step_deltas(RnnAmdSet *set, const StepSpec *sp, RamdPendingDelta *defer) {
   if (sp->i >= 0) {
     char_step_deltas(set, sp->i, defer);
   } else if (sp->i == -2) {
     multi_step_deltas(set, sp->hot, sp->next, sp->target_class, sp->alphabet_len, sp->leakage, 0, defer);
+  } else if (sp->loss == STEP_LOSS_TANH) {
+    set_opinion_tanh_error(set, sp->inputs, sp->ld_inputs, sp->targets, sp->ld, sp->n_targets, sp->on_dev, sp->advance);
+    set_calc_deltas(set, 0, NULL, NULL, 0, NULL, 0, defer);
   } else {
     rnn_amd_set_opinion_sigmoid_mse(set, sp->inputs, sp->ld_inputs, sp->targets, sp->ld, sp->n_targets);
     set_calc_deltas(set, 0, NULL, NULL, 0, NULL, 0, defer);
@@ -857,12 +944,13 @@ static void set_step(RnnAmdSet *set, const StepSpec *sp, int learning_style, flo
  * or the momentum rule: no optimiser launch (17 us of configs[3]'s 340) */
 void rnn_amd_set_multi_step(RnnAmdSet *set, const int *hot, const int *next, const int *target_class, int alphabet_len,
                             float leakage, int learning_style, float momentum) {
-  StepSpec sp = {-2, NULL, 0, NULL, 0, 0, hot, next, target_class, alphabet_len, leakage};
+  StepSpec sp = {.i = -2, .hot = hot, .next = next, .target_class = target_class, .alphabet_len = alphabet_len,
+                 .leakage = leakage};
   set_step(set, &sp, learning_style, momentum);
 }
 
 void rnn_amd_set_char_step(RnnAmdSet *set, int i, int learning_style, float momentum) {
-  StepSpec sp = {i, NULL, 0, NULL, 0, 0, NULL, NULL, NULL, 0, 0.0f};
+  StepSpec sp = {.i = i};
   set_step(set, &sp, learning_style, momentum);
 }
 
@@ -874,8 +962,67 @@ void rnn_amd_set_dense_step_sigmoid_mse(RnnAmdSet *set, const float *inputs, int
     abort();
   }
   rnn_bptt_clear_deltas(set->nets[0]); /* (lazy: the delta call below simply does not accumulate) */
-  StepSpec sp = {-1, inputs, ld_inputs, targets, ld, n, NULL, NULL, NULL, 0, 0.0f};
+  StepSpec sp = {.i = -1, .inputs = inputs, .ld_inputs = ld_inputs, .targets = targets, .ld = ld, .n_targets = n,
+                 .loss = STEP_LOSS_SIGMOID};
   set_step(set, &sp, learning_style, momentum);
+}
+
+/* parrot's maybe_learn for every channel at once (gstparrot.c:464-477, 487-554): see recur_amd.h */
+static void dense_step_tanh(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld, int n,
+                            int on_dev, int learning_style, float momentum) {
+  rnn_bptt_clear_deltas(set->nets[0]); /* (lazy: the delta call simply does not accumulate) */
+  StepSpec sp = {.i = -1, .inputs = inputs, .ld_inputs = ld_inputs, .targets = targets, .ld = ld, .n_targets = n,
+                 .loss = STEP_LOSS_TANH, .advance = 1, .on_dev = on_dev};
+  set_step(set, &sp, learning_style, momentum);
+}
+
+void rnn_amd_set_dense_step_tanh(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld, int n,
+                                 int learning_style, float momentum) {
+  tanh_check(set, "rnn_amd_set_dense_step_tanh", targets, ld, n);
+  if (!inputs || ld_inputs < set->eng->sh.input_size) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_dense_step_tanh needs inputs (ld %d for %d)\n", ld_inputs,
+            set->eng->sh.input_size);
+    abort();
+  }
+  dense_step_tanh(set, inputs, ld_inputs, targets, ld, n, 0, learning_style, momentum);
+}
+
+/* n_steps of them from one block of frames, frame t + 1 being generation t's target and generation t + 1's input: the
+ * block goes up once, the generations read their rows where they lie */
+void rnn_amd_set_dense_steps_tanh(RnnAmdSet *set, const float *frames, int ld, int n_steps, int n, int learning_style,
+                                  float momentum, int condition) {
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_dense_steps_tanh");
+  const int refusal = parrot_block_refusal(frames != NULL, n_steps, ld, e->sh.input_size, n, e->sh.output_size);
+  if (refusal) { /* (the rule is parrot_rule.h's, where it is asked without a device) */
+    fprintf(stderr, "librecur_amd: rnn_amd_set_dense_steps_tanh: %s (%d steps from frames %p of ld %d; %d inputs, %d of %d outputs)\n",
+            parrot_block_refusal_text(refusal), n_steps, (const void *)frames, ld, e->sh.input_size, n, e->sh.output_size);
+    abort();
+  }
+  const size_t frame = (size_t)set->n * ld;
+  /* (a bottom layer keeps a host copy of the last stream's inputs per generation, rnn_amd_set_opinion: such a set takes
+   * its rows from the host, generation by generation) */
+  const int on_dev = !e->sh.bI;
+  const float *base = frames;
+  if (on_dev) {
+    const size_t bytes = (size_t)(n_steps + 1) * frame * sizeof(float);
+    ramd_engine_ensure_device(e);
+    if (bytes > e->d_frames_bytes) {
+      ramd_dsync(); /* (an earlier block's generations may still be reading the old one) */
+      ramd_dev_free(e->d_frames);
+      e->d_frames = ramd_dev_alloc(bytes);
+      e->d_frames_bytes = bytes;
+    }
+    ramd_upload(e->d_frames, frames, bytes);
+    base = e->d_frames;
+  }
+  for (int t = 0; t < n_steps; t++) {
+    dense_step_tanh(set, base + (size_t)t * frame, ld, base + (size_t)(t + 1) * frame, ld, n, on_dev, learning_style,
+                    momentum);
+    if (condition) {
+      rnn_condition_net(set->nets[0]); /* gstparrot.c:544-545: behind the update */
+    }
+  }
 }
 
 /* The single-net text step of rnn_char_epoch (charmodel-predict.c:312-321) without a host round trip per

@@ -15,7 +15,9 @@ in the same form; ``classify_texts`` runs a list of encoded texts against one cl
 symbols' classes; ``run_automaton`` plays rnnca's automaton from a seed frame on an ``AutomatonGeometry`` in one call
 (rnn_amd_run_automaton): the frames as uint8 [n][3][height][width] and the cells' states, and ``parse_offsets`` expands an
 offset pattern (rnn_amd_automaton_parse_offsets); ``dream_sequences`` runs parrot's player, many closed-loop sequences fed
-their own answers, in one call (rnn_amd_dream_sequences).  ``synthetic_text_np`` is the seeded symbol stream of
+their own answers, in one call (rnn_amd_dream_sequences); ``train_frames`` runs parrot's trainer over a block of frames,
+every frame the target of one generation and the input of the next, in one call (rnn_amd_set_dense_steps_tanh).
+``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
 """
@@ -398,6 +400,21 @@ def dream_sequences(lib, net, first, n_frames, noise=1.0, seeds=None, rng_in=Non
     assert np.all(np.isnan(frames[count:])) and np.all(np.isnan(nxt[n * isz:])), "floats behind the last frame or row"
     return frames[:count].reshape(n_frames, n, osz).copy(), nxt[:n * isz].reshape(n, isz).copy(), \
         None if hout is None else hout[:n], rng[:n]
+
+
+def train_frames(lib, set_or_handle, frames, n, learning_style=rc.WEIGHTED, momentum=0.95, condition=False):
+    """rnn_amd_set_dense_steps_tanh: parrot's trainer over a block of frames, float32 [T + 1][n_nets][ld] with
+    ld >= max(input_size, n): T generations in one call, generation t fed frames[t] and scored against the first n values
+    of frames[t + 1] (tanh answer, slope error, the deltas summed over the nets, the update; rnn_condition_net behind
+    each with condition).  set_or_handle: an AmdBatchedSet or an RnnAmdSet handle.  The last frame of a block is the first
+    of the next.  Returns T."""
+    handle = getattr(set_or_handle, "handle", set_or_handle)
+    fr = np.ascontiguousarray(frames, dtype=np.float32)
+    assert fr.ndim == 3 and fr.shape[0] >= 2, "frames are [T + 1][n_nets][ld], T >= 1"
+    assert fr.shape[1] == lib.rnn_amd_set_size(handle), "one row per net of the set in every frame"
+    lib.rnn_amd_set_dense_steps_tanh(handle, rc.fptr(fr), fr.shape[2], fr.shape[0] - 1, n, learning_style, momentum,
+                                     int(bool(condition)))
+    return fr.shape[0] - 1
 
 
 class ApiSet:
