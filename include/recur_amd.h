@@ -983,6 +983,46 @@ int rnn_amd_automaton_parse_offsets(const char *pattern, int *offsets_y, int *le
 int rnn_amd_run_automaton(RecurNN *net, const RnnAmdAutomaton *ca, const u8 *seed /* [3][height * width] */, int n_frames,
                           const float *h_in, float *h_out /* [height * width][h_size] */, int segment_frames,
                           u8 *frames /* [n_frames][3][height * width] */);
+/* RNNCA'S TRAINER on the device, many generations in one call (gstrnnca.c: fill_net_inputs 669-691, train_net 693-716,
+ * maybe_learn 718-750).  `set` is a training set of n_nets trainers, clones of one net with bptt and no bottom layer; `ca`
+ * the grid and what a cell sees of it, as above; `frames` a film of n_steps + 1 frames of bytes; xy the trainers' cells as
+ * (x, y) pairs, one list for the block (xy_per_step == 0) or one per generation.  Generation t, for t = 0 .. n_steps - 1:
+ *     rnn_bptt_clear_deltas
+ *     for every trainer j at (x, y) = xy[t or 0][j]:
+ *         rnn_bptt_advance when `advance` is not 0 (the plugin never advances its trainers' rings: advance = 0 is the
+ *             plugin; advance = 1 is rnn_amd_set_advance in front of rnn_amd_set_dense_step_sigmoid_mse)
+ *         inputs = fill_net_inputs from frames[t] at (x, y), by rnn_amd_run_automaton's rule bit for bit, with ca->edges as
+ *             given (the plugin always trains clamped, gstrnnca.c:698: pass edges = 1 for the plugin)
+ *         answer = rnn_opinion(trainer, inputs, net->presynaptic_noise); fast_sigmoid_array(answer, answer, 3)
+ *         o_error[k] = a (1 - a) (target[k] - a), target[k] = frames[t + 1][k][y * width + x] * (1.0f / 255.0f), k = 0, 1, 2
+ *         rnn_bptt_calc_deltas, summed over the trainers
+ *     rnn_apply_learning(nets[0], learning_style, m) with m = momentum when momentum_soft_start == 0, otherwise
+ *         rnn_calculate_momentum_soft_start(nets[0]->generation, momentum, momentum_soft_start), read in front of each update
+ *     rnn_condition_net(nets[0]) when `condition` is not 0 (gstrnnca.c:739)
+ * that is: the results of rnn_amd_set_dense_step_sigmoid_mse on rows a host gathered by the same rule
+ * (csrc/automaton_train_rule.h), bit for bit, plus STATISTICS: per trainer-generation the sum over the three outputs of
+ * (target - a)^2 is added to `error` and 1 to `count` of rnn_amd_set_read_stats, so error / (3 * count) is the mean
+ * squared error.  The order of that sum is the library's own: held to a float64 restatement at 1e-4 relative, as parrot's.
+ * Only this call adds them: rnn_amd_set_sigmoid_mse_error, rnn_amd_set_opinion_sigmoid_mse and
+ * rnn_amd_set_dense_step_sigmoid_mse leave the statistics alone.  OUTPUTS THAT ARE NOT FINITE follow the sigmoid loss's
+ * rule ("OUTPUTS THAT ARE NOT FINITE" above), elementwise, and every call returns.
+ * The film, the positions and the offset lists go up once per block, into a buffer of the engine's that grows on demand
+ * and is freed with the engine; ONE launch gathers every generation's input and target rows from the film's bytes; the
+ * generations read them where they lie.  There is no upload and no synchronisation per generation (the block's own upload
+ * is waited for where it does not fit the mailbox; the conditioning's random damage, where the net's flags ask for it,
+ * draws on the host).  The last frame of a block is the first of the next: a caller chains blocks.  The positions are the
+ * caller's -- the plugin moves one trainer every 8 generations (gstrnnca.c:743-748), which xy_per_step expresses --, and
+ * the call draws from no generator beyond what the generations themselves draw.  What is not emulated: the plugin's
+ * choice of positions and its stasis check, which stay with the caller.
+ * It aborts with a message (which blocks it takes is stated once, csrc/automaton_train_rule.h: automaton_block_refusal,
+ * tested there without a device) on: a NULL set, ca, frames or xy; n_steps < 1; everything rnn_amd_run_automaton refuses
+ * about the grid, the lists, len_pos, the net's inputs and outputs and a wrapped offset; a set with a bottom layer; any
+ * (x, y) outside the grid -- every entry of xy is checked on the host before anything is launched. */
+void rnn_amd_set_automaton_steps(RnnAmdSet *set, const RnnAmdAutomaton *ca,
+                                 const u8 *frames /* [n_steps + 1][3][height * width] */,
+                                 const int *xy /* [xy_per_step ? n_steps : 1][n_nets][2]: (x, y) */, int xy_per_step,
+                                 int n_steps, int advance, int learning_style, float momentum, float momentum_soft_start,
+                                 int condition);
 /* PARROT'S PLAYER on the device, many closed-loop sequences in one run: the batched form of fill_audio_chunk's loop over
  * the channels (gstparrot.c:556-583), in which every channel's dream net is fed its own last answer.  Sequence k is a
  * forward-only clone c_k of `net` with a generator g_k and an input row x_k = first[k] (net->input_size floats, row stride

@@ -373,6 +373,9 @@ static void engine_free_device(RamdEngine *e) {
   ramd_dev_free(e->d_frames);
   e->d_frames = NULL;
   e->d_frames_bytes = 0;
+  ramd_dev_free(e->d_automaton);
+  e->d_automaton = NULL;
+  e->d_automaton_bytes = 0;
   e->d_mranges = NULL;
   e->d_mclass = NULL;
   free(e->lr_pushed);

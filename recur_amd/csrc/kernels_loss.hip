@@ -82,6 +82,7 @@ struct TopLoss {
   int ngroups;          /* 2 */
   const int *goff, *gsize, *gt;
   const float *weight;
+  int stats;            /* 1: the row's squared error and a count into the statistics (rnn_amd_set_automaton_steps alone) */
 };
 /* The progress figure of parrot's loss (parrot_rule.h: parrot_loss), per stream-step: a row's terms are added up by wave
  * reductions over threads 0 .. 255 (thread x brings columns x, x + 256, ...), then the four waves' sums in order 0 .. 3.
@@ -92,6 +93,13 @@ __device__ __forceinline__ float tanh_loss_wave_sum(float term) {
 }
 __device__ __forceinline__ void tanh_loss_add_stats(const View &v, int r, const float *wsum) {
   const float sum = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
+  v.b.stat_err[r] += (double)sum;
+  v.b.stat_count[r] += 1;
+}
+/* The progress figure of rnnca's loss for rnn_amd_set_automaton_steps, per trainer-generation: the sum over the scored
+ * outputs of (target - a)^2 -- the difference is the one the error is made of, its square one more rounding -- and one count.
+ * The order of the sum is the library's own (wave reductions, then the waves in order): held to a float64 restatement. */
+__device__ __forceinline__ void sigmoid_loss_add_stats(const View &v, int r, float sum) {
   v.b.stat_err[r] += (double)sum;
   v.b.stat_count[r] += 1;
 }
@@ -259,19 +267,29 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
     __syncthreads();
     if (threadIdx.x == 64) top_add_stats(v, r, tstat); /* (its loads return before the wave's backprop loads, which are issued behind them) */
   } else if constexpr (KIND == 1) { // k_sigmoid_mse_error: sigmoid in place on the first n outputs, slope * (target - answer)
-    if (seg == 0 && lane < s.O) { /* (o_size <= 64: launcher) */
-      float oe = pad_oe; /* the rest of the error row stays what it was */
-      if (lane < tl.n) {
-        const float a = 1.0f / (1.0f + fast_expf_dev(-sout[lane] * 1.0f));
-        v.b.out[(size_t)r * s.O + lane] = a;
-        const float slope = a * (1.0f - a);
-        oe = slope * (mse_target - a);
-        v.b.o_error[(size_t)r * s.O + lane] = oe;
+    if (seg == 0) { /* (o_size <= 64: launcher) */
+      float term = 0.0f;
+      if (lane < s.O) {
+        float oe = pad_oe; /* the rest of the error row stays what it was */
+        if (lane < tl.n) {
+          const float a = 1.0f / (1.0f + fast_expf_dev(-sout[lane] * 1.0f));
+          v.b.out[(size_t)r * s.O + lane] = a;
+          const float slope = a * (1.0f - a);
+          const float diff = mse_target - a;
+          oe = slope * diff;
+          v.b.o_error[(size_t)r * s.O + lane] = oe;
+          term = diff * diff;
+        }
+        serr[lane] = oe;
       }
-      serr[lane] = oe;
+      if (tl.stats) { /* (uniform over the launch) the one wave's sum, as sigmoid_loss_add_stats says */
+        term = tanh_loss_wave_sum(term);
+        if (lane == 0) tstat[0] = term;
+      }
     }
     if (threadIdx.x == 0) trained_sh = 1;
     __syncthreads();
+    if (tl.stats && threadIdx.x == 64) sigmoid_loss_add_stats(v, r, tstat[0]); /* (beside the backprop, as the text loss's) */
   } else if constexpr (KIND == 3) { // k_tanh_mse_error: tanh in place on the first n outputs, (1 - a a) (target - a)
     if (seg < 4) { /* (o_size <= 256: text_top_takes) */
       const int x = threadIdx.x;
@@ -755,6 +773,32 @@ __global__ __launch_bounds__(256) void k_tanh_mse_error(View v, int row0, int nr
   if (threadIdx.x == 0) tanh_loss_add_stats(v, r, wsum);
 }
 
+// k_sigmoid_mse_error with the progress figure, for rnn_amd_set_automaton_steps where the one-launch top does not take the
+// shape: the same arithmetic per output, so the same bits in answers and errors, by one workgroup of four waves per stream
+// (thread x takes columns x, x + 256, ...), which also adds the row's sum of (target - a)^2 and a count to the statistics.
+__global__ __launch_bounds__(256) void k_sigmoid_mse_error_stats(View v, int row0, int nrows, int n, const float *targets,
+                                                                 int ld) {
+  __shared__ float wsum[4];
+  const int j = blockIdx.x;
+  if (j >= nrows) return;
+  const int r = row0 + j;
+  float *out = v.b.out + (size_t)r * v.sh.O;
+  float *err = v.b.o_error + (size_t)r * v.sh.O;
+  float term = 0.0f;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const float a = 1.0f / (1.0f + fast_expf_dev(-out[i] * 1.0f));
+    out[i] = a;
+    const float slope = a * (1.0f - a);
+    const float diff = targets[(size_t)j * ld + i] - a;
+    err[i] = slope * diff;
+    term += diff * diff;
+  }
+  term = tanh_loss_wave_sum(term);
+  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = term;
+  __syncthreads();
+  if (threadIdx.x == 0) sigmoid_loss_add_stats(v, r, ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+}
+
 // fill_frame's fast_sigmoid_array(answer, answer, 3) (gstrnnca.c:813-814) for state rows
 __global__ void k_sigmoid_outputs(View v, int r0, int nrows, int n) {
   int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -799,13 +843,13 @@ extern "C" int ramd_dense_top_ok(const RamdShape *sh) {
 
 extern "C" int ramd_launch_dense_top(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
                                      RamdHandover left, const float *targets, int ld, int n, int ngroups, const int *goff,
-                                     const int *gsize, const int *gt, const float *weight) {
+                                     const int *gsize, const int *gt, const float *weight, int stats) {
   if (!ramd_dense_top_ok(sh)) return 0;
   const int fwd_ks = handover_fwd_ks(left);
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
   size_t shm = (size_t)(sh->H + OUT_SEGS * 64 * 4 + (OUT_SEGS + 3) * sh->O) * sizeof(float);
-  TopLoss tl = {targets, ld, n, ngroups, goff, gsize, gt, weight};
+  TopLoss tl = {targets, ld, n, ngroups, goff, gsize, gt, weight, ngroups > 0 ? 0 : stats};
   if (ngroups > 0)
     RAMD_LAUNCH(k_text_top<2>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
   else
@@ -826,7 +870,7 @@ extern "C" int ramd_launch_dense_top_tanh(ramd_stream_t st_, const RamdShape *sh
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
   size_t shm = (size_t)(sh->H + OUT_SEGS * 64 * 4 + (OUT_SEGS + 3) * sh->O) * sizeof(float);
-  TopLoss tl = {targets, ld, n, 0, NULL, NULL, NULL, NULL};
+  TopLoss tl = {targets, ld, n, 0, NULL, NULL, NULL, NULL, 0};
   RAMD_LAUNCH(k_text_top<3>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
   return 1;
 }
@@ -858,9 +902,13 @@ extern "C" void ramd_launch_multi_xent_accumulate(ramd_stream_t st_, const RamdS
 
 extern "C" void ramd_launch_sigmoid_mse_error(ramd_stream_t st_, const RamdShape *sh,
                                               const RamdBuffers *b, int row0, int nrows, int n,
-                                              const float *targets, int ld) {
+                                              const float *targets, int ld, int stats) {
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
+  if (stats) {
+    RAMD_LAUNCH(k_sigmoid_mse_error_stats, dim3(nrows), dim3(256), 0, st, v, row0, nrows, n, targets, ld);
+    return;
+  }
   RAMD_LAUNCH(k_sigmoid_mse_error, dim3((nrows * n + 255) / 256), dim3(256), 0, st, v, row0, nrows, n,
               targets, ld);
 }

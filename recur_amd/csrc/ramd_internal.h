@@ -200,10 +200,11 @@ int ramd_dense_top_ok(const RamdShape *sh); /* ramd_launch_dense_top will take t
 void ramd_launch_text_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
                           int nrows, RamdHandover left);
 /* the same launch with rnnca's loss (targets [nrows][ld] on the device, first n outputs; ngroups == 0) or gstclassify's
- * class groups between output layer and backprop; 0: not this kernel's shape, nothing launched */
+ * class groups between output layer and backprop; 0: not this kernel's shape, nothing launched.  stats (rnnca's loss only,
+ * rnn_amd_set_automaton_steps alone): the row's sum of (target - a)^2 and one count into the statistics */
 int ramd_launch_dense_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, RamdHandover left,
                           const float *targets, int ld, int n, int ngroups, const int *goff, const int *gsize, const int *gt,
-                          const float *weight);
+                          const float *weight, int stats);
 /* the same launch with parrot's loss (k_text_top<3>: tanh in place on the first n outputs, (1 - a a) (target - a), the
  * row's squared error into the statistics); a thread per column, so any o_size the text top takes (<= 256) */
 int ramd_dense_top_tanh_ok(const RamdShape *sh); /* (ramd_text_top_ok, RECUR_AMD_DENSE_TOP) */
@@ -336,6 +337,10 @@ void ramd_launch_classify_step(ramd_stream_t st, const RamdShape *sh, const Ramd
 struct RamdAutomatonStep;
 void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
                                 const struct RamdAutomatonStep *p);
+/* rnn_amd_set_automaton_steps (set_api.c): the one gather launch of a block (kernels_automaton_train.hip).
+ * RamdAutomatonTrainRows and its contract stand in automaton_train_rule.h, next to the rule it embeds */
+struct RamdAutomatonTrainRows;
+void ramd_launch_automaton_train_rows(ramd_stream_t st, const struct RamdAutomatonTrainRows *p);
 
 /* rnn_amd_dream_sequences (dream_api.c): parrot's player (fill_audio_chunk, gstparrot.c:556-583) for `rows` sequences in
  * lock step, sequence k on forward-only state row row0 + k, each fed its own last answer; the net has as many inputs as
@@ -396,9 +401,10 @@ typedef struct RamdTextsContinue {
 } RamdTextsContinue;
 void ramd_launch_texts_continue(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdTextsContinue *p);
 /* rnnca's loss (gstrnnca.c:701-714): sigmoid in place on the first n outputs, slope * (target -
- * a) into o_error; targets is a device array [nrows][ld] */
+ * a) into o_error; targets is a device array [nrows][ld].  stats: the same answers and errors from the variant that also
+ * adds the row's sum of (target - a)^2 and one count to the statistics (rnn_amd_set_automaton_steps alone) */
 void ramd_launch_sigmoid_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
-                                   int row0, int nrows, int n, const float *targets, int ld);
+                                   int row0, int nrows, int n, const float *targets, int ld, int stats);
 /* parrot's loss (gstparrot.c:464-477, parrot_rule.h): fast_tanhf in place on the first n outputs, (1 - a a) (target - a)
  * into o_error, the row's sum of (target - a)^2 and one count into the statistics; targets is a device array [nrows][ld] */
 void ramd_launch_tanh_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, int n,

@@ -69,6 +69,8 @@ typedef struct RamdEngine {
   float *d_dense;       /* staging for dense inputs, [Scap+Fcap][input_size] */
   float *d_frames;      /* rnn_amd_set_dense_steps_tanh's block of frames, [n_steps + 1][n_nets][ld]: grown on demand */
   size_t d_frames_bytes;
+  void *d_automaton;    /* rnn_amd_set_automaton_steps's block: film, positions, offset lists, gathered rows: grown on demand */
+  size_t d_automaton_bytes;
   float *delta_own;     /* library-owned ih_delta||ho_delta                */
   int delta_external;
   /* The delta sums of the last set call, kept as the un-summed planes the GEMM left (in a workspace of their own)

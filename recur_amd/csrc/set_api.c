@@ -8,6 +8,7 @@
 #define RAMD_HIP_HOST 1
 #include "rnn_host.h"
 #include "parrot_rule.h"
+#include "automaton_train_rule.h"
 
 RnnAmdSet *rnn_amd_set_open(RecurNN **nets, int n_nets) {
   if (!nets || n_nets < 1) {
@@ -632,23 +633,32 @@ void rnn_amd_set_text_opinion(RnnAmdSet *set, int i, int advance) {
 }
 
 /* rnnca's loss on the device (gstrnnca.c:701-714) after rnn_amd_set_opinion: sigmoid of the
- * first n outputs in place, o_error = slope * (target - answer); targets: host [n_nets][ld] */
-void rnn_amd_set_sigmoid_mse_error(RnnAmdSet *set, const float *targets, int ld, int n) {
+ * first n outputs in place, o_error = slope * (target - answer); targets: host [n_nets][ld], or (on_dev) device rows ld
+ * floats apart: the gathered rows of rnn_amd_set_automaton_steps.  stats: the row's squared error and a count go into the
+ * set's statistics -- only rnn_amd_set_automaton_steps asks for that, the public calls leave the statistics alone */
+static void set_sigmoid_mse_error(RnnAmdSet *set, const char *what, const float *targets, int ld, int n, int on_dev,
+                                  int stats) {
   RamdEngine *e = set->eng;
   ramd_top_done_clear(e);
-  ramd_set_need_training(set, "rnn_amd_set_sigmoid_mse_error");
+  ramd_set_need_training(set, what);
   if (n < 1 || n > e->sh.output_size || ld < n) {
-    fprintf(stderr, "librecur_amd: rnn_amd_set_sigmoid_mse_error over %d of %d outputs (ld %d)\n", n,
-            e->sh.output_size, ld);
+    fprintf(stderr, "librecur_amd: %s over %d of %d outputs (ld %d)\n", what, n, e->sh.output_size, ld);
     abort();
   }
   set_streams_to_dev(set);
-  size_t bytes = (size_t)set->n * n * sizeof(float);
-  group_room(e, bytes);
-  ramd_upload_rows(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n);
-  ramd_launch_sigmoid_mse_error(ramd_stream, &e->sh, &e->b, set->row0, set->n, n, (const float *)e->d_group,
-                                n);
+  if (!on_dev) {
+    size_t bytes = (size_t)set->n * n * sizeof(float);
+    group_room(e, bytes);
+    ramd_upload_rows(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n);
+    targets = (const float *)e->d_group;
+    ld = n;
+  }
+  ramd_launch_sigmoid_mse_error(ramd_stream, &e->sh, &e->b, set->row0, set->n, n, targets, ld, stats);
   set_streams_dev_wrote(set);
+}
+
+void rnn_amd_set_sigmoid_mse_error(RnnAmdSet *set, const float *targets, int ld, int n) {
+  set_sigmoid_mse_error(set, "rnn_amd_set_sigmoid_mse_error", targets, ld, n, 0, 0);
 }
 
 /* dense inputs -> hidden layer's sums only (they stay in the workspace for ramd_launch_dense_top); 0 where that launch
@@ -659,28 +669,48 @@ static int dense_top_ok(RnnAmdSet *set, const float *inputs) {
          set->nets[0]->presynaptic_noise == 0.0f && set->nets[0]->bptt;
 }
 
-void rnn_amd_set_opinion_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld,
-                                     int n) {
+/* on_dev: inputs and targets are device rows (never with a bottom layer: rnn_amd_set_automaton_steps refuses such a set);
+ * advance: rnn_bptt_advance first; stats: see set_sigmoid_mse_error */
+static void set_opinion_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld, int n,
+                                    int on_dev, int advance, int stats) {
   RamdEngine *e = set->eng;
   if (!dense_top_ok(set, inputs) || n < 1 || n > e->sh.output_size || ld < n) {
-    rnn_amd_set_opinion(set, inputs, ld_inputs, NULL);
-    rnn_amd_set_sigmoid_mse_error(set, targets, ld, n);
+    if (on_dev) {
+      set_forward(set, RAMD_IN_DENSE, inputs, ld_inputs, 0, NULL, advance, RAMD_FWD_WHOLE);
+    } else {
+      if (advance) {
+        rnn_amd_set_advance(set);
+      }
+      rnn_amd_set_opinion(set, inputs, ld_inputs, NULL);
+    }
+    set_sigmoid_mse_error(set, "rnn_amd_set_sigmoid_mse_error", targets, ld, n, on_dev, stats);
     return;
   }
   ramd_set_need_training(set, "rnn_amd_set_opinion_sigmoid_mse");
-  size_t bytes = (size_t)set->n * n * sizeof(float);
-  group_room(e, bytes);
-  /* inputs and targets leave together with the ring indices (set_forward's flush) */
-  ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), e->sh.input_size * sizeof(float), set->n, 0);
-  ramd_upload_rows_q(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n, 0);
-  const RamdHandover left = set_forward(set, RAMD_IN_DENSE, e->d_dense, e->sh.input_size, 0, NULL, 0, RAMD_FWD_FOR_DENSE_TOP);
-  if (!ramd_launch_dense_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, left, (const float *)e->d_group, n, n, 0,
-                             NULL, NULL, NULL, NULL)) {
+  if (!on_dev) {
+    size_t bytes = (size_t)set->n * n * sizeof(float);
+    group_room(e, bytes);
+    /* inputs and targets leave together with the ring indices (set_forward's flush) */
+    ramd_upload_rows_q(e->d_dense, inputs, ld_inputs * sizeof(float), e->sh.input_size * sizeof(float), set->n, 0);
+    ramd_upload_rows_q(e->d_group, targets, ld * sizeof(float), n * sizeof(float), set->n, 0);
+    inputs = e->d_dense;
+    ld_inputs = e->sh.input_size;
+    targets = (const float *)e->d_group;
+    ld = n;
+  }
+  const RamdHandover left = set_forward(set, RAMD_IN_DENSE, inputs, ld_inputs, 0, NULL, advance, RAMD_FWD_FOR_DENSE_TOP);
+  if (!ramd_launch_dense_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, left, targets, ld, n, 0, NULL, NULL, NULL, NULL,
+                             stats)) {
     fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_sigmoid_mse: the top launch declined a shape it had accepted\n");
     abort();
   }
   set_streams_dev_wrote(set);
   ramd_top_done_set(e, set->row0, set->n, 0);
+}
+
+void rnn_amd_set_opinion_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld_inputs, const float *targets, int ld,
+                                     int n) {
+  set_opinion_sigmoid_mse(set, inputs, ld_inputs, targets, ld, n, 0, 0, 0);
 }
 
 /* Parrot's loss (train_net, gstparrot.c:464-477; parrot_rule.h).  The rows of inputs and targets are the caller's host
@@ -778,7 +808,7 @@ void rnn_amd_set_opinion_grouped_softmax(RnnAmdSet *set, const float *inputs, in
   active_mask_to_dev(e, trained, set->n, 1); /* (for the delta call that follows: travels with the rest) */
   const RamdHandover left = set_forward(set, RAMD_IN_DENSE, e->d_dense, s->input_size, 0, NULL, 0, RAMD_FWD_FOR_DENSE_TOP);
   if (!ramd_launch_dense_top(ramd_stream, s, &e->b, set->row0, set->n, left, NULL, 0, 0, n_groups, g.offset, g.size,
-                             g.targets, g.weight)) {
+                             g.targets, g.weight, 0)) {
     fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_grouped_softmax: the top launch declined a shape it had accepted\n");
     abort();
   }
@@ -864,8 +894,9 @@ typedef struct {
   const float *targets; /* [n][ld], host rows or (on_dev) device rows: the first n_targets outputs */
   int ld, n_targets;
   int loss;             /* dense: STEP_LOSS_SIGMOID (rnnca's) or STEP_LOSS_TANH (parrot's) */
-  int advance;          /* dense, parrot's: rnn_bptt_advance in front, as train_net has it */
-  int on_dev;           /* dense, parrot's: inputs and targets are device rows (the many-step call's frames) */
+  int advance;          /* dense: rnn_bptt_advance in front (parrot's train_net; rnn_amd_set_automaton_steps's `advance`) */
+  int on_dev;           /* dense: inputs and targets are device rows (the many-step calls' blocks) */
+  int stats;            /* dense, rnnca's: the squared error into the statistics (rnn_amd_set_automaton_steps alone) */
   /* the multi-head step (rnn_amd_set_multi_step_deltas's arguments) */
   const int *hot, *next, *target_class;
   int alphabet_len;
@@ -882,7 +913,8 @@ static void step_deltas(RnnAmdSet *set, const StepSpec *sp, RamdPendingDelta *de
     set_opinion_tanh_error(set, sp->inputs, sp->ld_inputs, sp->targets, sp->ld, sp->n_targets, sp->on_dev, sp->advance);
     set_calc_deltas(set, 0, NULL, NULL, 0, NULL, 0, defer);
   } else {
-    rnn_amd_set_opinion_sigmoid_mse(set, sp->inputs, sp->ld_inputs, sp->targets, sp->ld, sp->n_targets);
+    set_opinion_sigmoid_mse(set, sp->inputs, sp->ld_inputs, sp->targets, sp->ld, sp->n_targets, sp->on_dev, sp->advance,
+                            sp->stats);
     set_calc_deltas(set, 0, NULL, NULL, 0, NULL, 0, defer);
   }
 }
@@ -1021,6 +1053,73 @@ void rnn_amd_set_dense_steps_tanh(RnnAmdSet *set, const float *frames, int ld, i
                     momentum);
     if (condition) {
       rnn_condition_net(set->nets[0]); /* gstparrot.c:544-545: behind the update */
+    }
+  }
+}
+
+/* rnnca's trainer over a block of a film (gstrnnca.c:669-750; automaton_train_rule.h): the film, the positions and the
+ * offset lists go up once, one launch gathers every generation's input and target rows from the film's bytes, and the
+ * generations read their rows where they lie: see recur_amd.h */
+static size_t automaton_room(size_t *at, size_t bytes) { /* -> the offset of `bytes` more, 256-byte aligned */
+  const size_t here = *at;
+  *at = (here + bytes + 255) & ~(size_t)255;
+  return here;
+}
+
+void rnn_amd_set_automaton_steps(RnnAmdSet *set, const RnnAmdAutomaton *ca, const u8 *frames, const int *xy, int xy_per_step,
+                                 int n_steps, int advance, int learning_style, float momentum, float momentum_soft_start,
+                                 int condition) {
+  AutomatonRule g = {0};
+  if (ca) {
+    g = (AutomatonRule){ca->width, ca->height, ca->offsets_y, ca->len_y, ca->offsets_c, ca->len_c, ca->len_pos, ca->edges};
+  }
+  RamdEngine *e = set ? set->eng : NULL;
+  const int refusal = automaton_block_refusal(set != NULL, ca ? &g : NULL, frames != NULL, xy, xy_per_step, n_steps,
+                                              set ? set->n : 0, e ? e->sh.input_size : 0, e ? e->sh.output_size : 0,
+                                              e ? e->sh.bI : 0);
+  if (refusal) { /* (the rule is automaton_train_rule.h's, where it is asked without a device) */
+    fprintf(stderr, "librecur_amd: rnn_amd_set_automaton_steps: %s (%d steps of %d trainers on a grid of %d x %d)\n",
+            automaton_block_refusal_text(refusal), n_steps, set ? set->n : 0, g.width, g.height);
+    abort();
+  }
+  ramd_set_need_training(set, "rnn_amd_set_automaton_steps");
+  const int n = set->n, in = e->sh.input_size;
+  const size_t cells = (size_t)g.width * g.height;
+  const size_t film = ((size_t)n_steps + 1) * 3 * cells, n_xy = 2 * (size_t)(xy_per_step ? n_steps : 1) * n;
+  const size_t n_offy = 2 * (size_t)g.len_y, n_offc = 2 * (size_t)g.len_c;
+  size_t bytes = 0;
+  const size_t at_film = automaton_room(&bytes, film);
+  const size_t at_xy = automaton_room(&bytes, n_xy * sizeof(int));
+  const size_t at_off = automaton_room(&bytes, (n_offy + n_offc) * sizeof(int));
+  const size_t at_rows = automaton_room(&bytes, (size_t)n_steps * n * in * sizeof(float));
+  const size_t at_targets = automaton_room(&bytes, (size_t)n_steps * n * 3 * sizeof(float));
+  ramd_engine_ensure_device(e);
+  if (bytes > e->d_automaton_bytes) {
+    ramd_dsync(); /* (an earlier block's generations may still be reading the old one) */
+    ramd_dev_free(e->d_automaton);
+    e->d_automaton = ramd_dev_alloc(bytes);
+    e->d_automaton_bytes = bytes;
+  }
+  char *base = e->d_automaton;
+  int *d_off = (int *)(base + at_off);
+  ramd_upload_q(base + at_xy, xy, n_xy * sizeof(int));
+  ramd_upload_q(d_off, g.offsets_y, n_offy * sizeof(int));
+  ramd_upload_q(d_off + n_offy, g.offsets_c, n_offc * sizeof(int));
+  ramd_upload(base + at_film, frames, film);
+  g.offsets_y = d_off;
+  g.offsets_c = d_off + n_offy;
+  const RamdAutomatonTrainRows gather = {.g = g, .frames = (const u8 *)(base + at_film), .xy = (const int *)(base + at_xy),
+                                         .xy_per_step = xy_per_step, .n_steps = n_steps, .n = n, .input_size = in,
+                                         .rows = (float *)(base + at_rows), .targets = (float *)(base + at_targets)};
+  ramd_launch_automaton_train_rows(ramd_stream, &gather);
+  for (int t = 0; t < n_steps; t++) {
+    rnn_bptt_clear_deltas(set->nets[0]); /* (lazy: the delta call simply does not accumulate) */
+    const StepSpec sp = {.i = -1, .inputs = gather.rows + (size_t)t * n * in, .ld_inputs = in,
+                         .targets = gather.targets + (size_t)t * n * 3, .ld = 3, .n_targets = 3, .loss = STEP_LOSS_SIGMOID,
+                         .advance = advance != 0, .on_dev = 1, .stats = 1};
+    set_step(set, &sp, learning_style, automaton_train_momentum(set->nets[0]->generation, momentum, momentum_soft_start));
+    if (condition) {
+      rnn_condition_net(set->nets[0]); /* gstrnnca.c:739: behind the update */
     }
   }
 }

@@ -17,6 +17,8 @@ symbols' classes; ``run_automaton`` plays rnnca's automaton from a seed frame on
 offset pattern (rnn_amd_automaton_parse_offsets); ``dream_sequences`` runs parrot's player, many closed-loop sequences fed
 their own answers, in one call (rnn_amd_dream_sequences); ``train_frames`` runs parrot's trainer over a block of frames,
 every frame the target of one generation and the input of the next, in one call (rnn_amd_set_dense_steps_tanh).
+``train_automaton`` runs rnnca's trainer over a block of a film of bytes, the trainers' rows gathered on the device, in one
+call (rnn_amd_set_automaton_steps).
 ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
@@ -415,6 +417,28 @@ def train_frames(lib, set_or_handle, frames, n, learning_style=rc.WEIGHTED, mome
     lib.rnn_amd_set_dense_steps_tanh(handle, rc.fptr(fr), fr.shape[2], fr.shape[0] - 1, n, learning_style, momentum,
                                      int(bool(condition)))
     return fr.shape[0] - 1
+
+
+def train_automaton(lib, set_or_handle, geometry, frames, xy, advance=False, learning_style=rc.WEIGHTED, momentum=0.95,
+                    soft_start=0.0, condition=False):
+    """rnn_amd_set_automaton_steps: rnnca's trainer over a block of a film, uint8 [T + 1][3][height][width] on the grid of
+    `geometry` (an AutomatonGeometry): T generations in one call, generation t's trainers fed fill_net_inputs of frames[t]
+    at their cells and scored against the three bytes of frames[t + 1] there (sigmoid answer, slope error, the deltas summed
+    over the trainers, the update with the soft-started momentum; rnn_condition_net behind each with condition).  xy: the
+    trainers' (x, y), int32 [n][2] for the whole block or [T][n][2], a list per generation.  advance: rnn_bptt_advance in
+    front of every opinion (the plugin does not).  set_or_handle: an AmdBatchedSet or an RnnAmdSet handle.  The last frame
+    of a block is the first of the next.  Returns T."""
+    handle = getattr(set_or_handle, "handle", set_or_handle)
+    g = geometry
+    fr = np.ascontiguousarray(frames, dtype=np.uint8)
+    assert fr.ndim == 4 and fr.shape[0] >= 2 and fr.shape[1:] == (3, g.height, g.width), "frames are [T + 1][3][height][width]"
+    T = fr.shape[0] - 1
+    pos = np.ascontiguousarray(xy, dtype=np.int32)
+    n = lib.rnn_amd_set_size(handle)
+    assert pos.shape in ((n, 2), (T, n, 2)), "xy is [n][2] or [T][n][2], n the nets of the set"
+    lib.rnn_amd_set_automaton_steps(handle, C.byref(g.struct), rc.u8ptr(fr), rc.iptr(pos), int(pos.ndim == 3), T,
+                                    int(bool(advance)), learning_style, momentum, soft_start, int(bool(condition)))
+    return T
 
 
 class ApiSet:
