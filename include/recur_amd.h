@@ -1023,6 +1023,47 @@ void rnn_amd_set_automaton_steps(RnnAmdSet *set, const RnnAmdAutomaton *ca,
                                  const int *xy /* [xy_per_step ? n_steps : 1][n_nets][2]: (x, y) */, int xy_per_step,
                                  int n_steps, int advance, int learning_style, float momentum, float momentum_soft_start,
                                  int condition);
+/* GSTCLASSIFY'S TRAINER on the device, many windows in one call (gstclassify.c: train_channel 2070-2127, maybe_learn
+ * 2180-2257).  `set` is a training set whose streams are the audio channels; features[t][j] is channel j's feature row of
+ * window t (input_size floats, rows ld apart), targets[t][j][i] its class in group i -- < 0 or >= group_size[i]: no label.
+ * The outputs are n_groups class groups, group i the columns group_offset[i] .. + group_size[i] - 1; error_weight (or
+ * NULL) one factor per output.  Generation t, for t = 0 .. n_steps - 1, is maybe_learn's body:
+ *     rnn_bptt_clear_deltas
+ *     for every channel j: rnn_opinion(features[t][j]); the class-group loss against targets[t][j] (softmax per labelled
+ *         group, +1 on the target, zeros in the groups without a label, the whole row times error_weight where any group
+ *         is labelled); rnn_bptt_calc_deltas, summed, for the channels that have a label; rnn_bptt_advance behind them
+ *     if (err_sum) rnn_apply_learning(nets[0], learning_style,
+ *                      rnn_calculate_momentum_soft_start(nets[0]->generation, nets[0]->bptt->momentum, momentum_soft_start))
+ *     rnn_condition_net(nets[0]) when `condition` is not 0
+ * THE UPDATE GATE is the reference's `if (err_sum)`, exactly and without a read-back: err_sum is the sum of the trained
+ * groups' wrongness 1 - p[target], every term >= 0, so it is non-zero iff some trained channel's wrongness is not 0.0f (a
+ * NaN counts as non-zero); the loss kernel raises a word on the device and the optimiser launch reads it
+ * (csrc/classify_train_rule.h states the rule and why it is the reference's).  A classifier that has become certain --
+ * every trained group's likelihood exactly 1 -- therefore makes NO update, not a momentum-only one.  A generation in which
+ * no channel has a label makes no delta call and no update.  After a generation whose gate stayed closed the weights,
+ * momentum and aux arrays are what they were; the delta arrays hold that generation's sums all the same; the statistics
+ * (rnn_amd_set_read_stats: error, correct, count) hold the loop's figures; the channels' generation counters have stepped.
+ * The results are those of a loop of rnn_amd_classify_generation(..., balance NULL, exact_gate 1) over the windows, bit
+ * for bit (that loop decides its gate from the statistics it reads back: clear them first where the difference of two
+ * large sums could lose a small error).
+ * Features, targets, every generation's mask of labelled channels (each on a 4-byte boundary), n_steps gate words, the
+ * groups and the weights go up once per block, into a buffer of the engine's that grows on demand and is freed with the
+ * engine; the generations read them where they lie: no upload per generation, no synchronisation between generations
+ * (the block's own upload is waited for where it does not fit the mailbox; the conditioning's random damage, where the
+ * net's flags ask for it, draws on the host).  Output layer, loss and top backprop are ONE launch exactly where
+ * rnn_amd_set_opinion_grouped_softmax makes them one -- at most 64 output columns and a whole number of 4 channels --,
+ * otherwise the forward pass and the loss kernel: the two forms sum the output layer in different orders, and the block
+ * keeps the loop's bits at every set size.  Both read the block, and the delta call reads the generation's mask there
+ * whatever the number of channels.  The update is always a launch of its own, never the delta GEMM's epilogue.
+ * A set with a bottom layer, a net with presynaptic noise, a joined exchange (rnn_amd_set_exchange_join) and a distributed
+ * group of more than one rank run generation by generation from the host rows instead, the gate read back: same results.
+ * It aborts with a message (which blocks it takes is stated once, csrc/classify_train_rule.h: classify_block_refusal,
+ * tested there without a device) on: NULL features or targets; n_steps < 1; ld < input_size; n_groups < 1 or no group
+ * lists; a group that is empty or not within the outputs; a forward-only set. */
+void rnn_amd_set_classify_steps(RnnAmdSet *set, const float *features /* [n_steps][n_nets][ld] */, int ld,
+                                const int *targets /* [n_steps][n_nets][n_groups], <0 or >=size: not trained */,
+                                int n_steps, int n_groups, const int *group_offset, const int *group_size,
+                                const float *error_weight, int learning_style, float momentum_soft_start, int condition);
 /* PARROT'S PLAYER on the device, many closed-loop sequences in one run: the batched form of fill_audio_chunk's loop over
  * the channels (gstparrot.c:556-583), in which every channel's dream net is fed its own last answer.  Sequence k is a
  * forward-only clone c_k of `net` with a generator g_k and an input row x_k = first[k] (net->input_size floats, row stride

@@ -94,6 +94,20 @@ int rnn_amd_classify_generation(RnnAmdSet *set, const float *features, int ld_fe
                                 const float *error_weight, RnnAmdBalancedTraining *balance,
                                 int learning_style, float momentum_soft_start, int exact_gate);
 
+/* n_steps of those generations, exact_gate 1, from one block of windows -- features [n_steps][channels][ld_features],
+ * targets [n_steps][channels][n_groups] -- as ONE call that stays on the device: rnn_amd_set_classify_steps (recur_amd.h)
+ * with rnn_condition_net behind every generation, the reference's `if (err_sum)` decided on the device, no upload per
+ * generation and no synchronisation between generations.  Results, statistics, generation counters and generators are
+ * those of the loop of rnn_amd_classify_generation(..., exact_gate 1), bit for bit.
+ * With `balance` every generation's draws are made ahead, in the loop's order (per generation the probabilities from the
+ * counts so far, then one draw per labelled (channel, group), channel-major), from the prototype's generator, and the
+ * block trains on the chosen labels; seen / used end as the loop's.  Drawing ahead is only the loop where nothing else
+ * draws from that generator in between: with presynaptic noise, or RNN_COND_BIT_RAND among the net's conditioning flags,
+ * the call IS the loop of rnn_amd_classify_generation(..., exact_gate 1).  Returns the number of groups trained. */
+int rnn_amd_classify_generations(RnnAmdSet *set, const float *features, int ld_features, const int *targets, int n_steps,
+                                 int n_groups, const int *group_offset, const int *group_size, const float *error_weight,
+                                 RnnAmdBalancedTraining *balance, int learning_style, float momentum_soft_start);
+
 #ifdef __cplusplus
 }
 #endif

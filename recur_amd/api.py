@@ -286,6 +286,8 @@ AMD_API = {
     "rnn_amd_run_automaton": (C.c_int, [NetP, C.POINTER(Automaton), c_u8_p, C.c_int, c_float_p, c_float_p, C.c_int, c_u8_p]),
     "rnn_amd_set_automaton_steps": (None, [C.c_void_p, C.POINTER(Automaton), c_u8_p, c_int_p, C.c_int, C.c_int, C.c_int,
                                            C.c_int, C.c_float, C.c_float, C.c_int]),
+    "rnn_amd_set_classify_steps": (None, [C.c_void_p, c_float_p, C.c_int, c_int_p, C.c_int, C.c_int, c_int_p, c_int_p,
+                                          c_float_p, C.c_int, C.c_float, C.c_int]),
     "rnn_amd_dream_sequences": (C.c_int, [NetP, c_float_p, C.c_int, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_uint64),
                                           C.POINTER(RandCtx), c_float_p, c_float_p, C.c_int, c_float_p, c_float_p,
                                           C.POINTER(RandCtx)]),
@@ -527,6 +529,8 @@ CLASSIFY_API = {
     "rnn_amd_balanced_begin": (None, [C.POINTER(BalancedTraining)]),
     "rnn_amd_classify_generation": (C.c_int, [C.c_void_p, c_float_p, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p,
                                               c_float_p, C.POINTER(BalancedTraining), C.c_int, C.c_float, C.c_int]),
+    "rnn_amd_classify_generations": (C.c_int, [C.c_void_p, c_float_p, C.c_int, c_int_p, C.c_int, C.c_int, c_int_p, c_int_p,
+                                               c_float_p, C.POINTER(BalancedTraining), C.c_int, C.c_float]),
 }
 
 

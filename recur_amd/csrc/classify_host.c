@@ -6,6 +6,7 @@
  */
 #include "char_host.h"
 #include "recur_amd_classify.h"
+#include "classify_train_rule.h"
 #include <inttypes.h>
 
 /* ------------------------------------------------------------------ metadata -- */
@@ -180,18 +181,11 @@ void rnn_amd_balanced_free(RnnAmdBalancedTraining *b) {
 }
 
 void rnn_amd_balanced_begin(RnnAmdBalancedTraining *b) {
-  u32 met = 0;
-  for (int c = 0; c < b->n_outputs; c++) {
-    met += b->seen[c];
-  }
-  const float share = 1.0f / (met + 1.0f);
-  for (int c = 0; c < b->n_outputs; c++) {
-    b->train_p[c] = powf(1.0f - b->seen[c] * share, b->bias);
-  }
+  classify_balance_probabilities(b->seen, b->n_outputs, b->bias, b->train_p); /* (classify_train_rule.h) */
 }
 
-/* recur-rng.h:80-85: a float in [0, 1] from 64 random bits */
-static float unit_draw(rand_ctx *rng) { return (float)ramd_rand64(rng) * (1.0f / ((float)0xfffffffffffffffeULL)); }
+/* the draws of the balanced choice: the next 64 bits of the prototype's generator (recur-rng.h:80-85 makes the float) */
+static uint64_t prototype_draw64(void *rng) { return ramd_rand64(rng); }
 
 /* ------------------------------------------------------------ one generation -- */
 
@@ -219,22 +213,10 @@ int rnn_amd_classify_generation(RnnAmdSet *set, const float *features, int ld_fe
   if (balance) {
     ramd_rng_to_host(net);
   }
-  for (int ch = 0; ch < channels; ch++) {
-    trains[ch] = 0;
-    for (int g = 0; g < n_groups; g++) {
-      const int t = targets[ch * n_groups + g];
-      int take = t >= 0 && t < group_size[g];
-      if (take && balance) {
-        const int out = group_offset[g] + t;
-        balance->seen[out]++;
-        take = balance->train_p[out] > unit_draw(&net->rng);
-        balance->used[out] += take;
-      }
-      use[ch * n_groups + g] = take ? t : -1;
-      trains[ch] |= take;
-      trained_groups += take;
-    }
-  }
+  /* (classify_train_rule.h: classify_balance_choose, shared with rnn_amd_classify_generations) */
+  trained_groups = classify_balance_choose(channels, n_groups, group_offset, group_size, targets,
+                                           balance ? balance->train_p : NULL, balance ? balance->seen : NULL,
+                                           balance ? balance->used : NULL, prototype_draw64, &net->rng, use, trains);
   if (balance) {
     ramd_rng_from_host(net);
   }
@@ -267,4 +249,56 @@ int rnn_amd_classify_generation(RnnAmdSet *set, const float *features, int ld_fe
   free(use);
   free(trains);
   return trained_groups;
+}
+
+/* ------------------------------------------------------------ many generations -- */
+
+int rnn_amd_classify_generations(RnnAmdSet *set, const float *features, int ld_features, const int *targets, int n_steps,
+                                 int n_groups, const int *group_offset, const int *group_size, const float *error_weight,
+                                 RnnAmdBalancedTraining *balance, int learning_style, float momentum_soft_start) {
+  RecurNN *net = set->nets[0]; /* the prototype: its generator makes the balanced-training draws */
+  const int channels = set->n;
+  const size_t window = (size_t)channels * n_groups;
+  /* (everything but the rows' width, which the set call knows: with a bottom layer it is that layer's) */
+  if (classify_block_refusal(features != NULL, targets != NULL, n_steps, 0, 0, n_groups, group_offset, group_size,
+                             net->output_size)) {
+    rnn_amd_set_classify_steps(set, features, ld_features, targets, n_steps, n_groups, group_offset, group_size, error_weight,
+                               learning_style, momentum_soft_start, 1); /* (prints which and aborts) */
+    return 0;
+  }
+  long long trained_groups = 0;
+  if (!balance) {
+    rnn_amd_set_classify_steps(set, features, ld_features, targets, n_steps, n_groups, group_offset, group_size, error_weight,
+                               learning_style, momentum_soft_start, 1);
+    for (size_t q = 0; q < (size_t)n_steps * window; q++) {
+      trained_groups += classify_target_trains(targets[q], group_size[q % n_groups]);
+    }
+    return (int)trained_groups;
+  }
+  /* every generation's draws ahead, in the loop's order -- only where nothing else draws from the prototype's generator
+   * between them: no noise in front of a pass, no random damage in the conditioning behind an update */
+  const u32 cond = net->flags >> RNN_COND_USE_OFFSET;
+  if (net->presynaptic_noise != 0.0f || (cond & (1u << RNN_COND_BIT_RAND))) {
+    for (int t = 0; t < n_steps; t++) {
+      trained_groups += rnn_amd_classify_generation(set, features + (size_t)t * channels * ld_features, ld_features, n_groups,
+                                                    group_offset, group_size, targets + (size_t)t * window, error_weight,
+                                                    balance, learning_style, momentum_soft_start, 1);
+    }
+    return (int)trained_groups;
+  }
+  int *use = malloc(sizeof(int) * (size_t)n_steps * window);
+  u8 *trains = malloc(channels);
+  ramd_rng_to_host(net);
+  for (int t = 0; t < n_steps; t++) {
+    rnn_amd_balanced_begin(balance);
+    trained_groups += classify_balance_choose(channels, n_groups, group_offset, group_size, targets + (size_t)t * window,
+                                              balance->train_p, balance->seen, balance->used, prototype_draw64, &net->rng,
+                                              use + (size_t)t * window, trains);
+  }
+  ramd_rng_from_host(net);
+  rnn_amd_set_classify_steps(set, features, ld_features, use, n_steps, n_groups, group_offset, group_size, error_weight,
+                             learning_style, momentum_soft_start, 1);
+  free(use);
+  free(trains);
+  return (int)trained_groups;
 }

@@ -376,6 +376,9 @@ static void engine_free_device(RamdEngine *e) {
   ramd_dev_free(e->d_automaton);
   e->d_automaton = NULL;
   e->d_automaton_bytes = 0;
+  ramd_dev_free(e->d_classify);
+  e->d_classify = NULL;
+  e->d_classify_bytes = 0;
   e->d_mranges = NULL;
   e->d_mclass = NULL;
   free(e->lr_pushed);

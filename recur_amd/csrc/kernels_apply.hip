@@ -78,7 +78,7 @@ for (int i = 0; i < 4; i++) {
 
 template <int METHOD>
 __global__ __launch_bounds__(256) void k_apply(ApplySegs sg, float momentum, float mw,
-                                               const float *rs) {
+                                               const float *rs, const unsigned *gate) {
   const int g = (blockIdx.x >= sg.first[2]) ? 2 : (blockIdx.x >= sg.first[1]) ? 1 : 0;
   /* the recurrent layer's blocks run from the bottom of the matrix up: the rows that sum many
    * planes (the rest rows, last in memory) then start first instead of forming the tail */
@@ -122,6 +122,9 @@ __global__ __launch_bounds__(256) void k_apply(ApplySegs sg, float momentum, flo
   } else {
     Dl = ld4(delta + 4 * q);
   }
+  /* a closed gate (classify_train_rule.h: no trained stream's wrongness was other than 0): the sums above are formed and
+   * stored, the update is not made */
+  if (gate && *gate == 0u) return;
   float4 A = (METHOD == 5 || METHOD == 6) ? ld4(aux + 4 * q) : zero4();
   float wv[4] = {W.x, W.y, W.z, W.w}, dv[4] = {Dl.x, Dl.y, Dl.z, Dl.w};
   float mv[4] = {M.x, M.y, M.z, M.w}, av[4] = {A.x, A.y, A.z, A.w};
@@ -359,7 +362,7 @@ extern "C" void ramd_launch_apply_multi(ramd_stream_t st_, int method, int nseg,
                                         const float *const *delta, float *const *m,
                                         float *const *aux, const size_t *n, const float *rate,
                                         float momentum, float mw, const float *rs,
-                                        const RamdPendingDelta *pend) {
+                                        const RamdPendingDelta *pend, const unsigned *gate) {
   hipStream_t st = (hipStream_t)st_;
   ApplySegs sg = {};
   if (pend && nseg >= 2) sg.pend = *pend;
@@ -382,11 +385,11 @@ extern "C" void ramd_launch_apply_multi(ramd_stream_t st_, int method, int nseg,
   dim3 gr(blocks), bl(256);
   int ev = timing_begin(st, T_APPLY);
   switch (method) {
-  case 1: RAMD_LAUNCH(k_apply<1>, gr, bl, 0, st, sg, momentum, mw, rs); break;
-  case 4: RAMD_LAUNCH(k_apply<4>, gr, bl, 0, st, sg, momentum, mw, rs); break;
-  case 5: RAMD_LAUNCH(k_apply<5>, gr, bl, 0, st, sg, momentum, mw, rs); break;
-  case 6: RAMD_LAUNCH(k_apply<6>, gr, bl, 0, st, sg, momentum, mw, rs); break;
-  default: RAMD_LAUNCH(k_apply<0>, gr, bl, 0, st, sg, momentum, mw, rs); break;
+  case 1: RAMD_LAUNCH(k_apply<1>, gr, bl, 0, st, sg, momentum, mw, rs, gate); break;
+  case 4: RAMD_LAUNCH(k_apply<4>, gr, bl, 0, st, sg, momentum, mw, rs, gate); break;
+  case 5: RAMD_LAUNCH(k_apply<5>, gr, bl, 0, st, sg, momentum, mw, rs, gate); break;
+  case 6: RAMD_LAUNCH(k_apply<6>, gr, bl, 0, st, sg, momentum, mw, rs, gate); break;
+  default: RAMD_LAUNCH(k_apply<0>, gr, bl, 0, st, sg, momentum, mw, rs, gate); break;
   }
   timing_end(st, ev);
 }
@@ -481,7 +484,7 @@ extern "C" void ramd_launch_replica_checksum(ramd_stream_t st, int n_arrays, con
 extern "C" void ramd_launch_apply(ramd_stream_t st_, int method, float *w, const float *delta,
                                   float *m, float *aux, size_t n, float rate, float momentum,
                                   float mw, const float *rs) {
-  ramd_launch_apply_multi(st_, method, 1, &w, &delta, &m, &aux, &n, &rate, momentum, mw, rs, nullptr);
+  ramd_launch_apply_multi(st_, method, 1, &w, &delta, &m, &aux, &n, &rate, momentum, mw, rs, nullptr, nullptr);
 }
 
 extern "C" void ramd_launch_fused_updates(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row,

@@ -12,6 +12,7 @@ __device__ unsigned long long g_tt_stamps[16];
 #include "k_top.h"
 #include "fwd_plan.h"
 #include "parrot_rule.h"
+#include "classify_train_rule.h"
 BND_DECL(g_bnd_top, ramd_bnd_top_stamps)
 #pragma clang fp contract(off)
 
@@ -83,6 +84,7 @@ struct TopLoss {
   const int *goff, *gsize, *gt;
   const float *weight;
   int stats;            /* 1: the row's squared error and a count into the statistics (rnn_amd_set_automaton_steps alone) */
+  unsigned *gate;       /* 2: (or NULL) the generation's gate word, raised by a trained row whose wrongness is not 0 */
 };
 /* The progress figure of parrot's loss (parrot_rule.h: parrot_loss), per stream-step: a row's terms are added up by wave
  * reductions over threads 0 .. 255 (thread x brings columns x, x + 256, ...), then the four waves' sums in order 0 .. 3.
@@ -331,6 +333,7 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
           v.b.stat_err[r] += wrong;
           v.b.stat_correct[r] += wins;
           v.b.stat_count[r] += trained;
+          if (tl.gate && classify_gate_raises(wrong)) *tl.gate = 1u; /* (classify_train_rule.h: the reference's if (err_sum)) */
         }
       }
     }
@@ -684,7 +687,7 @@ __global__ __launch_bounds__(64 * MS_WAVES) void k_multi_softmax_error(View v, i
 // ignored windows, the balanced-sampling draw), as the reference's caller does.
 __global__ __launch_bounds__(64) void k_grouped_softmax_error(View v, int row0, int ngroups,
                                                               const int *goff, const int *gsize,
-                                                              const int *gt, const float *weight) {
+                                                              const int *gt, const float *weight, unsigned *gate) {
   extern __shared__ float ex[]; /* [largest group] */
   const RamdShape &s = v.sh;
   const int j = blockIdx.x, r = row0 + j, lane = threadIdx.x;
@@ -701,6 +704,7 @@ __global__ __launch_bounds__(64) void k_grouped_softmax_error(View v, int row0, 
     v.b.stat_err[r] += wrong;
     v.b.stat_correct[r] += wins;
     v.b.stat_count[r] += trained;
+    if (gate && classify_gate_raises(wrong)) *gate = 1u; /* (classify_train_rule.h: the reference's if (err_sum)) */
   }
 }
 
@@ -843,13 +847,13 @@ extern "C" int ramd_dense_top_ok(const RamdShape *sh) {
 
 extern "C" int ramd_launch_dense_top(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
                                      RamdHandover left, const float *targets, int ld, int n, int ngroups, const int *goff,
-                                     const int *gsize, const int *gt, const float *weight, int stats) {
+                                     const int *gsize, const int *gt, const float *weight, int stats, unsigned *gate) {
   if (!ramd_dense_top_ok(sh)) return 0;
   const int fwd_ks = handover_fwd_ks(left);
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
   size_t shm = (size_t)(sh->H + OUT_SEGS * 64 * 4 + (OUT_SEGS + 3) * sh->O) * sizeof(float);
-  TopLoss tl = {targets, ld, n, ngroups, goff, gsize, gt, weight, ngroups > 0 ? 0 : stats};
+  TopLoss tl = {targets, ld, n, ngroups, goff, gsize, gt, weight, ngroups > 0 ? 0 : stats, ngroups > 0 ? gate : nullptr};
   if (ngroups > 0)
     RAMD_LAUNCH(k_text_top<2>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
   else
@@ -870,7 +874,7 @@ extern "C" int ramd_launch_dense_top_tanh(ramd_stream_t st_, const RamdShape *sh
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
   size_t shm = (size_t)(sh->H + OUT_SEGS * 64 * 4 + (OUT_SEGS + 3) * sh->O) * sizeof(float);
-  TopLoss tl = {targets, ld, n, 0, NULL, NULL, NULL, NULL, 0};
+  TopLoss tl = {targets, ld, n, 0, NULL, NULL, NULL, NULL, 0, nullptr};
   RAMD_LAUNCH(k_text_top<3>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
   return 1;
 }
@@ -947,9 +951,9 @@ extern "C" void ramd_launch_grouped_softmax_error(ramd_stream_t st_, const RamdS
                                                   const RamdBuffers *b, int row0, int nrows,
                                                   int ngroups, int largest, const int *goff,
                                                   const int *gsize, const int *gt,
-                                                  const float *weight) {
+                                                  const float *weight, unsigned *gate) {
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
   RAMD_LAUNCH(k_grouped_softmax_error, dim3(nrows), dim3(64), (size_t)largest * sizeof(float), st,
-                     v, row0, ngroups, goff, gsize, gt, weight);
+                     v, row0, ngroups, goff, gsize, gt, weight, gate);
 }

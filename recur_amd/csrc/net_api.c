@@ -685,7 +685,7 @@ void ramd_check_method_arrays(RamdEngine *e, int method) {
  * is one, the bottom layer with its own rate scale (recur-nn.c:606-676; the arrays are
  * disjoint, so the reference's order between them does not matter) */
 static void apply_all(RamdEngine *e, int method, float lr, float lr_top, float momentum,
-                      float mw, const RamdPendingDelta *pend) {
+                      float mw, const RamdPendingDelta *pend, const unsigned *gate) {
   RamdBuffers *b = &e->b;
   ramd_check_method_arrays(e, method);
   float *w[3] = {b->ho_w, b->ih_w, b->bw};
@@ -696,7 +696,7 @@ static void apply_all(RamdEngine *e, int method, float lr, float lr_top, float m
   float rate[3] = {lr_top, lr,
                    e->sh.bI ? lr * e->owner->bottom_layer->learn_rate_scale : 0.0f};
   ramd_launch_apply_multi(ramd_stream, method, e->sh.bI ? 3 : 2, w, d, m, aux, n, rate, momentum, mw,
-                          NULL, pend);
+                          NULL, pend, gate);
 }
 
 /* The update rule, stated once (recur-nn.c:601-678), for rnn_apply_learning, the update fused into the delta GEMM
@@ -719,9 +719,10 @@ int ramd_update_rule(const RecurNNBPTT *bptt, int learning_style, float momentum
   return learning_style;
 }
 
-/* recur-nn.h:312 / recur-nn.c:601-678 */
+/* recur-nn.h:312 / recur-nn.c:601-678.  gate (or NULL): a device word that switches the update off where it is 0
+ * (ramd_launch_apply_multi); the delta sums are formed and stored either way */
 void ramd_apply_learning(RecurNN *net, int learning_method, float momentum,
-                           const RamdPendingDelta *pend) {
+                           const RamdPendingDelta *pend, const unsigned *gate) {
   RamdEngine *e = ramd_engine_of(net);
   ramd_engine_ensure_device(e);
   if (!pend && e->kept_live && e->dev_ready) {
@@ -734,12 +735,12 @@ void ramd_apply_learning(RecurNN *net, int learning_method, float momentum,
   }
   float mw, rate, ho_rate;
   const int kernel_method = ramd_update_rule(net->bptt, learning_method, momentum, &mw, &rate, &ho_rate);
-  apply_all(e, kernel_method, rate, ho_rate, momentum, mw, pend);
+  apply_all(e, kernel_method, rate, ho_rate, momentum, mw, pend, gate);
   ramd_engine_dev_wrote(e, RNN_AMD_WEIGHTS | RNN_AMD_MOMENTUMS);
 }
 
 void rnn_apply_learning(RecurNN *net, int learning_method, float momentum) {
-  ramd_apply_learning(net, learning_method, momentum, NULL);
+  ramd_apply_learning(net, learning_method, momentum, NULL, NULL);
 }
 
 /* recur-nn.h:319 / recur-nn.c:782-855 */

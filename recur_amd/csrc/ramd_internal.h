@@ -201,10 +201,12 @@ void ramd_launch_text_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffe
                           int nrows, RamdHandover left);
 /* the same launch with rnnca's loss (targets [nrows][ld] on the device, first n outputs; ngroups == 0) or gstclassify's
  * class groups between output layer and backprop; 0: not this kernel's shape, nothing launched.  stats (rnnca's loss only,
- * rnn_amd_set_automaton_steps alone): the row's sum of (target - a)^2 and one count into the statistics */
+ * rnn_amd_set_automaton_steps alone): the row's sum of (target - a)^2 and one count into the statistics.  gate (the class
+ * groups only, rnn_amd_set_classify_steps alone; or NULL): a device word that a trained row whose summed wrongness is not
+ * 0.0f sets to 1 (classify_train_rule.h) */
 int ramd_launch_dense_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, RamdHandover left,
                           const float *targets, int ld, int n, int ngroups, const int *goff, const int *gsize, const int *gt,
-                          const float *weight, int stats);
+                          const float *weight, int stats, unsigned *gate);
 /* the same launch with parrot's loss (k_text_top<3>: tanh in place on the first n outputs, (1 - a a) (target - a), the
  * row's squared error into the statistics); a thread per column, so any o_size the text top takes (<= 256) */
 int ramd_dense_top_tanh_ok(const RamdShape *sh); /* (ramd_text_top_ok, RECUR_AMD_DENSE_TOP) */
@@ -230,11 +232,11 @@ void ramd_launch_calc_deltas(ramd_stream_t st, const RamdShape *sh, const RamdBu
                              RamdPendingDelta *defer);
 /* train_channel's loss (gstclassify.c:2070-2119): softmax error per class group against
  * gt[row][group] (< 0: the group is not trained), then the per-output error weights; all
- * arrays are device pointers, `largest` the largest group size */
+ * arrays are device pointers, `largest` the largest group size; gate (or NULL): as ramd_launch_dense_top's */
 void ramd_launch_grouped_softmax_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
                                        int row0, int nrows, int ngroups, int largest,
                                        const int *goff, const int *gsize, const int *gt,
-                                       const float *weight);
+                                       const float *weight, unsigned *gate);
 /* multi_softmax_error (charmodel-multi-predict.c:17-58) for rows whose opinion has been
  * formed: b->target holds each stream's next symbol, tclass[j] its own class head;
  * writes o_error and, per stream, the merged (start, len) range list (terminated by
@@ -436,12 +438,14 @@ void ramd_launch_clear_deltas(ramd_stream_t st, const RamdShape *sh, const RamdB
 void ramd_launch_apply(ramd_stream_t st, int method, float *w, const float *delta, float *m,
                        float *aux, size_t n, float rate, float momentum,
                        float momentum_weight, const float *rate_scale_dev);
-/* the same for up to three arrays in one launch (top, recurrent, bottom) */
+/* the same for up to three arrays in one launch (top, recurrent, bottom).  gate (or NULL): a device word; where it is 0
+ * the launch still sums and stores what `pend` holds as planes, and then leaves weights, momentum and aux arrays alone
+ * (rnn_amd_set_classify_steps: the reference's `if (err_sum)`, decided by the loss kernel that ran before) */
 void ramd_launch_apply_multi(ramd_stream_t st, int method, int nseg, float *const *w,
                              const float *const *delta, float *const *m, float *const *aux,
                              const size_t *n, const float *rate, float momentum,
                              float momentum_weight, const float *rate_scale_dev,
-                             const RamdPendingDelta *pend);
+                             const RamdPendingDelta *pend, const unsigned *gate);
 /* the exchange step as kernel-issued peer traffic (kernels_apply.hip: k_apply_xchg, k_xchg_barrier) */
 /* sum of word_i * (2 i + 1) mod 2^64 over the arrays in a row, on the device (kernels_apply.hip: k_replica_checksum) */
 void ramd_launch_replica_checksum(ramd_stream_t st, int n_arrays, const float *const *arrays, const size_t *n_floats,

@@ -71,6 +71,8 @@ typedef struct RamdEngine {
   size_t d_frames_bytes;
   void *d_automaton;    /* rnn_amd_set_automaton_steps's block: film, positions, offset lists, gathered rows: grown on demand */
   size_t d_automaton_bytes;
+  void *d_classify;     /* rnn_amd_set_classify_steps's block: features, targets, masks, gate words, groups, weights: grown on demand */
+  size_t d_classify_bytes;
   float *delta_own;     /* library-owned ih_delta||ho_delta                */
   int delta_external;
   /* The delta sums of the last set call, kept as the un-summed planes the GEMM left (in a workspace of their own)
@@ -216,7 +218,8 @@ const int *ramd_push_ranges(RamdEngine *e, RecurErrorRange *ranges);
 void ramd_log_bptt(RamdEngine *e, RecurNN *net, float mef_before);
 void ramd_check_method_arrays(RamdEngine *e, int method);
 int ramd_update_rule(const RecurNNBPTT *bptt, int learning_style, float momentum, float *mw, float *rate, float *ho_rate);
-void ramd_apply_learning(RecurNN *net, int learning_method, float momentum, const RamdPendingDelta *pend);
+void ramd_apply_learning(RecurNN *net, int learning_method, float momentum, const RamdPendingDelta *pend,
+                         const unsigned *gate);
 void ramd_fused_net_update(RamdEngine *e, RecurNN *net, int row, unsigned batch_size);
 
 /* texts_api.c: the refusals of rnn_amd_run_texts / _heads (alphabet_len 0: no heads), which need no device: -1 with a

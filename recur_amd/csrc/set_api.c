@@ -9,6 +9,7 @@
 #include "rnn_host.h"
 #include "parrot_rule.h"
 #include "automaton_train_rule.h"
+#include "classify_train_rule.h"
 
 RnnAmdSet *rnn_amd_set_open(RecurNN **nets, int n_nets) {
   if (!nets || n_nets < 1) {
@@ -343,10 +344,12 @@ static int kept_deltas_ok(RamdEngine *e) {
 }
 
 /* dev_ranges: one range list per stream already on the device (range_stride ints apart),
- * instead of the shared host list `ranges` */
-static void set_calc_deltas(RnnAmdSet *set, int accumulate, RecurErrorRange *ranges,
-                            const u8 *active, unsigned extra_flags, const int *dev_ranges,
-                            int range_stride, RamdPendingDelta *defer) {
+ * instead of the shared host list `ranges`.  dev_active (or NULL, with `active` only): these very flags lie on the device
+ * already (rnn_amd_set_classify_steps's per-generation masks) and the launch reads them there instead of b.active; the
+ * host copy `active` still drives the book-keeping here: the top launch's mask, the pending images, generation++ */
+static void set_calc_deltas_masked(RnnAmdSet *set, int accumulate, RecurErrorRange *ranges,
+                                   const u8 *active, const u8 *dev_active, unsigned extra_flags, const int *dev_ranges,
+                                   int range_stride, RamdPendingDelta *defer) {
   RamdEngine *e = set->eng;
   ramd_set_need_training(set, "rnn_amd_set_calc_deltas");
   if (e->deltas_zero_pending) { /* the sum into zeros is the sum */
@@ -366,7 +369,9 @@ static void set_calc_deltas(RnnAmdSet *set, int accumulate, RecurErrorRange *ran
   ramd_push_learn_rates(e, set->row0, set->n);
   const int *d_ranges = dev_ranges ? dev_ranges : ramd_push_ranges(e, ranges);
   const unsigned char *d_active = NULL;
-  if (active) {
+  if (active && dev_active) {
+    d_active = dev_active;
+  } else if (active) {
     active_mask_to_dev(e, active, set->n, 0);
     d_active = e->b.active;
   }
@@ -419,6 +424,12 @@ static void set_calc_deltas(RnnAmdSet *set, int accumulate, RecurErrorRange *ran
     ramd_pull_scalars(e, set->row0, 1);
     rnn_log_int(set->nets[0], "generation", set->nets[0]->generation);
   }
+}
+
+static void set_calc_deltas(RnnAmdSet *set, int accumulate, RecurErrorRange *ranges,
+                            const u8 *active, unsigned extra_flags, const int *dev_ranges,
+                            int range_stride, RamdPendingDelta *defer) {
+  set_calc_deltas_masked(set, accumulate, ranges, active, NULL, extra_flags, dev_ranges, range_stride, defer);
 }
 
 void rnn_amd_set_calc_deltas(RnnAmdSet *set, int accumulate, RecurErrorRange *ranges,
@@ -500,7 +511,7 @@ void rnn_amd_set_grouped_softmax_error(RnnAmdSet *set, int n_groups, const int *
   }
   ramd_mail_in_flush();
   ramd_launch_grouped_softmax_error(ramd_stream, &e->sh, &e->b, set->row0, set->n, n_groups, g.largest, g.offset, g.size,
-                                    g.targets, g.weight);
+                                    g.targets, g.weight, NULL);
   set_streams_dev_wrote(set);
 }
 
@@ -700,7 +711,7 @@ static void set_opinion_sigmoid_mse(RnnAmdSet *set, const float *inputs, int ld_
   }
   const RamdHandover left = set_forward(set, RAMD_IN_DENSE, inputs, ld_inputs, 0, NULL, advance, RAMD_FWD_FOR_DENSE_TOP);
   if (!ramd_launch_dense_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, left, targets, ld, n, 0, NULL, NULL, NULL, NULL,
-                             stats)) {
+                             stats, NULL)) {
     fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_sigmoid_mse: the top launch declined a shape it had accepted\n");
     abort();
   }
@@ -808,7 +819,7 @@ void rnn_amd_set_opinion_grouped_softmax(RnnAmdSet *set, const float *inputs, in
   active_mask_to_dev(e, trained, set->n, 1); /* (for the delta call that follows: travels with the rest) */
   const RamdHandover left = set_forward(set, RAMD_IN_DENSE, e->d_dense, s->input_size, 0, NULL, 0, RAMD_FWD_FOR_DENSE_TOP);
   if (!ramd_launch_dense_top(ramd_stream, s, &e->b, set->row0, set->n, left, NULL, 0, 0, n_groups, g.offset, g.size,
-                             g.targets, g.weight, 0)) {
+                             g.targets, g.weight, 0, NULL)) {
     fprintf(stderr, "librecur_amd: rnn_amd_set_opinion_grouped_softmax: the top launch declined a shape it had accepted\n");
     abort();
   }
@@ -968,7 +979,7 @@ static void set_step(RnnAmdSet *set, const StepSpec *sp, int learning_style, flo
       ramd_timing_end(ramd_stream, tev);
     }
   }
-  ramd_apply_learning(set->nets[0], learning_style, momentum, (pend.slab || pend.ho_slab) ? &pend : NULL);
+  ramd_apply_learning(set->nets[0], learning_style, momentum, (pend.slab || pend.ho_slab) ? &pend : NULL, NULL);
 }
 
 /* the multi-head generation as ONE call: rnn_amd_set_multi_step_deltas (accumulate 0) + rnn_apply_learning -- knowing the
@@ -1122,6 +1133,155 @@ void rnn_amd_set_automaton_steps(RnnAmdSet *set, const RnnAmdAutomaton *ca, cons
       rnn_condition_net(set->nets[0]); /* gstrnnca.c:739: behind the update */
     }
   }
+}
+
+/* gstclassify's trainer over a block of windows (maybe_learn, gstclassify.c:2180-2257; classify_train_rule.h): see
+ * recur_amd.h.  One generation from the caller's host rows, the gate decided by reading the summed error back: what the
+ * block call does where the block cannot stay on the device (a bottom layer's host copy of its inputs, noise drawn in
+ * front of every pass, an exchange or a group of ranks behind every update).  trains: room for a flag per stream */
+static void classify_generation_host(RnnAmdSet *set, const float *features, int ld, const int *targets, int n_groups,
+                                     const int *group_offset, const int *group_size, const float *error_weight,
+                                     int learning_style, float momentum_soft_start, int condition, u8 *trains) {
+  RecurNN *net = set->nets[0];
+  rnn_bptt_clear_deltas(net);
+  RnnAmdStats before, after;
+  const int together = net->presynaptic_noise == 0.0f; /* (a noisy pass draws first, as in train_channel) */
+  if (!together) {
+    rnn_amd_set_opinion(set, features, ld, NULL);
+  }
+  rnn_amd_set_read_stats(set, &before, 0);
+  if (together) {
+    rnn_amd_set_opinion_grouped_softmax(set, features, ld, n_groups, group_offset, group_size, targets, error_weight, trains);
+  } else {
+    rnn_amd_set_grouped_softmax_error(set, n_groups, group_offset, group_size, targets, error_weight, trains);
+  }
+  const int any = memchr(trains, 1, (size_t)set->n) != NULL;
+  if (any) {
+    rnn_amd_set_calc_deltas(set, 1, NULL, trains); /* adds to the cleared deltas */
+  }
+  rnn_amd_set_advance(set);
+  if (any) {
+    rnn_amd_set_read_stats(set, &after, 0);
+    if (after.error - before.error != 0.0) { /* the reference's `if (err_sum)` */
+      rnn_apply_learning(net, learning_style,
+                         rnn_calculate_momentum_soft_start(net->generation, net->bptt->momentum, momentum_soft_start));
+    }
+  }
+  if (condition) {
+    rnn_condition_net(net);
+  }
+}
+
+void rnn_amd_set_classify_steps(RnnAmdSet *set, const float *features, int ld, const int *targets, int n_steps, int n_groups,
+                                const int *group_offset, const int *group_size, const float *error_weight,
+                                int learning_style, float momentum_soft_start, int condition) {
+  if (!set) {
+    fprintf(stderr, "librecur_amd: rnn_amd_set_classify_steps without a set\n");
+    abort();
+  }
+  RamdEngine *e = set->eng;
+  ramd_set_need_training(set, "rnn_amd_set_classify_steps");
+  const int width = e->sh.bI ? e->sh.b_in : e->sh.input_size; /* (a bottom layer takes the features) */
+  const int refusal = classify_block_refusal(features != NULL, targets != NULL, n_steps, ld, width, n_groups, group_offset,
+                                             group_size, e->sh.output_size);
+  if (refusal) { /* (the rule is classify_train_rule.h's, where it is asked without a device) */
+    fprintf(stderr, "librecur_amd: rnn_amd_set_classify_steps: %s (%d steps, rows of %d for %d inputs, %d groups in %d outputs)\n",
+            classify_block_refusal_text(refusal), n_steps, ld, width, n_groups, e->sh.output_size);
+    abort();
+  }
+  RecurNN *net = set->nets[0];
+  const int n = set->n;
+  const size_t stride = classify_mask_stride(n);
+  if (e->sh.bI || net->presynaptic_noise != 0.0f || e->xchg_world || rnn_amd_dist_world() > 1) {
+    u8 *trains = ramd_zalloc(stride);
+    for (int t = 0; t < n_steps; t++) {
+      classify_generation_host(set, features + (size_t)t * n * ld, ld, targets + (size_t)t * n * n_groups, n_groups,
+                               group_offset, group_size, error_weight, learning_style, momentum_soft_start, condition, trains);
+    }
+    free(trains);
+    return;
+  }
+  /* the block: features, then -- staged on the host as one piece -- targets, masks, gate words (zero), groups, weights */
+  const size_t n_feat = (size_t)n_steps * n * ld, n_tg = (size_t)n_steps * n * n_groups;
+  const size_t n_weights = error_weight ? (size_t)e->sh.output_size : 0;
+  size_t bytes = 0;
+  const size_t at_feat = automaton_room(&bytes, n_feat * sizeof(float));
+  const size_t at_tg = automaton_room(&bytes, n_tg * sizeof(int));
+  const size_t at_masks = automaton_room(&bytes, (size_t)n_steps * stride);
+  const size_t at_gates = automaton_room(&bytes, (size_t)n_steps * sizeof(unsigned));
+  const size_t at_groups = automaton_room(&bytes, (size_t)2 * n_groups * sizeof(int));
+  const size_t at_weights = automaton_room(&bytes, n_weights * sizeof(float));
+  ramd_engine_ensure_device(e);
+  if (bytes > e->d_classify_bytes) {
+    ramd_dsync(); /* (an earlier block's generations may still be reading the old one) */
+    ramd_dev_free(e->d_classify);
+    e->d_classify = ramd_dev_alloc(bytes);
+    e->d_classify_bytes = bytes;
+  }
+  char *base = e->d_classify;
+  char *tail = ramd_zalloc(bytes - at_tg); /* (zeroed: the gate words, the masks' padding) */
+  u8 *masks = (u8 *)(tail + (at_masks - at_tg));
+  int *active = ramd_zalloc((size_t)n_steps * sizeof(int));
+  memcpy(tail, targets, n_tg * sizeof(int));
+  classify_block_decisions(targets, n_steps, n, n_groups, group_size, masks, active, NULL);
+  memcpy(tail + (at_groups - at_tg), group_offset, (size_t)n_groups * sizeof(int));
+  memcpy(tail + (at_groups - at_tg) + (size_t)n_groups * sizeof(int), group_size, (size_t)n_groups * sizeof(int));
+  if (error_weight) {
+    memcpy(tail + (at_weights - at_tg), error_weight, n_weights * sizeof(float));
+  }
+  ramd_upload_q(base + at_feat, features, n_feat * sizeof(float));
+  ramd_upload(base + at_tg, tail, bytes - at_tg);
+  const float *d_feat = (const float *)(base + at_feat);
+  const int *d_tg = (const int *)(base + at_tg);
+  const int *d_goff = (const int *)(base + at_groups), *d_gsize = d_goff + n_groups;
+  const float *d_weight = error_weight ? (const float *)(base + at_weights) : NULL;
+  unsigned *d_gates = (unsigned *)(base + at_gates);
+  int largest = 1;
+  for (int i = 0; i < n_groups; i++) {
+    largest = RAMD_MAX(largest, group_size[i]);
+  }
+  for (int t = 0; t < n_steps; t++) {
+    rnn_bptt_clear_deltas(net); /* (lazy: the delta call simply does not accumulate) */
+    const float *x = d_feat + (size_t)t * n * ld;
+    const int *gt = d_tg + (size_t)t * n * n_groups;
+    const u8 *mask = masks + (size_t)t * stride;
+    /* generation t - 1's rnn_bptt_advance rides in this forward launch; the last one's follows the loop */
+    const int advance = t > 0;
+    /* the one-launch top where rnn_amd_set_opinion_grouped_softmax takes it: its output layer sums in another order than
+     * the separate kernels', and the block keeps the bits of the loop of rnn_amd_classify_generation at every set size */
+    if (dense_top_ok(set, x) && n % 4 == 0) {
+      const RamdHandover left = set_forward(set, RAMD_IN_DENSE, x, ld, 0, NULL, advance, RAMD_FWD_FOR_DENSE_TOP);
+      if (!ramd_launch_dense_top(ramd_stream, &e->sh, &e->b, set->row0, n, left, NULL, 0, 0, n_groups, d_goff, d_gsize, gt,
+                                 d_weight, 0, d_gates + t)) {
+        fprintf(stderr, "librecur_amd: rnn_amd_set_classify_steps: the top launch declined a shape it had accepted\n");
+        abort();
+      }
+      set_streams_dev_wrote(set);
+      ramd_top_done_set(e, set->row0, n, 1);
+      if (!e->top_done_mask) {
+        e->top_done_mask = ramd_zalloc((size_t)e->sh.Scap + 4);
+      }
+      memcpy(e->top_done_mask, mask, (size_t)n);
+    } else {
+      set_forward(set, RAMD_IN_DENSE, x, ld, 0, NULL, advance, RAMD_FWD_WHOLE);
+      ramd_launch_grouped_softmax_error(ramd_stream, &e->sh, &e->b, set->row0, n, n_groups, largest, d_goff, d_gsize, gt,
+                                        d_weight, d_gates + t);
+      set_streams_dev_wrote(set);
+    }
+    if (active[t]) {
+      /* never with the delta GEMM's update epilogue: the gate needs the optimiser launch of its own */
+      set_calc_deltas_masked(set, 1, NULL, mask, (const u8 *)(base + at_masks) + (size_t)t * stride, 0, NULL, 0, NULL);
+      ramd_apply_learning(net, learning_style,
+                          rnn_calculate_momentum_soft_start(net->generation, net->bptt->momentum, momentum_soft_start), NULL,
+                          d_gates + t);
+    }
+    if (condition) {
+      rnn_condition_net(net);
+    }
+  }
+  rnn_amd_set_advance(set);
+  free(active);
+  free(tail);
 }
 
 /* The single-net text step of rnn_char_epoch (charmodel-predict.c:312-321) without a host round trip per

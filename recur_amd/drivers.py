@@ -18,7 +18,9 @@ offset pattern (rnn_amd_automaton_parse_offsets); ``dream_sequences`` runs parro
 their own answers, in one call (rnn_amd_dream_sequences); ``train_frames`` runs parrot's trainer over a block of frames,
 every frame the target of one generation and the input of the next, in one call (rnn_amd_set_dense_steps_tanh).
 ``train_automaton`` runs rnnca's trainer over a block of a film of bytes, the trainers' rows gathered on the device, in one
-call (rnn_amd_set_automaton_steps).
+call (rnn_amd_set_automaton_steps).  ``train_windows`` runs gstclassify's trainer over a block of windows of features and
+class targets, the reference's update gate decided on the device, in one call (rnn_amd_set_classify_steps, or
+rnn_amd_classify_generations with balanced training).
 ``synthetic_text_np`` is the seeded symbol stream of
 SURVEY.md section 8(d)'s data-free workload, restated in numpy (Jenkins PRNG, recur-rng.h) so that input data
 never comes out of a checker's library.
@@ -439,6 +441,38 @@ def train_automaton(lib, set_or_handle, geometry, frames, xy, advance=False, lea
     lib.rnn_amd_set_automaton_steps(handle, C.byref(g.struct), rc.u8ptr(fr), rc.iptr(pos), int(pos.ndim == 3), T,
                                     int(bool(advance)), learning_style, momentum, soft_start, int(bool(condition)))
     return T
+
+
+def train_windows(lib, set_or_handle, features, targets, group_offset, group_size, error_weight=None, balance=None,
+                  learning_style=rc.NESTEROV, soft_start=2000.0, condition=True):
+    """rnn_amd_set_classify_steps: gstclassify's trainer (maybe_learn) over a block of windows in one call.  features:
+    float32 [T][n][ld], ld >= the net's inputs; targets: int32 [T][n][G], the class of channel j in group i at window t, < 0
+    or >= the group's size for "no label"; group_offset / group_size: the G class groups' first output and size;
+    error_weight: a factor per output, or None.  Generation t clears the deltas, forms every channel's opinion of
+    features[t], the class-group loss against targets[t], the deltas of the labelled channels, advances the rings, updates
+    with the soft-started momentum if the generation's summed error is not zero (the reference's `if (err_sum)`, decided on
+    the device) and conditions the net when `condition`.  balance: a pointer from rnn_amd_balanced_new; then the call is
+    rnn_amd_classify_generations (the library bound with bind_classify), which draws every generation's balanced sample
+    ahead and always conditions.  set_or_handle: an AmdBatchedSet or an RnnAmdSet handle.  Returns the number of groups
+    trained (with balance: the library's count; otherwise counted here from the targets)."""
+    handle = getattr(set_or_handle, "handle", set_or_handle)
+    x = np.ascontiguousarray(features, dtype=np.float32)
+    tg = np.ascontiguousarray(targets, dtype=np.int32)
+    goff = np.ascontiguousarray(group_offset, dtype=np.int32)
+    gsize = np.ascontiguousarray(group_size, dtype=np.int32)
+    n = lib.rnn_amd_set_size(handle)
+    assert x.ndim == 3 and x.shape[0] >= 1 and x.shape[1] == n, "features are [T][n][ld], n the nets of the set"
+    assert goff.ndim == 1 and goff.shape == gsize.shape and len(goff) >= 1, "one offset and one size per class group"
+    assert tg.shape == (x.shape[0], n, len(goff)), "targets are [T][n][G]"
+    w = None if error_weight is None else np.ascontiguousarray(error_weight, dtype=np.float32)
+    wp = None if w is None else rc.fptr(w)
+    if balance is not None:
+        assert condition, "rnn_amd_classify_generations always conditions the net"
+        return lib.rnn_amd_classify_generations(handle, rc.fptr(x), x.shape[2], rc.iptr(tg), x.shape[0], len(goff), rc.iptr(goff),
+                                                rc.iptr(gsize), wp, balance, learning_style, soft_start)
+    lib.rnn_amd_set_classify_steps(handle, rc.fptr(x), x.shape[2], rc.iptr(tg), x.shape[0], len(goff), rc.iptr(goff),
+                                   rc.iptr(gsize), wp, learning_style, soft_start, int(bool(condition)))
+    return int(((tg >= 0) & (tg < gsize[None, None, :])).sum())
 
 
 class ApiSet:

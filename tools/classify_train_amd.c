@@ -9,9 +9,13 @@
  * windows, the 32 "log-power bins" are noise plus a class-dependent spectral tilt.  The loop is
  * rnn_amd_classify_generation, all channels per launch sequence; the net is saved under the
  * reference's file name with the reference's metadata, loaded back and checked.
+ * With -B the windows are generated a block at a time and every block is ONE call of rnn_amd_classify_generations
+ * (always the exact `if (err_sum)` gate, decided on the device): the same windows, draws and net whatever the block.
  *
  *   classify_train_amd [-H hidden] [-c channels] [-d depth] [-g generations] [-l learn_rate]
  *                      [-b balanced_bias (0 = off)] [-r report_every] [-x (exact `if (err_sum)` gate)]
+ *                      [-B block (windows per call; without it the loop of single generations)]
+ *                      [-o file (the saved net is kept there; otherwise it is removed after the check)]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -33,9 +37,10 @@ static float uniform(rand_ctx *r) { /* host-side feature noise: a generator of t
 }
 
 int main(int argc, char **argv) {
-  int hidden = 512, channels = 128, depth = 30, generations = 600, report = 100, exact = 0, opt;
+  int hidden = 512, channels = 128, depth = 30, generations = 600, report = 100, exact = 0, block = 0, opt;
+  const char *keep = NULL;
   float lr = 3e-4f, bias = 1.0f;
-  while ((opt = getopt(argc, argv, "H:c:d:g:l:b:r:x")) != -1) {
+  while ((opt = getopt(argc, argv, "H:c:d:g:l:b:r:xB:o:")) != -1) {
     switch (opt) {
     case 'H': hidden = atoi(optarg); break;
     case 'c': channels = atoi(optarg); break;
@@ -45,9 +50,16 @@ int main(int argc, char **argv) {
     case 'b': bias = atof(optarg); break;
     case 'r': report = atoi(optarg); break;
     case 'x': exact = 1; break;
+    case 'B': block = atoi(optarg); break;
+    case 'o': keep = optarg; break;
     default: fprintf(stderr, "see the head of tools/classify_train_amd.c\n"); return 2;
     }
   }
+  if (block < 0 || generations < 1 || report < 1) {
+    fprintf(stderr, "see the head of tools/classify_train_amd.c\n");
+    return 2;
+  }
+  const int per_call = block > 0 ? block : 1;
   RnnAmdClassifyMetadata md = {"01", 100.f, 1600.f, 700.f, 0, 256, "synthetic", 0, 600.f, 0.f, 0, 0.f, NULL, NULL};
   char *metadata = rnn_amd_classify_construct_metadata(&md);
   int g_off[4], g_size[4], n_outputs = 0;
@@ -62,8 +74,8 @@ int main(int argc, char **argv) {
   RnnAmdSet *set = rnn_amd_set_open(nets, channels);
   RnnAmdBalancedTraining *balance = bias > 0 ? rnn_amd_balanced_new(n_outputs, bias) : NULL;
 
-  float *features = malloc(sizeof(float) * channels * N_FEATURES);
-  int *targets = malloc(sizeof(int) * channels * n_groups), *left = calloc(channels, sizeof(int));
+  float *features = malloc(sizeof(float) * per_call * channels * N_FEATURES);
+  int *targets = malloc(sizeof(int) * per_call * channels * n_groups), *left = calloc(channels, sizeof(int));
   int *cls = calloc(channels, sizeof(int));
   rand_ctx noise = {0xf1ea5eed, 7, 7, 7};
   for (int i = 0; i < 20; i++) uniform(&noise);
@@ -72,21 +84,32 @@ int main(int argc, char **argv) {
   struct timespec t0, t1;
   clock_gettime(CLOCK_MONOTONIC, &t0);
   long trained = 0;
-  for (int g = 1; g <= generations; g++) {
-    for (int ch = 0; ch < channels; ch++) {
-      if (left[ch]-- <= 0) { /* the channel's sound changes: class 0 four times as likely as class 1 */
-        cls[ch] = uniform(&noise) < 0.2f;
-        left[ch] = 50 + (int)(150 * uniform(&noise));
-      }
-      targets[ch] = uniform(&noise) < 0.9f ? cls[ch] : -1; /* a tenth of the windows carry no label */
-      for (int k = 0; k < N_FEATURES; k++) {
-        const float tilt = cls[ch] ? (k - 16) * 0.04f : (16 - k) * 0.04f;
-        features[ch * N_FEATURES + k] = tilt + 0.6f * (uniform(&noise) + uniform(&noise) - 1.0f);
+  int reported = 0;
+  for (int g0 = 0; g0 < generations; g0 += per_call) {
+    const int windows = generations - g0 < per_call ? generations - g0 : per_call, g = g0 + windows;
+    for (int w = 0; w < windows; w++) {
+      float *x = features + (size_t)w * channels * N_FEATURES;
+      int *tg = targets + (size_t)w * channels * n_groups;
+      for (int ch = 0; ch < channels; ch++) {
+        if (left[ch]-- <= 0) { /* the channel's sound changes: class 0 four times as likely as class 1 */
+          cls[ch] = uniform(&noise) < 0.2f;
+          left[ch] = 50 + (int)(150 * uniform(&noise));
+        }
+        tg[ch] = uniform(&noise) < 0.9f ? cls[ch] : -1; /* a tenth of the windows carry no label */
+        for (int k = 0; k < N_FEATURES; k++) {
+          const float tilt = cls[ch] ? (k - 16) * 0.04f : (16 - k) * 0.04f;
+          x[ch * N_FEATURES + k] = tilt + 0.6f * (uniform(&noise) + uniform(&noise) - 1.0f);
+        }
       }
     }
-    trained += rnn_amd_classify_generation(set, features, N_FEATURES, n_groups, g_off, g_size, targets, NULL, balance,
-                                           RNN_MOMENTUM_NESTEROV, 2000.0f, exact);
-    if (g % report == 0) {
+    if (block > 0) {
+      trained += rnn_amd_classify_generations(set, features, N_FEATURES, targets, windows, n_groups, g_off, g_size, NULL,
+                                              balance, RNN_MOMENTUM_NESTEROV, 2000.0f);
+    } else {
+      trained += rnn_amd_classify_generation(set, features, N_FEATURES, n_groups, g_off, g_size, targets, NULL, balance,
+                                             RNN_MOMENTUM_NESTEROV, 2000.0f, exact);
+    }
+    if (g / report > g0 / report) { /* (a block that crosses a multiple of report_every) */
       rnn_amd_set_read_stats(set, &st, 1);
       clock_gettime(CLOCK_MONOTONIC, &t1);
       const double s = (t1.tv_sec - t0.tv_sec) + 1e-9 * (t1.tv_nsec - t0.tv_nsec);
@@ -94,16 +117,18 @@ int main(int argc, char **argv) {
       printf("generation %6d error %.4f correct %.4f trained %ld", g, st.count ? st.error / st.count : 0.0,
              st.count ? (double)st.correct / st.count : 0.0, trained);
       if (balance) printf(" seen %u/%u used %u/%u", balance->seen[0], balance->seen[1], balance->used[0], balance->used[1]);
-      printf(" %.0f channel-windows/s\n", (double)report * channels / s);
+      printf(" %.0f channel-windows/s\n", (double)(g - reported) * channels / s);
+      reported = g;
       trained = 0;
     }
   }
   /* save under the reference's name, load back, check it is the net this configuration expects */
   rnn_amd_set_close(set);
-  int rc = rnn_save_net(net, filename, 0);
-  RecurNN *back = rc == 0 ? rnn_load_net(filename) : NULL;
+  const char *saved = keep ? keep : filename;
+  int rc = rnn_save_net(net, saved, 0);
+  RecurNN *back = rc == 0 ? rnn_load_net(saved) : NULL;
   const int ok = back && rnn_amd_classify_check_net(back, metadata, hidden, 0, n_outputs, 0) == 0;
-  printf("net file %s: %s\n", filename, ok ? "saved, loaded, metadata and sizes agree" : "FAILED");
+  printf("net file %s: %s\n", saved, ok ? "saved, loaded, metadata and sizes agree" : "FAILED");
   if (back) {
     RnnAmdClassifyMetadata seen = {0};
     const int missing = rnn_amd_classify_load_metadata(back->metadata, &seen);
@@ -111,7 +136,9 @@ int main(int argc, char **argv) {
     rnn_amd_classify_free_metadata_items(&seen);
     rnn_delete_net(back);
   }
-  unlink(filename);
+  if (!keep) {
+    unlink(filename);
+  }
   rnn_amd_balanced_free(balance);
   rnn_delete_training_set(nets, channels, 0);
   free(features); free(targets); free(left); free(cls); free(metadata); free(filename);
