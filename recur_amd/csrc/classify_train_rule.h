@@ -1,6 +1,6 @@
 /* classify_train_rule.h -- what gstclassify's trainer decides per generation (maybe_learn, gstclassify.c:2180-2257, with
  * train_channel's loss 2070-2119 and the balanced-training draw 2096-2104, 2190-2215), stated once: for
- * rnn_amd_set_classify_steps (set_api.c), for rnn_amd_classify_generation and rnn_amd_classify_generations
+ * rnn_amd_set_classify_steps (set_train.c), for rnn_amd_classify_generation and rnn_amd_classify_generations
  * (classify_host.c), for the gate the loss kernels write and k_apply reads (kernels_loss.hip, kernels_apply.hip) and for any
  * host compiler alone (tests/classify_train_rule_harness.cpp runs it under g++ against numpy).  No HIP header is needed.
  *

@@ -370,15 +370,9 @@ static void engine_free_device(RamdEngine *e) {
   e->kept_live = 0;
   e->d_group = NULL;
   e->d_group_bytes = 0;
-  ramd_dev_free(e->d_frames);
-  e->d_frames = NULL;
-  e->d_frames_bytes = 0;
-  ramd_dev_free(e->d_automaton);
-  e->d_automaton = NULL;
-  e->d_automaton_bytes = 0;
-  ramd_dev_free(e->d_classify);
-  e->d_classify = NULL;
-  e->d_classify_bytes = 0;
+  ramd_dev_free(e->d_block);
+  e->d_block = NULL;
+  e->d_block_bytes = 0;
   e->d_mranges = NULL;
   e->d_mclass = NULL;
   free(e->lr_pushed);
@@ -929,4 +923,20 @@ void ramd_engine_ensure_device(RamdEngine *e) {
     ramd_priv(e->fwd[i])->dev_valid = 0;
   }
   ramd_dsync();
+}
+
+/* The trainers' block buffer (RamdEngine.d_block) has room for `bytes`: synchronised, freed and allocated anew only when
+ * it has to grow.  The three block calls share it, which is sound for the reason that one trainer reusing it between two
+ * calls is: every upload into it and every launch that reads it is ordered on ramd_stream, so a call's uploads land behind
+ * the reads of whichever call used it before; only a free needs the synchronisation (an earlier block's generations may
+ * still be reading the old buffer). */
+void *ramd_block_room(RamdEngine *e, size_t bytes) {
+  ramd_engine_ensure_device(e);
+  if (bytes > e->d_block_bytes) {
+    ramd_dsync();
+    ramd_dev_free(e->d_block);
+    e->d_block = ramd_dev_alloc(bytes);
+    e->d_block_bytes = bytes;
+  }
+  return e->d_block;
 }

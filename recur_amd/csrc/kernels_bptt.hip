@@ -202,7 +202,7 @@ extern "C" void ramd_launch_clear_deltas(ramd_stream_t st_, const RamdShape *sh,
 
 static int g_calc_wrote_images = 0;
 /* Multi-GPU: the weight-delta GEMM in two row halves, so that the sum over the ranks of the first half
- * can travel while the second half is still being multiplied (set_api.c sets the hook for the call it
+ * can travel while the second half is still being multiplied (set_train.c sets the hook for the call it
  * wants split; the launcher calls it after each half's deltas are complete in ih_delta || ho_delta,
  * with the half's range in floats from ih_delta). */
 static void (*g_delta_half_hook)(void *ctx, int half, size_t first_float, size_t n_floats) = nullptr;

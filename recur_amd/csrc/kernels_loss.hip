@@ -12,6 +12,7 @@ __device__ unsigned long long g_tt_stamps[16];
 #include "k_top.h"
 #include "fwd_plan.h"
 #include "parrot_rule.h"
+#include "sigmoid_rule.h"
 #include "classify_train_rule.h"
 BND_DECL(g_bnd_top, ramd_bnd_top_stamps)
 #pragma clang fp contract(off)
@@ -70,43 +71,31 @@ extern "C" void ramd_top_stamps(unsigned long long *out) {
   HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tt_stamps), sizeof(unsigned long long) * 16));
 }
 #endif
-/* KIND: which loss sits between the output layer and the backprop -- 0: the text model's softmax against the stream's
- * next symbol; 1: rnnca's sigmoid + squared error (k_sigmoid_mse_error's arithmetic, gstrnnca.c:701-714); 2: gstclassify's
- * class groups (k_grouped_softmax_error's, gstclassify.c:2070-2119); 3: parrot's tanh + slope error (k_tanh_mse_error's,
- * gstparrot.c:464-477, parrot_rule.h).  1 and 2 serve rnn_amd_set_opinion_sigmoid_mse / _grouped_softmax, 3 serves
- * rnn_amd_set_opinion_tanh_error: finalize + output layer + loss + top backprop of a dense-input generation in ONE launch
- * instead of four (7.4 + 12.0 + 4.9 + 9.8 us at 2048 / 512, 5.0 + 4.7 + 4.8 + 5.0 us at 512 / 128).  1 and 2 are one
- * wave's work (o_size <= 64); 3 gives every column a thread of its own (o_size <= 256: parrot's 256 bins, waves 0 .. 3). */
-struct TopLoss {
-  const float *targets; /* 1, 3: [nrows][ld] */
-  int ld, n;
-  int ngroups;          /* 2 */
-  const int *goff, *gsize, *gt;
-  const float *weight;
-  int stats;            /* 1: the row's squared error and a count into the statistics (rnn_amd_set_automaton_steps alone) */
-  unsigned *gate;       /* 2: (or NULL) the generation's gate word, raised by a trained row whose wrongness is not 0 */
+/* KIND (RamdTopLoss.kind, ramd_internal.h): which loss sits between the output layer and the backprop -- 0: the text model's
+ * softmax against the stream's next symbol; 1: rnnca's sigmoid + squared error (sigmoid_rule.h, gstrnnca.c:701-714); 2:
+ * gstclassify's class groups (k_grouped_softmax_error's, gstclassify.c:2070-2119); 3: parrot's tanh + slope error
+ * (parrot_rule.h, gstparrot.c:464-477).  1 and 3 serve the dense losses' opinion-plus-loss calls, 2 the class groups':
+ * finalize + output layer + loss + top backprop of a dense-input generation in ONE launch instead of four (7.4 + 12.0 + 4.9 +
+ * 9.8 us at 2048 / 512, 5.0 + 4.7 + 4.8 + 5.0 us at 512 / 128).  1 and 2 are one wave's work (o_size <= 64); 3 gives every
+ * column a thread of its own (o_size <= 256: parrot's 256 bins, waves 0 .. 3). */
+struct FastExpDev { /* the rules' exponential on the device */
+  __device__ __forceinline__ float operator()(float x) const { return fast_expf_dev(x); }
 };
-/* The progress figure of parrot's loss (parrot_rule.h: parrot_loss), per stream-step: a row's terms are added up by wave
- * reductions over threads 0 .. 255 (thread x brings columns x, x + 256, ...), then the four waves' sums in order 0 .. 3.
- * The order is the library's own: the figure is held to a float64 restatement, not bit for bit. */
-__device__ __forceinline__ float tanh_loss_wave_sum(float term) {
+/* The progress figure of the dense losses (parrot_loss, sigmoid_loss), per stream-generation: a row's terms are added up by
+ * wave reductions (thread x brings columns x, x + 256, ...), then the waves' sums in order 0 .. 3, and the row's sum and one
+ * count go into the set's statistics.  The order is the library's own: the figure is held to a float64 restatement, not bit
+ * for bit. */
+__device__ __forceinline__ float loss_wave_sum(float term) {
   for (int off = 32; off > 0; off >>= 1) term += __shfl_down(term, off, 64);
   return term;
 }
-__device__ __forceinline__ void tanh_loss_add_stats(const View &v, int r, const float *wsum) {
-  const float sum = ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3];
-  v.b.stat_err[r] += (double)sum;
-  v.b.stat_count[r] += 1;
-}
-/* The progress figure of rnnca's loss for rnn_amd_set_automaton_steps, per trainer-generation: the sum over the scored
- * outputs of (target - a)^2 -- the difference is the one the error is made of, its square one more rounding -- and one count.
- * The order of the sum is the library's own (wave reductions, then the waves in order): held to a float64 restatement. */
-__device__ __forceinline__ void sigmoid_loss_add_stats(const View &v, int r, float sum) {
+__device__ __forceinline__ float loss_four_waves(const float *wsum) { return ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]; }
+__device__ __forceinline__ void loss_add_stats(const View &v, int r, float sum) {
   v.b.stat_err[r] += (double)sum;
   v.b.stat_count[r] += 1;
 }
 template <int KIND>
-__global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, int fwd_ks, TopLoss tl) {
+__global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, int fwd_ks, RamdTopLoss tl) {
   extern __shared__ float tsh[];
   __shared__ float tred[16];
   __shared__ float tstat[4];
@@ -268,31 +257,29 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
     else if (seg == 1) text_count_zeros_wave(s, lane, shid, tstat);
     __syncthreads();
     if (threadIdx.x == 64) top_add_stats(v, r, tstat); /* (its loads return before the wave's backprop loads, which are issued behind them) */
-  } else if constexpr (KIND == 1) { // k_sigmoid_mse_error: sigmoid in place on the first n outputs, slope * (target - answer)
+  } else if constexpr (KIND == 1) { // sigmoid_rule.h: sigmoid in place on the first n outputs, slope * (target - answer)
     if (seg == 0) { /* (o_size <= 64: launcher) */
       float term = 0.0f;
       if (lane < s.O) {
         float oe = pad_oe; /* the rest of the error row stays what it was */
         if (lane < tl.n) {
-          const float a = 1.0f / (1.0f + fast_expf_dev(-sout[lane] * 1.0f));
+          const float a = sigmoid_answer(sout[lane], FastExpDev{});
           v.b.out[(size_t)r * s.O + lane] = a;
-          const float slope = a * (1.0f - a);
-          const float diff = mse_target - a;
-          oe = slope * diff;
+          oe = sigmoid_error(a, mse_target);
           v.b.o_error[(size_t)r * s.O + lane] = oe;
-          term = diff * diff;
+          term = sigmoid_loss(a, mse_target);
         }
         serr[lane] = oe;
       }
-      if (tl.stats) { /* (uniform over the launch) the one wave's sum, as sigmoid_loss_add_stats says */
-        term = tanh_loss_wave_sum(term);
+      if (tl.stats) { /* (uniform over the launch) the one wave's sum */
+        term = loss_wave_sum(term);
         if (lane == 0) tstat[0] = term;
       }
     }
     if (threadIdx.x == 0) trained_sh = 1;
     __syncthreads();
-    if (tl.stats && threadIdx.x == 64) sigmoid_loss_add_stats(v, r, tstat[0]); /* (beside the backprop, as the text loss's) */
-  } else if constexpr (KIND == 3) { // k_tanh_mse_error: tanh in place on the first n outputs, (1 - a a) (target - a)
+    if (tl.stats && threadIdx.x == 64) loss_add_stats(v, r, tstat[0]); /* (beside the backprop, as the text loss's) */
+  } else if constexpr (KIND == 3) { // parrot_rule.h: tanh in place on the first n outputs, (1 - a a) (target - a)
     if (seg < 4) { /* (o_size <= 256: text_top_takes) */
       const int x = threadIdx.x;
       float term = 0.0f;
@@ -307,11 +294,11 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
         }
         serr[x] = oe;
       }
-      term = tanh_loss_wave_sum(term);
+      term = loss_wave_sum(term);
       if (lane == 0) tstat[seg] = term;
     }
     __syncthreads();
-    if (threadIdx.x == 64) tanh_loss_add_stats(v, r, tstat); /* (beside the backprop, as the text loss's) */
+    if (threadIdx.x == 64) loss_add_stats(v, r, loss_four_waves(tstat)); /* (beside the backprop, as the text loss's) */
   } else { // k_grouped_softmax_error, operation for operation, the outputs from LDS
     if (seg == 0) {
       float *err = v.b.o_error + (size_t)r * s.O;
@@ -737,26 +724,38 @@ __global__ __launch_bounds__(64) void k_multi_xent_accumulate(View v, int r, int
   acc[c] += (double)capped_log2f_dev(e);
 }
 
-// rnnca's loss (gstrnnca.c:701-714, train_net): fast_sigmoid_array(answer, answer, n) IN
-// PLACE on the first n outputs (badmaths.h:33-44), then o_error[i] = a (1 - a) (target - a).
-// One thread per (stream, output); the rest of the error row stays as it was (zero).
+// rnnca's loss (gstrnnca.c:701-714, train_net; sigmoid_rule.h): fast_sigmoid_array(answer, answer, n) IN PLACE on the
+// first n outputs (badmaths.h:33-44), then o_error[i] = a (1 - a) (target - a).  The public call's kernel: one thread per
+// (stream, output); the rest of the error row stays as it was (zero); the statistics are left alone.
 __global__ void k_sigmoid_mse_error(View v, int row0, int nrows, int n, const float *targets,
                                     int ld) {
   int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nrows * n) return;
   int j = q / n, i = q - j * n, r = row0 + j;
   float *out = v.b.out + (size_t)r * v.sh.O;
-  float a = 1.0f / (1.0f + fast_expf_dev(-out[i] * 1.0f));
+  float a = sigmoid_answer(out[i], FastExpDev{});
   out[i] = a;
-  float slope = a * (1.0f - a);
-  v.b.o_error[(size_t)r * v.sh.O + i] = slope * (targets[(size_t)j * ld + i] - a);
+  v.b.o_error[(size_t)r * v.sh.O + i] = sigmoid_error(a, targets[(size_t)j * ld + i]);
 }
 
-// parrot's loss (gstparrot.c:464-477, train_net; parrot_rule.h): fast_tanhf IN PLACE on the first n outputs (tanh_opinion),
-// then o_error[i] = (1 - a a) (target - a).  One workgroup of four waves per stream, thread x taking columns x, x + 256, ...
-// at any o_size; outputs and error columns from n on stay what they were.  The row's sum of (target - a)^2 goes to the
-// set's statistics (tanh_loss_add_stats).
-__global__ __launch_bounds__(256) void k_tanh_mse_error(View v, int row0, int nrows, int n, const float *targets, int ld) {
+// A dense loss with its progress figure, a row at a time: the rule's answer IN PLACE on the first n outputs, its error into
+// o_error, the row's sum of its loss terms and one count into the set's statistics (loss_add_stats).  One workgroup of four
+// waves per stream, thread x taking columns x, x + 256, ... at any o_size; outputs and error columns from n on stay what
+// they were.  TanhLossRule: parrot's loss (gstparrot.c:464-477, train_net: fast_tanhf, (1 - a a) (target - a)).
+// SigmoidLossRule: rnnca's for rnn_amd_set_automaton_steps where the one-launch top does not take the shape --
+// k_sigmoid_mse_error's arithmetic per output, so the same bits in answers and errors.
+struct TanhLossRule {
+  static __device__ __forceinline__ float answer(float x) { return dream_tanh(x); }
+  static __device__ __forceinline__ float error(float a, float t) { return parrot_error(a, t); }
+  static __device__ __forceinline__ float loss(float a, float t) { return parrot_loss(a, t); }
+};
+struct SigmoidLossRule {
+  static __device__ __forceinline__ float answer(float x) { return sigmoid_answer(x, FastExpDev{}); }
+  static __device__ __forceinline__ float error(float a, float t) { return sigmoid_error(a, t); }
+  static __device__ __forceinline__ float loss(float a, float t) { return sigmoid_loss(a, t); }
+};
+template <class RULE>
+__global__ __launch_bounds__(256) void k_dense_loss_row(View v, int row0, int nrows, int n, const float *targets, int ld) {
   __shared__ float wsum[4];
   const int j = blockIdx.x;
   if (j >= nrows) return;
@@ -766,41 +765,15 @@ __global__ __launch_bounds__(256) void k_tanh_mse_error(View v, int row0, int nr
   float term = 0.0f;
   for (int i = threadIdx.x; i < n; i += 256) {
     const float t = targets[(size_t)j * ld + i];
-    const float a = dream_tanh(out[i]);
+    const float a = RULE::answer(out[i]);
     out[i] = a;
-    err[i] = parrot_error(a, t);
-    term += parrot_loss(a, t);
+    err[i] = RULE::error(a, t);
+    term += RULE::loss(a, t);
   }
-  term = tanh_loss_wave_sum(term);
+  term = loss_wave_sum(term);
   if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = term;
   __syncthreads();
-  if (threadIdx.x == 0) tanh_loss_add_stats(v, r, wsum);
-}
-
-// k_sigmoid_mse_error with the progress figure, for rnn_amd_set_automaton_steps where the one-launch top does not take the
-// shape: the same arithmetic per output, so the same bits in answers and errors, by one workgroup of four waves per stream
-// (thread x takes columns x, x + 256, ...), which also adds the row's sum of (target - a)^2 and a count to the statistics.
-__global__ __launch_bounds__(256) void k_sigmoid_mse_error_stats(View v, int row0, int nrows, int n, const float *targets,
-                                                                 int ld) {
-  __shared__ float wsum[4];
-  const int j = blockIdx.x;
-  if (j >= nrows) return;
-  const int r = row0 + j;
-  float *out = v.b.out + (size_t)r * v.sh.O;
-  float *err = v.b.o_error + (size_t)r * v.sh.O;
-  float term = 0.0f;
-  for (int i = threadIdx.x; i < n; i += 256) {
-    const float a = 1.0f / (1.0f + fast_expf_dev(-out[i] * 1.0f));
-    out[i] = a;
-    const float slope = a * (1.0f - a);
-    const float diff = targets[(size_t)j * ld + i] - a;
-    err[i] = slope * diff;
-    term += diff * diff;
-  }
-  term = tanh_loss_wave_sum(term);
-  if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = term;
-  __syncthreads();
-  if (threadIdx.x == 0) sigmoid_loss_add_stats(v, r, ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+  if (threadIdx.x == 0) loss_add_stats(v, r, loss_four_waves(wsum));
 }
 
 // fill_frame's fast_sigmoid_array(answer, answer, 3) (gstrnnca.c:813-814) for state rows
@@ -809,7 +782,7 @@ __global__ void k_sigmoid_outputs(View v, int r0, int nrows, int n) {
   if (q >= nrows * n) return;
   int j = q / n, i = q - j * n;
   float *out = v.b.out + (size_t)(r0 + j) * v.sh.O;
-  out[i] = 1.0f / (1.0f + fast_expf_dev(-out[i] * 1.0f));
+  out[i] = sigmoid_answer(out[i], FastExpDev{});
 }
 
 #pragma clang fp contract(fast)
@@ -833,49 +806,36 @@ extern "C" void ramd_launch_text_top(ramd_stream_t st_, const RamdShape *sh, con
     return;
   }
   size_t shm = (size_t)(sh->H + OUT_SEGS * 64 * 4 + (OUT_SEGS + 3) * sh->O) * sizeof(float);
-  RAMD_LAUNCH(k_text_top<0>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, TopLoss{});
+  RAMD_LAUNCH(k_text_top<0>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, RamdTopLoss{});
 }
 
-/* the same launch with rnnca's loss (targets [nrows][ld] on the device, the first n outputs) or gstclassify's class groups
- * (ngroups > 0: offsets, sizes, targets [nrows][ngroups], per-output weights or NULL) between the output layer and the
- * backprop; returns 0 when the shape is not the kernel's kind (o_size > 64) and nothing was launched */
-/* the launch below takes the shape (and its switch is on): callers decide on the two-call form UP FRONT with this -- by the
- * time the launch could decline, the forward pass has run for it (hidden sums only) and cannot be redone */
-extern "C" int ramd_dense_top_ok(const RamdShape *sh) {
-  return ramd_text_top_ok(sh) && sh->O <= 64 && env_int("RECUR_AMD_DENSE_TOP", 1);
+/* the same launch with one of the other losses between the output layer and the backprop (RamdTopLoss, ramd_internal.h).
+ * ramd_dense_top_ok: the launch takes the shape for this kind (and its switch is on) -- callers decide on the two-call form
+ * UP FRONT with this: by the time the launch could decline (0, nothing launched), the forward pass has run for it (hidden
+ * sums only) and cannot be redone.  Rnnca's loss and the class groups are one wave's work (o_size <= 64); parrot's has a
+ * thread per column, so any o_size the text top takes. */
+extern "C" int ramd_dense_top_ok(const RamdShape *sh, int kind) {
+  return ramd_text_top_ok(sh) && (kind == RAMD_TOP_TANH_SLOPE || sh->O <= 64) && env_int("RECUR_AMD_DENSE_TOP", 1);
 }
 
 extern "C" int ramd_launch_dense_top(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
-                                     RamdHandover left, const float *targets, int ld, int n, int ngroups, const int *goff,
-                                     const int *gsize, const int *gt, const float *weight, int stats, unsigned *gate) {
-  if (!ramd_dense_top_ok(sh)) return 0;
+                                     RamdHandover left, const RamdTopLoss *loss) {
+  if (!ramd_dense_top_ok(sh, loss->kind)) return 0;
   const int fwd_ks = handover_fwd_ks(left);
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
   size_t shm = (size_t)(sh->H + OUT_SEGS * 64 * 4 + (OUT_SEGS + 3) * sh->O) * sizeof(float);
-  TopLoss tl = {targets, ld, n, ngroups, goff, gsize, gt, weight, ngroups > 0 ? 0 : stats, ngroups > 0 ? gate : nullptr};
-  if (ngroups > 0)
-    RAMD_LAUNCH(k_text_top<2>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
+  RamdTopLoss tl = *loss; /* (stats and gate only for the kinds that own them) */
+  if (tl.kind != RAMD_TOP_SIGMOID_MSE) tl.stats = 0;
+  if (tl.kind != RAMD_TOP_CLASS_GROUPS) tl.gate = nullptr;
+  if (tl.kind == RAMD_TOP_SIGMOID_MSE)
+    RAMD_LAUNCH(k_text_top<RAMD_TOP_SIGMOID_MSE>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
+  else if (tl.kind == RAMD_TOP_CLASS_GROUPS)
+    RAMD_LAUNCH(k_text_top<RAMD_TOP_CLASS_GROUPS>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
+  else if (tl.kind == RAMD_TOP_TANH_SLOPE)
+    RAMD_LAUNCH(k_text_top<RAMD_TOP_TANH_SLOPE>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
   else
-    RAMD_LAUNCH(k_text_top<1>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
-  return 1;
-}
-
-/* the same launch with parrot's loss (k_text_top<3>): every column of up to 256 has a thread, so no o_size <= 64 cap; the
- * switch is the dense top's own */
-extern "C" int ramd_dense_top_tanh_ok(const RamdShape *sh) {
-  return ramd_text_top_ok(sh) && env_int("RECUR_AMD_DENSE_TOP", 1);
-}
-
-extern "C" int ramd_launch_dense_top_tanh(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
-                                          RamdHandover left, const float *targets, int ld, int n) {
-  if (!ramd_dense_top_tanh_ok(sh)) return 0;
-  const int fwd_ks = handover_fwd_ks(left);
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  size_t shm = (size_t)(sh->H + OUT_SEGS * 64 * 4 + (OUT_SEGS + 3) * sh->O) * sizeof(float);
-  TopLoss tl = {targets, ld, n, 0, NULL, NULL, NULL, NULL, 0, nullptr};
-  RAMD_LAUNCH(k_text_top<3>, dim3(nrows), dim3(1024), shm, st, v, row0, nrows, fwd_ks, tl);
+    return 0;
   return 1;
 }
 
@@ -904,24 +864,16 @@ extern "C" void ramd_launch_multi_xent_accumulate(ramd_stream_t st_, const RamdS
               v, row, alphabet_len, acc, count_it);
 }
 
-extern "C" void ramd_launch_sigmoid_mse_error(ramd_stream_t st_, const RamdShape *sh,
-                                              const RamdBuffers *b, int row0, int nrows, int n,
-                                              const float *targets, int ld, int stats) {
+extern "C" void ramd_launch_dense_loss(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
+                                       int kind, int n, const float *targets, int ld, int stats) {
   hipStream_t st = (hipStream_t)st_;
   View v = make_view(sh, b);
-  if (stats) {
-    RAMD_LAUNCH(k_sigmoid_mse_error_stats, dim3(nrows), dim3(256), 0, st, v, row0, nrows, n, targets, ld);
-    return;
-  }
-  RAMD_LAUNCH(k_sigmoid_mse_error, dim3((nrows * n + 255) / 256), dim3(256), 0, st, v, row0, nrows, n,
-              targets, ld);
-}
-
-extern "C" void ramd_launch_tanh_mse_error(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
-                                           int n, const float *targets, int ld) {
-  hipStream_t st = (hipStream_t)st_;
-  View v = make_view(sh, b);
-  RAMD_LAUNCH(k_tanh_mse_error, dim3(nrows), dim3(256), 0, st, v, row0, nrows, n, targets, ld);
+  if (kind == RAMD_TOP_TANH_SLOPE)
+    RAMD_LAUNCH(k_dense_loss_row<TanhLossRule>, dim3(nrows), dim3(256), 0, st, v, row0, nrows, n, targets, ld);
+  else if (stats)
+    RAMD_LAUNCH(k_dense_loss_row<SigmoidLossRule>, dim3(nrows), dim3(256), 0, st, v, row0, nrows, n, targets, ld);
+  else
+    RAMD_LAUNCH(k_sigmoid_mse_error, dim3((nrows * n + 255) / 256), dim3(256), 0, st, v, row0, nrows, n, targets, ld);
 }
 
 extern "C" void ramd_launch_sigmoid_outputs(ramd_stream_t st_, const RamdShape *sh,

@@ -1,7 +1,7 @@
 /* net_api.c -- the reference's RecurNN API for one net (recur-nn.h:269-334; behaviour of recur-nn.c and
  * recur-nn-init.c; gnu11 C) on top of engine.c and the HIP kernels in kernels_*.hip: construction, clones and training
  * sets, rnn_opinion, rnn_bptt_*, rnn_apply_learning with the one statement of the update rule, conditioning, logging,
- * a text through one net.  What set_api.c's batched calls share with these lives here too. */
+ * a text through one net.  What the batched calls (set_api.c, set_loss.c, set_train.c) share with these lives here too. */
 #define RAMD_HIP_HOST 1
 #include "rnn_host.h"
 

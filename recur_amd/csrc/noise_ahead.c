@@ -13,7 +13,7 @@
  *
  * WHETHER a pass may do that, and what an offer launches into which slot from where, is noise_ahead.h's, asked on
  * RamdEngine.ahead.  Here is the host's share and all of it: the side stream, the slots' device buffers, the events and
- * the launches (set_api.c has the call sites, engine.c the two releases). */
+ * the launches (set_api.c, set_loss.c and set_train.c have the call sites, engine.c the two releases). */
 #define RAMD_HIP_HOST 1
 #include "rnn_host.h"
 

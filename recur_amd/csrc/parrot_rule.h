@@ -1,5 +1,6 @@
-/* parrot_rule.h -- the loss of parrot's trainer (train_net, gstparrot.c:464-477), stated once: for k_tanh_mse_error and
- * k_text_top<3> (kernels_loss.hip) and for any host compiler alone (tests/parrot_rule_harness.cpp runs it under g++
+/* parrot_rule.h -- the loss of parrot's trainer (train_net, gstparrot.c:464-477), stated once: for
+ * k_dense_loss_row<TanhLossRule> and k_text_top<3> (kernels_loss.hip) and for any host compiler alone
+ * (tests/parrot_rule_harness.cpp runs it under g++
  * against numpy).  No HIP header is needed: under hipcc the functions are host and device functions, elsewhere plain
  * inline ones.  The answer itself is dream_rule.h's dream_tanh (fast_tanhf), which the player uses too.
  *

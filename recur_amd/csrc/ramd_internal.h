@@ -1,5 +1,5 @@
 /* ramd_internal.h -- private interface between the gnu11 C host code
- * (engine.c, net_api.c, set_api.c, noise_ahead.c, exchange.c, rnn_init.c, rnn_io.c) and the
+ * (engine.c, net_api.c, set_api.c, set_loss.c, set_train.c, noise_ahead.c, exchange.c, rnn_init.c, rnn_io.c) and the
  * HIP kernels and their launchers (kernels_*.hip).
  *
  * The C side owns residency, coherence and call order: what lives where, when
@@ -165,7 +165,7 @@ typedef struct RamdHandover {
 } RamdHandover;
 /* The pass: fwd_plan.h says which kernels, this enqueues them.  `seam` (or NULL) is called with `ctx` between the
  * hidden layer's end and the output layer where the hidden layer was the fused launch with its own finishing kernel,
- * and nowhere else (set_api.c: the multi-head step offers the next pass's noise to noise_ahead.c there). */
+ * and nowhere else (set_loss.c: the multi-head step offers the next pass's noise to noise_ahead.c there). */
 RamdHandover ramd_launch_forward(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdFwdCall *call,
                                  void (*seam)(void *ctx), void *ctx);
 /* the bottom layer's share of rnn_bptt_calc_deltas (recur-nn.c:377-382, 750-757) for
@@ -196,22 +196,35 @@ void ramd_launch_bottom_deltas(ramd_stream_t st, const RamdShape *sh, RamdBuffer
 #define RAMD_HEADBITS_AT 130
 #define RAMD_MULTI_RANGE_STRIDE 132
 int ramd_text_top_ok(const RamdShape *sh);
-int ramd_dense_top_ok(const RamdShape *sh); /* ramd_launch_dense_top will take the shape (O <= 64, RECUR_AMD_DENSE_TOP) */
 void ramd_launch_text_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0,
                           int nrows, RamdHandover left);
-/* the same launch with rnnca's loss (targets [nrows][ld] on the device, first n outputs; ngroups == 0) or gstclassify's
- * class groups between output layer and backprop; 0: not this kernel's shape, nothing launched.  stats (rnnca's loss only,
- * rnn_amd_set_automaton_steps alone): the row's sum of (target - a)^2 and one count into the statistics.  gate (the class
- * groups only, rnn_amd_set_classify_steps alone; or NULL): a device word that a trained row whose summed wrongness is not
- * 0.0f sets to 1 (classify_train_rule.h) */
+/* The same launch with another loss between the output layer and the backprop, handed one struct as the batched rows'
+ * launches below are: the host fills it, the launcher checks it, the kernel (k_text_top<kind>) takes it by value.
+ *   RAMD_TOP_SIGMOID_MSE   rnnca's loss (sigmoid_rule.h): targets [nrows][ld] on the device, the first n outputs.  stats
+ *                          (rnn_amd_set_automaton_steps alone): the row's sum of (target - a)^2 and one count into the
+ *                          statistics
+ *   RAMD_TOP_CLASS_GROUPS  gstclassify's class groups: offsets, sizes, targets gt [nrows][ngroups], per-output weights or
+ *                          NULL.  gate (rnn_amd_set_classify_steps alone; or NULL): a device word that a trained row whose
+ *                          summed wrongness is not 0.0f sets to 1 (classify_train_rule.h)
+ *   RAMD_TOP_TANH_SLOPE    parrot's loss (parrot_rule.h): targets as rnnca's; tanh in place on the first n outputs, (1 - a a)
+ *                          (target - a), the row's squared error into the statistics
+ * stats and gate are ignored for the kinds that do not own them.  ramd_dense_top_ok(sh, kind): the launch will take the shape
+ * (the text top's; O <= 64 for the one-wave kinds 1 and 2; the RECUR_AMD_DENSE_TOP switch); the launch returns 0 where it
+ * does not, and nothing was launched. */
+enum { RAMD_TOP_TEXT = 0, RAMD_TOP_SIGMOID_MSE = 1, RAMD_TOP_CLASS_GROUPS = 2, RAMD_TOP_TANH_SLOPE = 3 };
+typedef struct RamdTopLoss {
+  const float *targets; /* 1, 3: [nrows][ld] */
+  int ld, n;
+  int ngroups;          /* 2 */
+  const int *goff, *gsize, *gt;
+  const float *weight;
+  int stats;            /* 1 */
+  int kind;             /* RAMD_TOP_* */
+  unsigned *gate;       /* 2 */
+} RamdTopLoss;
+int ramd_dense_top_ok(const RamdShape *sh, int kind);
 int ramd_launch_dense_top(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, RamdHandover left,
-                          const float *targets, int ld, int n, int ngroups, const int *goff, const int *gsize, const int *gt,
-                          const float *weight, int stats, unsigned *gate);
-/* the same launch with parrot's loss (k_text_top<3>: tanh in place on the first n outputs, (1 - a a) (target - a), the
- * row's squared error into the statistics); a thread per column, so any o_size the text top takes (<= 256) */
-int ramd_dense_top_tanh_ok(const RamdShape *sh); /* (ramd_text_top_ok, RECUR_AMD_DENSE_TOP) */
-int ramd_launch_dense_top_tanh(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows,
-                               RamdHandover left, const float *targets, int ld, int n);
+                          const RamdTopLoss *loss);
 /* o_error = onehot(target) - softmax(out) and statistics
  * (charmodel-predict.c:18-27, 299-304) */
 void ramd_launch_softmax_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
@@ -339,7 +352,7 @@ void ramd_launch_classify_step(ramd_stream_t st, const RamdShape *sh, const Ramd
 struct RamdAutomatonStep;
 void ramd_launch_automaton_step(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
                                 const struct RamdAutomatonStep *p);
-/* rnn_amd_set_automaton_steps (set_api.c): the one gather launch of a block (kernels_automaton_train.hip).
+/* rnn_amd_set_automaton_steps (set_train.c): the one gather launch of a block (kernels_automaton_train.hip).
  * RamdAutomatonTrainRows and its contract stand in automaton_train_rule.h, next to the rule it embeds */
 struct RamdAutomatonTrainRows;
 void ramd_launch_automaton_train_rows(ramd_stream_t st, const struct RamdAutomatonTrainRows *p);
@@ -402,15 +415,12 @@ typedef struct RamdTextsContinue {
   int rows;                      /* the launch's rows (the launcher's: a workgroup each) */
 } RamdTextsContinue;
 void ramd_launch_texts_continue(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, const RamdTextsContinue *p);
-/* rnnca's loss (gstrnnca.c:701-714): sigmoid in place on the first n outputs, slope * (target -
- * a) into o_error; targets is a device array [nrows][ld].  stats: the same answers and errors from the variant that also
- * adds the row's sum of (target - a)^2 and one count to the statistics (rnn_amd_set_automaton_steps alone) */
-void ramd_launch_sigmoid_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b,
-                                   int row0, int nrows, int n, const float *targets, int ld, int stats);
-/* parrot's loss (gstparrot.c:464-477, parrot_rule.h): fast_tanhf in place on the first n outputs, (1 - a a) (target - a)
- * into o_error, the row's sum of (target - a)^2 and one count into the statistics; targets is a device array [nrows][ld] */
-void ramd_launch_tanh_mse_error(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, int n,
-                                const float *targets, int ld);
+/* a dense loss behind a finished pass, kind RAMD_TOP_SIGMOID_MSE or RAMD_TOP_TANH_SLOPE as above: the rule's answer in
+ * place on the first n outputs, its error into o_error; targets is a device array [nrows][ld].  Parrot's always adds the
+ * row's sum of (target - a)^2 and one count to the statistics; rnnca's only with stats (rnn_amd_set_automaton_steps alone:
+ * the same answers and errors from the row kernel instead of the public call's thread per output) */
+void ramd_launch_dense_loss(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int row0, int nrows, int kind, int n,
+                            const float *targets, int ld, int stats);
 /* fast_sigmoid_array in place on the first n outputs of state rows r0 .. r0 + nrows */
 void ramd_launch_sigmoid_outputs(ramd_stream_t st, const RamdShape *sh, const RamdBuffers *b, int r0,
                                  int nrows, int n);

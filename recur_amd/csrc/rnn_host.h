@@ -67,12 +67,11 @@ typedef struct RamdEngine {
   void *d_group;        /* staging of the class-group loss: offsets, sizes, targets, weights */
   size_t d_group_bytes;
   float *d_dense;       /* staging for dense inputs, [Scap+Fcap][input_size] */
-  float *d_frames;      /* rnn_amd_set_dense_steps_tanh's block of frames, [n_steps + 1][n_nets][ld]: grown on demand */
-  size_t d_frames_bytes;
-  void *d_automaton;    /* rnn_amd_set_automaton_steps's block: film, positions, offset lists, gathered rows: grown on demand */
-  size_t d_automaton_bytes;
-  void *d_classify;     /* rnn_amd_set_classify_steps's block: features, targets, masks, gate words, groups, weights: grown on demand */
-  size_t d_classify_bytes;
+  /* the block a many-generation trainer call keeps on the device (rnn_amd_set_dense_steps_tanh's frames,
+   * rnn_amd_set_automaton_steps's film and gathered rows, rnn_amd_set_classify_steps's windows): ONE buffer for all of
+   * them, grown on demand (ramd_block_room) */
+  void *d_block;
+  size_t d_block_bytes;
   float *delta_own;     /* library-owned ih_delta||ho_delta                */
   int delta_external;
   /* The delta sums of the last set call, kept as the un-summed planes the GEMM left (in a workspace of their own)
@@ -149,8 +148,8 @@ static inline void ramd_top_done_set(RamdEngine *e, int row0, int n, int masked)
   e->top_done_masked = masked;
 }
 
-/* The host files that call the HIP runtime themselves (engine.c, net_api.c, set_api.c, noise_ahead.c, exchange.c) define
- * RAMD_HIP_HOST before they include this header. */
+/* The host files that call the HIP runtime themselves (engine.c, net_api.c, set_api.c, set_loss.c, set_train.c,
+ * noise_ahead.c, exchange.c) define RAMD_HIP_HOST before they include this header. */
 #ifdef RAMD_HIP_HOST
 #define __HIP_PLATFORM_AMD__ 1
 #include <hip/hip_runtime_api.h>
@@ -207,6 +206,13 @@ void ramd_need_host(RecurNN *net, int what);
 void ramd_host_wrote(RecurNN *net, int what);
 void ramd_rng_to_host(RecurNN *net);
 void ramd_rng_from_host(RecurNN *net);
+void *ramd_block_room(RamdEngine *e, size_t bytes);
+/* carving such a block into pieces: the offset of `bytes` more behind *at, which moves on to the next 256-byte boundary */
+static inline size_t ramd_block_carve(size_t *at, size_t bytes) {
+  const size_t here = *at;
+  *at = (here + bytes + 255) & ~(size_t)255;
+  return here;
+}
 
 /* net_api.c: what the batched calls share with the per-net calls */
 void ramd_host_advance(RecurNN *net);
@@ -267,7 +273,7 @@ void ramd_rows_states_out(const RamdRows *rows, int n, float *dst);
 /* the forward pass of the call's first nrows rows, whose input rows the launch before has built */
 void ramd_rows_forward(const RamdRows *rows, int nrows);
 
-/* set_api.c */
+/* set_api.c (what set_api.c, set_loss.c and set_train.c share among themselves: set_internal.h) */
 void ramd_set_need_training(const RnnAmdSet *set, const char *what);
 
 /* noise_ahead.c: the presynaptic noise of the next forward pass, generated ahead on the side stream (the decisions are
@@ -282,7 +288,7 @@ void ramd_noise_ahead_offer(RnnAmdSet *set, int loss_classes);
 void ramd_noise_ahead_free_device(RamdEngine *e); /* with the device image: the slots' buffers */
 void ramd_noise_ahead_destroy(RamdEngine *e);     /* with the engine: the events */
 
-/* exchange.c: the all-reduce overlapped with the weight-delta GEMM, for set_step (set_api.c) */
+/* exchange.c: the all-reduce overlapped with the weight-delta GEMM, for set_step (set_train.c) */
 void ramd_delta_half_ready(void *ctx, int half, size_t first_float, size_t n_floats);
 extern int ramd_halves_seen; /* bit h: half h's sum is on its way */
 

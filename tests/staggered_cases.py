@@ -158,7 +158,7 @@ CASES = {
         dict(ks=4, nkt=4, input="assemble", end="finalize", output="gemm", o_nkt=3, o_ks=3),
         calc_args=dict(flags=0), fwd_args=dict(want=0)),
     # 5 heads of 10 symbols on 40 hidden units, 6 streams: I = 52, H = 44, O = 52.  Heads narrower than 24 columns are plain
-    # per-stream ranges (set_api.c: multi_calc_deltas): the ranged top backprop with min(16, 256 / 6) partial sums per
+    # per-stream ranges (set_loss.c: multi_calc_deltas): the ranged top backprop with min(16, 256 / 6) partial sums per
     # stream and, ranges given, the top layer's own summed GEMM.  No update is announced: the planes go to the set's own
     # workspace (8 I H + 64 x 128 H floats).  calc: nkt = 6, one tile: 6 / k + 0.15 k falls to k = 6.  fwd: nkt = 2 -> 2
     "multi_head": _case(

@@ -9,7 +9,8 @@ tools/classify_train_amd -B.
      the delta arrays hold the loop's sums -- once at a shape whose delta call leaves planes (asked of calc_plan.h);
   3. one block from the device's state against the oracle twin at the bar, `correct` and `count` exact;
   4. a net outside the set is left alone and the deferred state after the call is the loop's;
-  5. tools/classify_train_amd -B 1 and -B 16 write the same net, byte for byte.
+  5. tools/classify_train_amd -B 1 and -B 16 write the same net, byte for byte;
+  6. the block buffer the three block trainers share on an engine: parrot's block, a larger block of windows, parrot's again.
 tests/test_classify_train_cases_cpu.py shows on the oracle alone that these cases can notice a failure."""
 import os
 import subprocess
@@ -22,7 +23,7 @@ import recur_ctypes as rc
 import replay
 import scenarios as sc
 import test_calc_plan as calc
-from recur_amd.drivers import train_windows
+from recur_amd.drivers import train_frames, train_windows
 from test_gpu_callers import _same_mask, _sync_oracle_to
 
 pytestmark = pytest.mark.gpu
@@ -322,3 +323,43 @@ def test_the_tool_writes_the_same_net_whatever_the_block(amd, tmp_path):
         with open(path, "rb") as f:
             nets.append(f.read())
     assert len(nets[0]) > 1000 and nets[0] == nets[1]
+
+
+# ------------------------------------------------------------------ 6. the shared block buffer --
+
+def test_the_block_trainers_share_one_buffer(amd):
+    """One engine (hidden 24, 4 streams, depth 3) takes a parrot block of 2 steps (rnn_amd_set_dense_steps_tanh), then a
+    block of 3 windows that is larger, so that the engine's one block buffer grows under it, then the parrot block again,
+    which finds the grown buffer holding the windows.  Each call's result equals the same call made on a fresh engine whose
+    buffer it is the first to touch -- brought to the same state by the per-generation loops, which the tests above and
+    test_gpu_parrot_training.py hold to the blocks bit for bit and which use no block buffer -- in every array of the
+    snapshot (weights, momentums, deltas, ...) and in the statistics."""
+    lib, groups, n = amd, cc.GAP, 4
+    kw = set_kw(n, 24, 3, groups)
+    frames = np.ascontiguousarray(np.random.default_rng(91).uniform(-1, 1, (3, n, N_IN)).astype(F))
+    x, tg = cc.block_of(3, n, N_IN, groups, 92)
+    assert frames.nbytes < x.nbytes + tg.nbytes, "the block of windows is the larger one"
+    width = groups[2]
+
+    def parrot_loop(gs):
+        for t in range(len(frames) - 1):
+            a, b = np.ascontiguousarray(frames[t]), np.ascontiguousarray(frames[t + 1])
+            lib.rnn_amd_set_dense_step_tanh(gs.handle, rc.fptr(a), a.shape[1], rc.fptr(b), b.shape[1], width, rc.WEIGHTED, 0.95)
+
+    shared, fresh1, fresh2, fresh3 = twins(lib, kw, 4)
+    train_frames(lib, shared, frames, width)
+    train_frames(lib, fresh1, frames, width)
+    hold_twins(shared, fresh1, "parrot's block, the buffer's first use")
+    train_windows(lib, shared, x, tg, groups[0], groups[1])
+    parrot_loop(fresh2)
+    train_windows(lib, fresh2, x, tg, groups[0], groups[1])
+    hold_twins(shared, fresh2, "the windows, in the buffer they grew")
+    train_frames(lib, shared, frames, width)
+    parrot_loop(fresh3)
+    cc.run_loop(lib, fresh3, x, tg, groups)
+    train_frames(lib, fresh3, frames, width)
+    snap = hold_twins(shared, fresh3, "parrot's block again, in the windows' buffer")
+    assert shared.stats().count > 0 and np.abs(snap["ih_delta"]).max() > 0
+    for gs in (shared, fresh1, fresh2, fresh3):
+        gs.close()
+

@@ -1,5 +1,5 @@
 """Parrot's trainer on the device (gstparrot.c: train_net 464-477, maybe_learn 487-554): rnn_amd_set_tanh_error
-(k_tanh_mse_error), rnn_amd_set_opinion_tanh_error (k_text_top<3>), rnn_amd_set_dense_step_tanh and
+(k_dense_loss_row<TanhLossRule>), rnn_amd_set_opinion_tanh_error (k_text_top<3>), rnn_amd_set_dense_step_tanh and
 rnn_amd_set_dense_steps_tanh, and tools/parrot_train_amd.
 
   1. the separate kernel against the numpy rule (tests/parrot_cases.py) on the fetched raw answers, bit for bit, and on a

@@ -29,7 +29,7 @@ entries the second run should have KEPT had never been written, and the device s
 run: stale images zeroed, the wrong settlement the ranged scripts were written for, found where there are no ranges.
 Nothing computes with those entries; a caller who reads bptt->h_error sees them.  Fixed in bptt_control_wave (k_extras.h):
 a run of two or more steps leaves h_error's entries from h_size on at once (one row's input columns from the extras plane
-stale_plane(n); k_bptt_small writes its images itself), and in set_calc_deltas (set_api.c): a masked call that leaves a
+stale_plane(n); k_bptt_small writes its images itself), and in ramd_set_calc_deltas (set_api.c): a masked call that leaves a
 stream out, whose images are to stay WHOLE, rebuilds the pending images first (masked_twice, the ragged net under the
 walking mask, was added to the catalogue with it).  Second run: every script and the child equal.
 """

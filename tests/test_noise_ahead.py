@@ -1,5 +1,5 @@
 """Whether a forward pass may take the presynaptic noise that was generated ahead of it, asked of the rule itself
-(recur_amd/csrc/noise_ahead.h, what noise_ahead.c, set_api.c and engine.c ask) without a GPU: noise_ahead_harness.cpp is
+(recur_amd/csrc/noise_ahead.h, what noise_ahead.c, the set API's files and engine.c ask) without a GPU: noise_ahead_harness.cpp is
 compiled with g++ alone, is fed events and prints the rule's answer to each.
 
 The rule counts the events that move a generator and compares counts.  The model it is held to here compares HISTORIES:
@@ -11,7 +11,7 @@ stream's work); a launch from a slot's states starts at what that slot holds whe
 the classes on the device cause, or with `skip` draws per stream, added.  A pass may adopt a slot only if its start IS the
 true history, for the pass's rows and level.
 
-What the model takes from the callers (set_api.c) rather than from the rule: an offer between a pass and its loss is
+What the model takes from the callers (set_loss.c, set_train.c) rather than from the rule: an offer between a pass and its loss is
 followed by that loss, of that many heads, with no upload in between -- both are one call (rnn_amd_set_multi_step_deltas);
 the sets of one engine that train with classes are equally wide here and the classes on the device are those of the last
 upload, the engine's one in-range flag being what the rule keeps; and a class is in range, or stray, for either head count.
@@ -47,7 +47,7 @@ def test_the_header_is_plain_c_and_cxx_without_hip():
     subprocess.run(["g++", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-I", CSRC, "-x", "c++",
                     os.path.join(CSRC, "noise_ahead.h")], check=True)
     subprocess.run(["gcc", "-std=gnu11", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-I", CSRC, "-x", "c",
-                    os.path.join(CSRC, "noise_ahead.h")], check=True)   # (noise_ahead.c, set_api.c and engine.c are C)
+                    os.path.join(CSRC, "noise_ahead.h")], check=True)   # (noise_ahead.c, the set API's files and engine.c are C)
 
 
 class Rule:
@@ -186,7 +186,7 @@ class Rule:
         self.hist += (("loss", self.draws(heads)),)
         return ans["dropped"]
 
-    # ---- the callers' sequences (set_api.c) ----
+    # ---- the callers' sequences (set_loss.c, set_train.c) ----
     def text_step(self, rows, level):
         """char_step_deltas: the pass, then the offer -- no draws between this pass's noise and the next one's"""
         took = self.forward(rows, level)

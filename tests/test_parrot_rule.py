@@ -111,5 +111,5 @@ def test_which_blocks_of_frames_the_many_step_call_takes(harness):
     assert ask(ld=255) == (4, "rows too short for a frame") and ask(input_size=8, n=3, output_size=5, ld=7)[0] == 4
     assert ask(input_size=2, n=5, output_size=5, ld=4)[0] == 4 and ask(ld=0)[0] == 4
     # ... and the call refuses by this rule, not by a restatement of it
-    text = open(os.path.join(dc.CSRC, "set_api.c")).read()
+    text = open(os.path.join(dc.CSRC, "set_train.c")).read()
     assert "parrot_block_refusal(frames != NULL, n_steps, ld, e->sh.input_size, n, e->sh.output_size)" in text
