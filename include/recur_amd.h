@@ -1119,6 +1119,9 @@ void rnn_amd_synchronize(void);
  * arrivals and sharded update: what a rank waits and works for between its deltas and its next forward pass). */
 void rnn_amd_kernel_time_enable(int enable);
 double rnn_amd_kernel_time_ms(int which, long *launches, int reset);
+/* How many text steps of this process took the forward pass and the top layer as ONE launch (the north star's shape;
+ * RECUR_AMD_FWD_TOP=0 for the two launches): for tests that compare the two forms. */
+long rnn_amd_fwd_top_launches(void);
 
 #ifdef __cplusplus
 }

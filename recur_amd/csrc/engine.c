@@ -61,6 +61,7 @@ void rnn_amd_synchronize(void) {
   }
 }
 void rnn_amd_kernel_time_enable(int enable) { ramd_timing_enable(enable); }
+long rnn_amd_fwd_top_launches(void) { return ramd_fwd_top_launches(); }
 double rnn_amd_kernel_time_ms(int which, long *launches, int reset) {
   return ramd_timing_ms(which, launches, reset);
 }
@@ -117,6 +118,10 @@ void ramd_dsync(void) {
     if (code == 6) {
       fprintf(stderr, "librecur_amd: a rank waited its time out (20 s; RECUR_AMD_XCHG_BARRIER_TIMEOUT_S) at a barrier of the kernel-issued exchange: not every rank "
                       "reached it (did one die, or drive fewer generations?); the replicas are out of step.\n");
+    } else if (code == 7) {
+      fprintf(stderr, "librecur_amd: the text step's forward + top launch gave up (code 7: its 256 workgroups were not all "
+                      "resident, one per CU, or a hand-off timed out); its results are invalid.  Set RECUR_AMD_FWD_TOP=0 "
+                      "(the two launches).\n");
     } else if (code == 2) {
       fprintf(stderr, "librecur_amd: a workgroup of the one-launch BPTT chain was not on the XCD its number implies (code 2): "
                       "something else ran on this GPU beside the chain and the dispatcher interleaved the two launches; "

@@ -17,6 +17,9 @@ constexpr int OUT_SEGS = 16;    /* segments of the hidden row in the output-laye
 constexpr int WM = 64, WN = 64, WK = 64, W_STAGES = 4;
 constexpr int W_STAGE_FLOATS = (WM + WN) * WK; /* 32 KB */
 constexpr int FF_MAXIN = 64;    /* k_fwd_fused: dense input columns at most */
+constexpr int T2_NB = 17;       /* k_text_top2 (k_text_top2.h): float4 of W_ho per lane, i.e. a wave's rows in one batch of 4 x T2_NB */
+/* ... and the LDS its body needs, in floats: [H] hidden row, [16 waves][O] column sums, [O] outputs, [O] output error */
+constexpr int text_top2_lds_floats(int H, int O) { return H + 18 * O; }
 
 /* the RECUR_AMD_* switches, which the plans read: kernels_support.hip in the library (k_common.h declares it hidden there,
  * the version script keeps it unexported); the plans' test harnesses have their own */

@@ -220,13 +220,22 @@ struct WaveSumDpp { /* wave_sum_all: DPP within a row, then (r0 + r1) + (r2 + r3
 // The hidden row into shid (LDS).  fwd_ks != 0: the forward GEMM's K slabs are still in the workspace: sum them, apply the
 // activation and write the hidden row here (what k_fwd_finalize does, recur-nn.c:123-148).  fwd_ks < 0: k_fwd_fused left
 // one plane of sums and, for the h_size padding columns, -fwd_ks per-tile partial sums in plane 1.
-template <class WSUM>
-__device__ __forceinline__ void top_hidden_row(const View &v, int r, int nrows, int fwd_ks, float *shid, WSUM wave_sum) {
+/* one of the forward launch's sums.  PAST_L1: by a load that does not look in this CU's L1 -- another workgroup of the
+ * SAME launch wrote the value (k_fwd_top, kernels_forward.hip); the value is the same either way */
+template <bool PAST_L1> __device__ __forceinline__ float top_fwd_sum(const float *p) {
+  if constexpr (PAST_L1)
+    return __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<const unsigned *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+  else
+    return *p;
+}
+/* j: the stream within the call (the row of the workspace), r: its state row */
+template <bool PAST_L1, class WSUM>
+__device__ __forceinline__ void top_hidden_row_at(const View &v, int j, int r, int nrows, int fwd_ks, float *shid, WSUM wave_sum) {
 #pragma clang fp contract(off)
   const RamdShape &s = v.sh;
   float *hid = v.b.hidden + (size_t)r * s.H;
   if (fwd_ks != 0) {
-    const float *p = v.b.slab + (size_t)blockIdx.x * s.H;
+    const float *p = v.b.slab + (size_t)j * s.H;
     const int npart = fwd_ks < 0 ? -fwd_ks : 0;
     if (fwd_ks < 0) fwd_ks = 1;
     const size_t plane = (size_t)nrows * s.H;
@@ -235,12 +244,12 @@ __device__ __forceinline__ void top_hidden_row(const View &v, int r, int nrows, 
        * them one L2 latency after another) */
       float xs[8];
 #pragma unroll
-      for (int z = 0; z < 8; z++) xs[z] = (z < fwd_ks) ? p[z * plane + i] : 0.0f;
+      for (int z = 0; z < 8; z++) xs[z] = (z < fwd_ks) ? top_fwd_sum<PAST_L1>(p + z * plane + i) : 0.0f;
       float x = xs[0];
 #pragma unroll
       for (int z = 1; z < 8; z++)
         if (z < fwd_ks) x += xs[z];
-      for (int z = 8; z < fwd_ks; z++) x += p[z * plane + i];
+      for (int z = 8; z < fwd_ks; z++) x += top_fwd_sum<PAST_L1>(p + z * plane + i);
       if (npart && i >= s.H - 4) continue; /* the tail columns: below */
       x = act_forward(s, x);
       if (i == 0) x = 1.0f; /* the bias node, recur-nn.c:148 */
@@ -251,9 +260,9 @@ __device__ __forceinline__ void top_hidden_row(const View &v, int r, int nrows, 
       /* k_fwd_fused's four tail columns (hidden value hidden_size and the padding of h_size):
        * wave p4 adds column p4's per-tile partial sums */
       const int p4 = threadIdx.x >> 6, ln = threadIdx.x & 63;
-      const float *pd = v.b.slab + (size_t)nrows * s.H + (size_t)blockIdx.x * 4 + p4;
+      const float *pd = v.b.slab + (size_t)nrows * s.H + (size_t)j * 4 + p4;
       float x = 0.0f;
-      for (int t = ln; t < npart; t += 64) x += pd[(size_t)t * nrows * 4];
+      for (int t = ln; t < npart; t += 64) x += top_fwd_sum<PAST_L1>(pd + (size_t)t * nrows * 4);
       x = act_forward(s, wave_sum(x));
       if (ln == 0) {
         hid[s.H - 4 + p4] = x;
@@ -263,6 +272,11 @@ __device__ __forceinline__ void top_hidden_row(const View &v, int r, int nrows, 
   } else {
     for (int i = threadIdx.x; i < s.H; i += 1024) shid[i] = hid[i];
   }
+}
+/* ... by the workgroup of stream blockIdx.x of the call (the top launches) */
+template <class WSUM>
+__device__ __forceinline__ void top_hidden_row(const View &v, int r, int nrows, int fwd_ks, float *shid, WSUM wave_sum) {
+  top_hidden_row_at<false>(v, (int)blockIdx.x, r, nrows, fwd_ks, shid, wave_sum);
 }
 /* the stream's running statistics of the epoch loop (charmodel-predict.c:302-304) from tstat, by one thread */
 __device__ __forceinline__ void top_add_stats(const View &v, int r, const float *tstat) {

@@ -520,9 +520,7 @@ struct ChainSync {
 struct SeatTable {
   unsigned seat[8][256];
 };
-typedef const __attribute__((address_space(4))) unsigned *seat_tbl_p;
-/* HW_REG_HW_ID (register 4) bits 8 .. 15: cu_id[3:0], sh_id, se_id[2:0] -- the CU's number within its XCD */
-#define PC_HW_CU_KEY() (__builtin_amdgcn_s_getreg(((8 - 1) << 11) | (8 << 6) | 4) & 0xffu)
+/* (seat_tbl_p, PC_HW_CU_KEY: k_common.h -- the forward + top launch of kernels_forward.hip seats its workgroups by the same table) */
 
 typedef __attribute__((address_space(1))) unsigned gu32;
 
@@ -1218,6 +1216,13 @@ static void chain_validate(hipStream_t st) {
 static bool g_side_streams = false;
 static unsigned g_ticket_launches = 0; /* launches that drew tickets: 32 per XCD each */
 extern "C" void ramd_note_side_stream(void) { g_side_streams = true; }
+
+/* The residency probe's answer for another launch that seats one workgroup per CU by the same table (k_fwd_top,
+ * kernels_forward.hip; fwd_top_plan.h decides with it): probed and standing, the table made, the process on tickets */
+SeatRule chain_seat_rule(hipStream_t st) {
+  chain_validate(st);
+  return SeatRule{g_chain_validated && !g_chain_broken, g_seat_table, g_side_streams, g_seats};
+}
 
 /* the host-mapped abort word's device address, for other bounded device-side waits (the exchange's barriers) */
 extern "C" unsigned *ramd_abort_word_dev(void) {

@@ -3,6 +3,8 @@
 #include "k_common.h"
 #include "k_gemm.h"
 #include "fwd_plan.h"
+#include "fwd_top_plan.h"
+#include "k_text_top2.h"
 
 // ------------------------------------------------------------ K0: advance --
 
@@ -512,16 +514,19 @@ extern "C" void ramd_fwd_stamps(unsigned long long *out) {
 #define FF_STAMP(i) do { } while (0)
 #endif
 BND_DECL(g_bnd_fwd, ramd_bnd_fwd_stamps)
-template <int NS = 0>
-__global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, int new_idx, int row0,
-                                                   int nrows, int tm, int tn, int nstages_arg,
-                                                   int mode, int text_i, int global_first,
-                                                   int n_set, const float *__restrict__ dense, int ld) {
-  FF_STAMP(0);
-  BND_MARK(g_bnd_fwd, 0);
-  View v = *vp;
+/* The work of one 32 x 32 tile (row tile mt, column tile nt) by the first eight waves of a workgroup: waves 0-3 multiply
+ * and finish, waves 4-7 load.  k_fwd_fused and k_fwd_top (below) both call it, so the sums are the same bits in either.
+ * NS s_barriers and one __syncthreads: waves of the workgroup that do not come here keep the count (k_fwd_top's 8-15).
+ * smem: the operand ring, C_STAGES * C_STAGE_FLOATS floats of LDS; free again when the function returns.
+ * MODE >= 0: the input mode as a constant (the forms of the other modes are not compiled in).
+ * PARK: what the epilogue needs from memory waits in LDS, not in registers, while the K loop runs -- the same values; for
+ * a caller whose waves have 128 registers (sixteen waves a workgroup), where they and the read-ahead do not fit together. */
+template <int NS, int MODE, bool PARK = false>
+__device__ __forceinline__ void fwd_fused_tile(const View &v, float *smem, const int mt, const int nt, int new_idx, int row0,
+                                               int nrows, int tn, int nstages_arg, int mode_arg, int text_i,
+                                               int global_first, int n_set, const float *__restrict__ dense, int ld) {
+  const int mode = MODE >= 0 ? MODE : mode_arg;
   const int nstages = NS > 0 ? NS : nstages_arg;
-  __shared__ __attribute__((aligned(16))) float smem[C_STAGES * C_STAGE_FLOATS];
   __shared__ float rs_sh[4][CM];
   __shared__ float4 wt_sh[CN];
   /* dense inputs (mode RAMD_IN_DENSE: the feature vectors of gstclassify, rnnca's neighbourhoods -- up to FF_MAXIN
@@ -530,10 +535,6 @@ __global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, 
   __shared__ __attribute__((aligned(16))) float win_sh[FF_MAXIN][CN];
   __shared__ float4 wint_sh[FF_MAXIN]; /* ... and those rows' tail columns (column tile 0) */
   const RamdShape &s = v.sh;
-  const int L = blockIdx.x;
-  const int xcd = L & 7, q = L >> 3;
-  const int mt = q % tm, nt = (q / tm) * 8 + xcd;
-  if (nt >= tn) return;
   /* column tiles start at column 0 (16-byte aligned rows of W and of the outputs); column 0's
    * sum is never used (the bias node), and the last four columns of h_size -- hidden value
    * hidden_size and the padding -- are not in any tile: they come as partial sums */
@@ -587,15 +588,30 @@ __global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, 
 #pragma unroll
   for (int i = 0; i < 16; i++) acc[i] = 0.0f;
 
-  const int etid = threadIdx.x & 255;
-  const int erow = etid >> 3, ec4 = (etid & 7) * 4;
-  const int er = m0 + erow < nrows ? m0 + erow : nrows - 1; /* row within the set */
-  const int grow = row0 + er;
+  /* (not const: PARK derives them a second time behind the K loop, so that they are not alive across it) */
+  int etid = threadIdx.x & 255;
+  int erow = etid >> 3, ec4 = (etid & 7) * 4;
+  int er = m0 + erow < nrows ? m0 + erow : nrows - 1; /* row within the set */
+  int grow = row0 + er;
   const int tail = s.H - 4; /* the four columns outside the tiles: hidden_size = tail or tail + 1 .. */
+  auto loader_loop = [&]() {
+#pragma unroll
+    for (int st = 0; st < nstages; st++) {
+      const int ahead = min(C_STAGES - 2, nstages - 1 - st);
+      if (ahead >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
+      else if (ahead == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      if (st + C_STAGES - 1 < nstages) issue(st + C_STAGES - 1);
+    }
+  };
   if (loader) {
 #pragma unroll
     for (int p = 0; p < C_STAGES - 1; p++)
       if (p < nstages) issue(p);
+    /* (PARK: the loaders' whole loop here, so that their sources are not alive across the other waves' requests below --
+     * the waves' own order of instructions is the same either way) */
+    if constexpr (PARK) loader_loop();
   }
   // --- what the epilogue needs (compute waves): the one-hot index, this thread's four input
   // values x[n0 + ec4 ..] (column 0 is the bias node, 1), the bias row's and the input row's
@@ -608,7 +624,7 @@ __global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, 
   constexpr int TAILK = 4; /* hidden values tail .. hidden_size: at most h_size - tail */
   float xt[TAILK] = {0.f, 0.f, 0.f, 0.f};
   float4 wtl[TAILK] = {zero4(), zero4(), zero4(), zero4()}, wth = zero4();
-  const bool tail_row = nt == 0 && (etid & 7) == 0;
+  bool tail_row = nt == 0 && (etid & 7) == 0;
   const bool dns = mode == RAMD_IN_DENSE;
   const int insz = dns ? s.input_size : 0;
   float xin_r[CM * FF_MAXIN / 256]; /* requested here, stored to LDS behind the K loop: nobody waits for them */
@@ -657,19 +673,32 @@ __global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, 
     ws = ld4(v.b.ih_w + (size_t)(hot >= 0 ? s.hidden_size + 1 + hot : 0) * s.H + n0 + ec4);
     if (tail_row) wth = ld4(v.b.ih_w + (size_t)(hot >= 0 ? s.hidden_size + 1 + hot : 0) * s.H + tail);
   }
+  /* PARK: they go to LDS as they land (the ones behind one load about when the first operand stage does, the two behind
+   * the symbol's load a round trip later) */
+  __shared__ float4 park_sh[PARK ? 3 : 1][PARK ? 256 : 1];
+  __shared__ float4 park_tail_sh[PARK ? TAILK + 2 : 1][PARK ? CM : 1];
+  __shared__ int park_sym_sh[PARK ? 2 : 1][PARK ? 256 : 1];
+  if constexpr (PARK) {
+    if (!loader) {
+      park_sh[0][etid] = a4;
+      park_sh[1][etid] = wb;
+      park_sh[2][etid] = ws;
+      park_sym_sh[0][etid] = hot;
+      park_sym_sh[1][etid] = text_o;
+      if (etid < CN) wt_sh[etid] = wt_mine;
+      if (tail_row) {
+        park_tail_sh[TAILK][erow] = make_float4(xt[0], xt[1], xt[2], xt[3]);
+        park_tail_sh[TAILK + 1][erow] = wth;
+#pragma unroll
+        for (int i = 0; i < TAILK; i++) park_tail_sh[i][erow] = wtl[i];
+      }
+    }
+  }
   const uint32_t lds0 = lds_byte_addr(smem);
   const uint32_t rowoff = (uint32_t)lm * (CK * 4u);
   float rsum = 0.0f;
   if (loader) {
-#pragma unroll
-    for (int st = 0; st < nstages; st++) {
-      const int ahead = min(C_STAGES - 2, nstages - 1 - st);
-      if (ahead >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if (ahead == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      if (st + C_STAGES - 1 < nstages) issue(st + C_STAGES - 1);
-    }
+    if constexpr (!PARK) loader_loop();
   } else {
     struct BFrag {
       f32x2 lo[4], hi[4];
@@ -747,7 +776,7 @@ __global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, 
     }
     rsum += __shfl_xor(rsum, 32, 64);
     if (kh == 0) rs_sh[wave][lm] = rsum;
-    if (etid < CN) wt_sh[etid] = wt_mine;
+    if (!PARK && etid < CN) wt_sh[etid] = wt_mine;
     if (dns) {
 #pragma unroll
       for (int u = 0; u < CM * FF_MAXIN / 256; u++) {
@@ -765,6 +794,28 @@ __global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, 
   __syncthreads();
   if (loader) return;
   FF_STAMP(4);
+  if constexpr (PARK) {
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid)); /* (the compiler is not to know that these are the values it had before the loop) */
+    etid = tid & 255;
+    erow = etid >> 3, ec4 = (etid & 7) * 4;
+    er = m0 + erow < nrows ? m0 + erow : nrows - 1;
+    grow = row0 + er;
+    tail_row = nt == 0 && (etid & 7) == 0;
+    hot = park_sym_sh[0][etid];
+    text_o = park_sym_sh[1][etid];
+    a4 = park_sh[0][etid];
+    wb = park_sh[1][etid];
+    ws = park_sh[2][etid];
+    { /* (every lane, not the tail rows' alone: a lane that kept its old values would keep them alive across the loop;
+       * what the others read is never used) */
+      wth = park_tail_sh[TAILK + 1][erow];
+      const float4 x4 = park_tail_sh[TAILK][erow];
+      xt[0] = x4.x, xt[1] = x4.y, xt[2] = x4.z, xt[3] = x4.w;
+#pragma unroll
+      for (int i = 0; i < TAILK; i++) wtl[i] = park_tail_sh[i][erow];
+    }
+  }
   const int row = erow, c4 = ec4;
   float4 wt[4];
 #pragma unroll
@@ -858,6 +909,135 @@ __global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, 
       for (int k = sub; k < s.input_size; k += 8) slot[s.hidden_size + 1 + k] = (k == hot) ? scale : 0.0f;
   }
   FF_STAMP(5);
+}
+
+template <int NS = 0>
+__global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, int new_idx, int row0,
+                                                   int nrows, int tm, int tn, int nstages_arg,
+                                                   int mode, int text_i, int global_first,
+                                                   int n_set, const float *__restrict__ dense, int ld) {
+  FF_STAMP(0);
+  BND_MARK(g_bnd_fwd, 0);
+  View v = *vp;
+  __shared__ __attribute__((aligned(16))) float smem[C_STAGES * C_STAGE_FLOATS];
+  const int L = blockIdx.x;
+  const int xcd = L & 7, q = L >> 3;
+  const int mt = q % tm, nt = (q / tm) * 8 + xcd;
+  if (nt >= tn) return;
+  fwd_fused_tile<NS, -1>(v, smem, mt, nt, new_idx, row0, nrows, tn, nstages_arg, mode, text_i, global_first, n_set, dense, ld);
+  BND_MARK(g_bnd_fwd, 1);
+}
+
+// ------------------------------------ the text step's forward pass AND top layer in one launch --
+//
+// k_fwd_fused + k_text_top2 as one launch (fwd_top_plan.h says when): between the two launches lie 1.7 us of boundary, and
+// k_text_top2 spends its first 3.5 us waiting for its rows of W_ho, which depend on nothing the forward pass computes.
+// 256 workgroups of sixteen waves, one per CU (113 KB of LDS, 1024 threads); the workgroup on seat j of XCD g (the
+// residency probe's seat table, as in k_chain_persist) is column tile j of row tile g:
+//   phase 1: waves 0-7 run fwd_fused_tile, k_fwd_fused's work for the tile.  Waves 8-15 request their rows of W_ho as the
+//            kernel's first instructions and then only keep the barrier count; waves 4-7, the loaders, request theirs when
+//            their last stage has been taken (their counted vmcnt waits see nothing of it), waves 0-3 behind the hand-off;
+//   hand-off: the block's stores drained, a barrier, ONE plain store of the launch's number into the workgroup's flag
+//            word -- row tile and readers share the XCD's L2, the chain's protocol.  Wave 8 polls the row tile's 32 flags
+//            past the L1, bounded: a time-out or the abort word set ends the workgroup and raises the abort word
+//            (host-mapped: ramd_dsync reports it), and lowers the workgroup's own flag so that no late workgroup of the row
+//            tile goes on alone;
+//   phase 2: text_top2_rest for stream j of the row tile, all sixteen waves, the sums and the target read past the L1,
+//            the ring's LDS for its hidden row and column sums.
+// A workgroup on an XCD past the set's row tiles has nothing to do.
+struct FwdTopSync {
+  unsigned flags[FWD_TOP_MAX_TILES][32]; /* [row tile][column tile]: the number of the last launch that stored its block */
+  unsigned abort;                        /* raised by any workgroup that gives up */
+};
+typedef __attribute__((address_space(1))) unsigned ft_gu32;
+#if defined(PC_STAMPS) || defined(FT_STAMPS) /* development builds only: workgroup (0, 0)'s phases (-DFT_STAMPS: these stamps alone) */
+__device__ unsigned long long g_ft_stamps[8];
+extern "C" void ramd_fwd_top_stamps(unsigned long long *out) {
+  HIP_CHECK(hipDeviceSynchronize());
+  HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ft_stamps), sizeof(unsigned long long) * 8));
+}
+#define FT_STAMP(i) do { if (g == 0 && j == 0 && threadIdx.x == ((i) < 4 ? 0u : 512u)) g_ft_stamps[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
+#else
+#define FT_STAMP(i) do { } while (0)
+#endif
+template <int NS>
+__global__ __launch_bounds__(1024) void k_fwd_top(const View *__restrict__ vp, int new_idx, int row0, int nrows, int text_i,
+                                                  int global_first, int n_set, FwdTopSync *sy, unsigned seq,
+                                                  unsigned *host_abort, const unsigned *seats) {
+  /* (first: one scalar load beside the arguments' -- see SeatTable, kernels_chain.hip) */
+  const unsigned hw_xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u; /* HW_REG_XCC_ID */
+  const unsigned seat = ((seat_tbl_p)seats)[hw_xcc * 256u + PC_HW_CU_KEY()];
+  __shared__ __attribute__((aligned(16))) float smem[C_STAGES * C_STAGE_FLOATS];
+  __shared__ unsigned ft_dead;
+  BND_MARK(g_bnd_fwd, 0);
+  View v = *vp;
+  const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int g = (int)hw_xcc, j = (int)seat;
+  if (seat >= 32u) { /* a CU the probe did not name: cannot happen with one workgroup per CU on a 256-CU part */
+    if (threadIdx.x == 0) {
+      __hip_atomic_store(&sy->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(host_abort, 7u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    return;
+  }
+  if (g >= nrows / CM) return;
+  FT_STAMP(0);
+  unsigned *const flag = &sy->flags[g][j];
+  float4 wv[T2_NB];
+  if (wave8 >= 8) {
+    text_top2_request(v, wv);
+    /* fwd_fused_tile's barriers (NS and its __syncthreads), and the hand-off's */
+#pragma unroll
+    for (int i = 0; i < NS + 2; i++) __builtin_amdgcn_s_barrier();
+  } else {
+    fwd_fused_tile<NS, RAMD_IN_TEXT, true>(v, smem, g, j, new_idx, row0, nrows, FWD_TOP_HIDDEN / CN, NS, RAMD_IN_TEXT, text_i,
+                                     global_first, n_set, nullptr, 0);
+    if (wave8 >= 4) text_top2_request(v, wv);
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* the block of sums, the partials, the slot, index and target: in the L2 */
+    FT_STAMP(1);
+    __builtin_amdgcn_s_barrier();
+    if (threadIdx.x == 0) *flag = seq; /* plain: stays in this XCD's L2, where the row tile's polls find it */
+    if (wave8 < 4) text_top2_request(v, wv);
+    FT_STAMP(2);
+  }
+  // ---- every column tile of the row tile has stored its block?  (wave 8: it requested its W_ho rows as the kernel's first
+  // instructions, the K loop ago.  The poll's vmcnt(0) waits for them too, loads return in order: after 8 stages that is
+  // no wait; it is never wrong, and the rows are needed right behind the poll anyway.  Waves 0-7 asked later.)
+  if (wave8 == 8) {
+    const unsigned *fbase = &sy->flags[g][0];
+    const unsigned poll_off = (unsigned)((lane & 31) * sizeof(unsigned));
+    unsigned dead = 0u;
+    for (unsigned spins = 0;; spins++) {
+      unsigned got;
+      asm volatile("global_load_dword %0, %1, %2 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(got) : "v"(poll_off), "s"(fbase) : "memory");
+      if (__all(got >= seq)) break;
+      if ((spins & 1023u) == 1023u) { /* rarely: has somebody else given up; have we been here for a second */
+        const unsigned ab = __hip_atomic_load((ft_gu32 *)&sy->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (__any(ab != 0u) || spins > (1u << 21)) {
+          if (lane == 0) {
+            __hip_atomic_store(&sy->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(host_abort, 7u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          }
+          dead = 1u;
+          break;
+        }
+      }
+      __builtin_amdgcn_s_sleep(1);
+    }
+    if (lane == 0) ft_dead = dead;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+  __builtin_amdgcn_s_barrier();
+  {
+    unsigned dead;
+    asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(dead) : "v"(lds_byte_addr(&ft_dead)) : "memory");
+    if (__builtin_amdgcn_readfirstlane(dead)) return;
+  }
+  FT_STAMP(4);
+  const int jc = g * CM + j, r = row0 + jc; /* the stream: within the call, state row */
+  text_top2_rest<true, true>(v, jc, r, nrows, -(FWD_TOP_HIDDEN / CN), smem, wv);
+  FT_STAMP(5);
   BND_MARK(g_bnd_fwd, 1);
 }
 
@@ -1073,6 +1253,34 @@ static void launch_fwd_fused_ns(hipStream_t st, const View *d_view, const RamdBu
               p.ht.tn, p.nstages, c->mode, c->text_i, c->global_first, c->global_count, c->dense, c->ld);
 }
 
+/* the text step's pass and its top layer as one launch, where fwd_top_plan.h says so; false: nothing launched */
+static FwdTopSync *g_ft_sync = nullptr;
+static unsigned g_ft_seq = 0;
+static long g_ft_launches = 0;
+static bool launch_fwd_top(hipStream_t st, const View &v, const RamdShape *sh, const RamdBuffers *b, const RamdFwdCall *c,
+                           const FwdPlan &p) {
+  if (!fwd_top_shape_ok(sh, b, c, p)) return false; /* (first: the probe behind the seats is a launch and a wait, once) */
+  const SeatRule sr = chain_seat_rule(st);
+  if (!fwd_top_seats_ok(FwdTopSeats{sr.resident, sr.table, sr.tickets})) return false;
+  if (!g_ft_sync) {
+    HIP_CHECK(hipMalloc(&g_ft_sync, sizeof(FwdTopSync)));
+    HIP_CHECK(hipMemset(g_ft_sync, 0, sizeof(FwdTopSync)));
+  }
+  if (g_ft_seq >= (1u << 30)) { /* flags compare as unsigned numbers: start over long before they wrap */
+    HIP_CHECK(hipStreamSynchronize(st));
+    HIP_CHECK(hipMemset(g_ft_sync, 0, sizeof(FwdTopSync)));
+    g_ft_seq = 0;
+  }
+  const View *d_view = device_view(st, v);
+  int ev = timing_begin(st, T_FWD);
+  RAMD_LAUNCH(k_fwd_top<8>, dim3(256), dim3(1024), 0, st, d_view, b->uniform_idx, c->row0, c->nrows, c->text_i, c->global_first,
+              c->global_count, g_ft_sync, ++g_ft_seq, ramd_abort_word_dev(), sr.seats);
+  timing_end(st, ev);
+  g_ft_launches++;
+  return true;
+}
+extern "C" long ramd_fwd_top_launches(void) { return g_ft_launches; }
+
 static void stage_input(hipStream_t st, const View &v, const RamdShape *sh, const RamdFwdCall *c, const FwdPlan &p) {
   if (p.input == FIN_BOTTOM) {
     if (p.advance_first) RAMD_LAUNCH(k_advance, dim3((c->nrows + 255) / 256), dim3(256), 0, st, v, c->row0, c->nrows);
@@ -1154,8 +1362,9 @@ static void stage_output(hipStream_t st, const View &v, const RamdShape *sh, con
 extern "C" RamdHandover ramd_launch_forward(ramd_stream_t st_, const RamdShape *sh, const RamdBuffers *b, const RamdFwdCall *c,
                                             void (*seam)(void *ctx), void *ctx) {
   hipStream_t st = (hipStream_t)st_;
-  const FwdPlan p = ramd_plan_forward(sh, b, c);
   View v = make_view(sh, b);
+  const FwdPlan p = ramd_plan_forward(sh, b, c);
+  if (launch_fwd_top(st, v, sh, b, c, p)) return RamdHandover{0, 0, 1}; /* the top layer is done too */
   stage_input(st, v, sh, c, p);
   stage_hidden(st, v, b, c, p);
   stage_noise(st, v, c, p);

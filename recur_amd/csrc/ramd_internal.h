@@ -159,9 +159,12 @@ typedef struct RamdFwdCall {
   int one_net;     /* rnn_opinion for one net: the one-launch form for small nets may take it */
 } RamdFwdCall;
 /* What a pass that stops for a top launch leaves in the workspace: `planes` K slabs of the hidden layer's sums
- * (0: nothing), or one plane and `partials` per-tile partial sums of the h_size padding columns behind it */
+ * (0: nothing), or one plane and `partials` per-tile partial sums of the h_size padding columns behind it.  top_done: a
+ * pass for the text step's top launch has run that top layer in its own launch (fwd_top_plan.h): nothing is left, and
+ * ramd_launch_text_top is not to follow */
 typedef struct RamdHandover {
   int planes, partials;
+  int top_done;
 } RamdHandover;
 /* The pass: fwd_plan.h says which kernels, this enqueues them.  `seam` (or NULL) is called with `ctx` between the
  * hidden layer's end and the output layer where the hidden layer was the fused launch with its own finishing kernel,
@@ -479,6 +482,7 @@ void ramd_launch_fused_updates(ramd_stream_t st, const RamdShape *sh, const Ramd
  * resident, or a poll timed out): the results of that launch are not valid */
 unsigned ramd_chain_abort_word(void);
 unsigned *ramd_abort_word_dev(void);
+long ramd_fwd_top_launches(void); /* kernels_forward.hip: launches of the forward + top kernel so far */
 /* the library has created a second stream with work that may run beside the BPTT chain: the chain then stops
  * deriving its workgroups' XCDs from their numbers (kernels_chain.hip) */
 void ramd_note_side_stream(void);

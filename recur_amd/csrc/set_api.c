@@ -468,7 +468,9 @@ void rnn_amd_set_char_step_fused(RnnAmdSet *set, int i, unsigned batch_size) {
   unsigned top_done = 0;
   if (ramd_text_top_ok(s)) { /* advance + hidden layer, then output layer, loss and top backprop in one launch */
     const RamdHandover left = ramd_set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_FOR_TEXT_TOP);
-    ramd_launch_text_top(ramd_stream, s, &e->b, j, 1, left);
+    if (!left.top_done) { /* (one stream: always -- the one-launch form takes whole row tiles) */
+      ramd_launch_text_top(ramd_stream, s, &e->b, j, 1, left);
+    }
     top_done = RAMD_TOP_DONE;
   } else {
     ramd_set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_WHOLE); /* advance + one-hot opinion */

@@ -13,10 +13,13 @@ static void char_step_deltas(RnnAmdSet *set, int i, RamdPendingDelta *defer) {
   RamdEngine *e = set->eng;
   ramd_set_check_text_pos(e, i, 0, "rnn_amd_set_char_step");
   if (ramd_text_top_ok(&e->sh)) {
-    /* advance + hidden layer, then output layer, loss and top backprop in one launch */
+    /* advance + hidden layer, then output layer, loss and top backprop in one launch -- or all of it in one
+     * (fwd_top_plan.h: the north star's shape, RECUR_AMD_FWD_TOP=0 for the two) */
     const RamdHandover left = ramd_set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_FOR_TEXT_TOP);
     ramd_noise_ahead_offer(set, 0); /* no draws between this pass's noise and the next one's */
-    ramd_launch_text_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, left);
+    if (!left.top_done) {
+      ramd_launch_text_top(ramd_stream, &e->sh, &e->b, set->row0, set->n, left);
+    }
     ramd_set_calc_deltas(set, 0, NULL, NULL, NULL, RAMD_TOP_DONE, NULL, 0, defer);
   } else {
     ramd_set_forward(set, RAMD_IN_TEXT, NULL, 0, i, NULL, 1, RAMD_FWD_WHOLE); /* advance + one-hot opinion */
