@@ -5,6 +5,7 @@
  * aborts (ramd_require_device). */
 #define RAMD_HIP_HOST 1
 #include "rnn_host.h"
+#include "coop_rule.h"
 
 static int g_device = -1;      /* -1: not initialised */
 static int g_device_count = -1;
@@ -115,19 +116,19 @@ void ramd_dsync(void) {
   g_syncs++;
   if (ramd_chain_abort_word()) {
     const unsigned code = ramd_chain_abort_word();
-    if (code == 6) {
+    if (code == COOP_ABORT_XCHG_BARRIER) {
       fprintf(stderr, "librecur_amd: a rank waited its time out (20 s; RECUR_AMD_XCHG_BARRIER_TIMEOUT_S) at a barrier of the kernel-issued exchange: not every rank "
                       "reached it (did one die, or drive fewer generations?); the replicas are out of step.\n");
-    } else if (code == 7) {
+    } else if (code == COOP_ABORT_FWD_TOP) {
       fprintf(stderr, "librecur_amd: the text step's forward + top launch gave up (code 7: its 256 workgroups were not all "
                       "resident, one per CU, or a hand-off timed out); its results are invalid.  Set RECUR_AMD_FWD_TOP=0 "
                       "(the two launches).\n");
-    } else if (code == 2) {
+    } else if (code == COOP_ABORT_CHAIN_OFF_XCD) {
       fprintf(stderr, "librecur_amd: a workgroup of the one-launch BPTT chain was not on the XCD its number implies (code 2): "
                       "something else ran on this GPU beside the chain and the dispatcher interleaved the two launches; "
                       "its results are invalid.  That form is only taken with RECUR_AMD_XCD_STATIC=1: drop it (the default "
                       "takes the seat from the CU a workgroup runs on, whatever runs beside it).\n");
-    } else {
+    } else { /* COOP_ABORT_CHAIN */
       fprintf(stderr, "librecur_amd: the one-launch BPTT chain gave up (code %u: its 256 workgroups were "
                       "not all resident, one per CU, or a hand-off timed out); its results are invalid.  "
                       "Set RECUR_AMD_CHAIN_CHECK=1 (every launch checked, a chain that gives up is redone) or "

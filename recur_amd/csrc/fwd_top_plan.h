@@ -5,7 +5,8 @@
 // and tests/test_fwd_top_plan.py asks it on a machine without a GPU.
 //
 // The launch is 256 workgroups of sixteen waves, one per CU; the 32 column-tile workgroups of a 32-stream row tile sit on
-// ONE XCD (row tile g on XCD g, seats from the residency probe's table as the one-launch chain's), raise a flag each when
+// ONE XCD (row tile g on XCD g, seats from the residency probe's table as the one-launch chain's: coop_rule.h, and DESIGN.md,
+// "Launches whose workgroups wait for one another"), raise a flag each when
 // their block of the new hidden sums is stored, and workgroup j of them then runs the top layer for stream j of the tile.
 // So: hidden 1024 (32 column tiles = 32 seats = 32 streams), whole row tiles, at most eight of them, every stream at one
 // ring position, text input, no presynaptic noise, no bottom layer, the shape k_text_top2 takes -- and the process not on
@@ -15,13 +16,7 @@
 // a give-up of this launch, first in the generation, would be taken for the chain's and its generation kept.
 #pragma once
 #include "fwd_plan.h"
-
-/* what the residency probe found, as plain numbers (kernels_chain.hip: chain_seat_rule) */
-struct FwdTopSeats {
-  int resident; /* 256 workgroups were resident together, one per CU, and no launch has given up since */
-  int table;    /* the seat table is there */
-  int tickets;  /* side stream, RCCL group (ramd_note_side_stream): the chain draws tickets */
-};
+#include "coop_rule.h" /* SeatRule: what the residency probe found, as plain numbers (kernels_coop.hip: coop_seat_rule) */
 
 constexpr int FWD_TOP_HIDDEN = 1024, FWD_TOP_MAX_TILES = 8;
 
@@ -49,9 +44,9 @@ static inline bool fwd_top_shape_ok(const RamdShape *sh, const RamdBuffers *b, c
 }
 
 /* the other half: what the probe found */
-static inline bool fwd_top_seats_ok(const FwdTopSeats &seats) { return seats.resident && seats.table && !seats.tickets; }
+static inline bool fwd_top_seats_ok(const SeatRule &seats) { return seats.resident && seats.table && !seats.tickets; }
 
 static inline bool fwd_top_takes(const RamdShape *sh, const RamdBuffers *b, const RamdFwdCall *c, const FwdPlan &p,
-                                 const FwdTopSeats &seats) {
+                                 const SeatRule &seats) {
   return fwd_top_shape_ok(sh, b, c, p) && fwd_top_seats_ok(seats);
 }

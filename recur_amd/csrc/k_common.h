@@ -8,11 +8,13 @@
 //   forward   Hpre[S x H] = X[S x I] . W_ih[I x H]              (recur-nn.c:18-48, 117)
 //   chain     E_i[S x I]  = E_h[S x H] . W_ih^T   per BPTT step (recur-nn.c:338-376)
 //   delta     dW[I x H]   = sum_t X_t^T . diag(c_t) . E_h,t      (recur-nn.c:344-356, 738)
-// kernels_forward.hip holds the first, kernels_chain.hip the second, kernels_bptt.hip the third with
+// kernels_forward.hip holds the first, kernels_chain.hip the second (its kernels in k_chain_steps.h and k_chain_persist.h),
+// kernels_bptt.hip the third with
 // the rest of rnn_bptt_calc_deltas (its kernels by stage in k_bptt_top.h, k_bptt_extras.h, k_delta_direct.h,
 // k_delta_dma.h, k_bptt_small.h; the launchers in the .hip), kernels_loss.hip the callers' loss functions on the device, kernels_rows.hip
 // the batched forward-only calls' one launch between two forward passes,
-// kernels_apply.hip rnn_apply_learning and the conditioning helpers.
+// kernels_apply.hip rnn_apply_learning and the conditioning helpers, kernels_coop.hip the process state of the launches
+// whose workgroups wait for one another (k_coop.h: their device part).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstring>
@@ -554,19 +556,6 @@ RAMD_LOCAL int env_int(const char *name, int dflt);
 // ---- the BPTT chain (kernels_chain.hip) ----
 // the device copy of the View for the kernels that take it by pointer
 RAMD_LOCAL const View *device_view(hipStream_t st, const View &v);
-/* The seat table of the launches whose workgroups wait for one another, one per CU (kernels_chain.hip: SeatTable): read
- * through a constant-address-space pointer, indexed by XCD and the CU's number within it */
-typedef const __attribute__((address_space(4))) unsigned *seat_tbl_p;
-/* HW_REG_HW_ID (register 4) bits 8 .. 15: cu_id[3:0], sh_id, se_id[2:0] -- the CU's number within its XCD */
-#define PC_HW_CU_KEY() (__builtin_amdgcn_s_getreg(((8 - 1) << 11) | (8 << 6) | 4) & 0xffu)
-/* what the residency probe found (chain_validate; made at the first call that asks) */
-struct SeatRule {
-  bool resident;        /* 256 workgroups were resident together, one per CU, and no launch has given up since */
-  bool table;           /* the seat table is there */
-  bool tickets;         /* another queue of this process has work beside the main one: the chain draws tickets */
-  const unsigned *seats; /* SeatTable, device */
-};
-RAMD_LOCAL SeatRule chain_seat_rule(hipStream_t st);
 // All D steps of the chain for streams [row0, row0 + nrows): the one-launch chain where it applies,
 // otherwise a launch per step.  Returns the number of partial sums of squares per (step, stream) it
 // left for the extras kernels (0: the extras sum the rows themselves).

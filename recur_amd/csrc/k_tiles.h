@@ -16,6 +16,11 @@ constexpr int OUT_SEGS = 16;    /* segments of the hidden row in the output-laye
 /* 64 x 64 tiles of the wide chain step and the wide forward GEMM (k_chain_wide, k_fwd_wide) */
 constexpr int WM = 64, WN = 64, WK = 64, W_STAGES = 4;
 constexpr int W_STAGE_FLOATS = (WM + WN) * WK; /* 32 KB */
+/* the one-launch chain (k_chain_persist.h): streams per sub-chain, its partial-tile area, its LDS per workgroup at hidden
+ * size K -- more than half a CU's, so one workgroup per CU; the residency probe (kernels_coop.hip) has the same footprint */
+constexpr int PC_SUB = 16;
+constexpr int PC_RED_FLOATS = 4 * PC_SUB * 32;
+constexpr int pc_lds_bytes(int K) { return (2 * PC_SUB * K + 2 * PC_RED_FLOATS) * 4 + 64; }
 constexpr int FF_MAXIN = 64;    /* k_fwd_fused: dense input columns at most */
 constexpr int T2_NB = 17;       /* k_text_top2 (k_text_top2.h): float4 of W_ho per lane, i.e. a wave's rows in one batch of 4 x T2_NB */
 /* ... and the LDS its body needs, in floats: [H] hidden row, [16 waves][O] column sums, [O] outputs, [O] output error */

@@ -1,6 +1,7 @@
 // kernels_apply.hip -- rnn_apply_learning (seven update rules), the fused two-update launch, conditioning helpers
 // (scale, abs-max, zero) and the small segmented copy.
 #include "k_common.h"
+#include "coop_rule.h"
 
 // --------------------------------------------------------- K11: optimiser --
 
@@ -216,7 +217,7 @@ __global__ void k_xchg_barrier(unsigned *flags, int rank, int world, unsigned se
       /* (seq - got) as a signed number: counters that have wrapped still compare */
       if ((int)(__hip_atomic_load(&flags[p], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - seq) >= 0) break;
       if (__builtin_amdgcn_s_memrealtime() - t0 > timeout_ticks) {
-        if (abort_word) __hip_atomic_store(abort_word, 6u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        if (abort_word) __hip_atomic_store(abort_word, (unsigned)COOP_ABORT_XCHG_BARRIER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         __hip_atomic_store(&g_xchg_gave_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         break;
       }

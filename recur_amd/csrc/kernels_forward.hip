@@ -1,6 +1,6 @@
 // kernels_forward.hip -- rnn_bptt_advance and rnn_opinion on the device: history advance, input assembly,
 // presynaptic noise, the bottom layer, the hidden-layer GEMM in its four forms and the output layer.
-#include "k_common.h"
+#include "k_coop.h"
 #include "k_gemm.h"
 #include "fwd_plan.h"
 #include "fwd_top_plan.h"
@@ -933,7 +933,8 @@ __global__ __launch_bounds__(512) void k_fwd_fused(const View *__restrict__ vp, 
 // k_fwd_fused + k_text_top2 as one launch (fwd_top_plan.h says when): between the two launches lie 1.7 us of boundary, and
 // k_text_top2 spends its first 3.5 us waiting for its rows of W_ho, which depend on nothing the forward pass computes.
 // 256 workgroups of sixteen waves, one per CU (113 KB of LDS, 1024 threads); the workgroup on seat j of XCD g (the
-// residency probe's seat table, as in k_chain_persist) is column tile j of row tile g:
+// residency probe's seat table, as in k_chain_persist: k_coop.h; DESIGN.md, "Launches whose workgroups wait for one
+// another") is column tile j of row tile g:
 //   phase 1: waves 0-7 run fwd_fused_tile, k_fwd_fused's work for the tile.  Waves 8-15 request their rows of W_ho as the
 //            kernel's first instructions and then only keep the barrier count; waves 4-7, the loaders, request theirs when
 //            their last stage has been taken (their counted vmcnt waits see nothing of it), waves 0-3 behind the hand-off;
@@ -949,7 +950,6 @@ struct FwdTopSync {
   unsigned flags[FWD_TOP_MAX_TILES][32]; /* [row tile][column tile]: the number of the last launch that stored its block */
   unsigned abort;                        /* raised by any workgroup that gives up */
 };
-typedef __attribute__((address_space(1))) unsigned ft_gu32;
 #if defined(PC_STAMPS) || defined(FT_STAMPS) /* development builds only: workgroup (0, 0)'s phases (-DFT_STAMPS: these stamps alone) */
 __device__ unsigned long long g_ft_stamps[8];
 extern "C" void ramd_fwd_top_stamps(unsigned long long *out) {
@@ -964,9 +964,9 @@ template <int NS>
 __global__ __launch_bounds__(1024) void k_fwd_top(const View *__restrict__ vp, int new_idx, int row0, int nrows, int text_i,
                                                   int global_first, int n_set, FwdTopSync *sy, unsigned seq,
                                                   unsigned *host_abort, const unsigned *seats) {
-  /* (first: one scalar load beside the arguments' -- see SeatTable, kernels_chain.hip) */
-  const unsigned hw_xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u; /* HW_REG_XCC_ID */
-  const unsigned seat = ((seat_tbl_p)seats)[hw_xcc * 256u + PC_HW_CU_KEY()];
+  /* (first: one scalar load beside the arguments' -- k_coop.h: seat_tbl_p) */
+  const unsigned hw_xcc = coop_hw_xcc();
+  const unsigned seat = coop_seat(seats, hw_xcc);
   __shared__ __attribute__((aligned(16))) float smem[C_STAGES * C_STAGE_FLOATS];
   __shared__ unsigned ft_dead;
   BND_MARK(g_bnd_fwd, 0);
@@ -974,10 +974,7 @@ __global__ __launch_bounds__(1024) void k_fwd_top(const View *__restrict__ vp, i
   const int wave8 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const int g = (int)hw_xcc, j = (int)seat;
   if (seat >= 32u) { /* a CU the probe did not name: cannot happen with one workgroup per CU on a 256-CU part */
-    if (threadIdx.x == 0) {
-      __hip_atomic_store(&sy->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(host_abort, 7u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+    if (threadIdx.x == 0) coop_give_up(&sy->abort, host_abort, COOP_ABORT_FWD_TOP);
     return;
   }
   if (g >= nrows / CM) return;
@@ -1006,24 +1003,11 @@ __global__ __launch_bounds__(1024) void k_fwd_top(const View *__restrict__ vp, i
   if (wave8 == 8) {
     const unsigned *fbase = &sy->flags[g][0];
     const unsigned poll_off = (unsigned)((lane & 31) * sizeof(unsigned));
-    unsigned dead = 0u;
-    for (unsigned spins = 0;; spins++) {
-      unsigned got;
-      asm volatile("global_load_dword %0, %1, %2 sc1\n\ts_waitcnt vmcnt(0)" : "=v"(got) : "v"(poll_off), "s"(fbase) : "memory");
-      if (__all(got >= seq)) break;
-      if ((spins & 1023u) == 1023u) { /* rarely: has somebody else given up; have we been here for a second */
-        const unsigned ab = __hip_atomic_load((ft_gu32 *)&sy->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (__any(ab != 0u) || spins > (1u << 21)) {
-          if (lane == 0) {
-            __hip_atomic_store(&sy->abort, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(host_abort, 7u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-          dead = 1u;
-          break;
-        }
-      }
-      __builtin_amdgcn_s_sleep(1);
+    /* has somebody else given up; have we been here for a second */
+    const unsigned dead = coop_poll(fbase, poll_off, seq, &sy->abort) ? 0u : 1u;
+    if (dead && lane == 0) {
+      coop_give_up(&sy->abort, host_abort, COOP_ABORT_FWD_TOP);
+      __hip_atomic_store(flag, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); /* (no late workgroup of the row tile goes on alone) */
     }
     if (lane == 0) ft_dead = dead;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1260,13 +1244,13 @@ static long g_ft_launches = 0;
 static bool launch_fwd_top(hipStream_t st, const View &v, const RamdShape *sh, const RamdBuffers *b, const RamdFwdCall *c,
                            const FwdPlan &p) {
   if (!fwd_top_shape_ok(sh, b, c, p)) return false; /* (first: the probe behind the seats is a launch and a wait, once) */
-  const SeatRule sr = chain_seat_rule(st);
-  if (!fwd_top_seats_ok(FwdTopSeats{sr.resident, sr.table, sr.tickets})) return false;
+  const SeatRule sr = coop_seat_rule(st);
+  if (!fwd_top_seats_ok(sr)) return false;
   if (!g_ft_sync) {
     HIP_CHECK(hipMalloc(&g_ft_sync, sizeof(FwdTopSync)));
     HIP_CHECK(hipMemset(g_ft_sync, 0, sizeof(FwdTopSync)));
   }
-  if (g_ft_seq >= (1u << 30)) { /* flags compare as unsigned numbers: start over long before they wrap */
+  if (coop_seq_starts_over(g_ft_seq, COOP_FWD_TOP_SEQ_LIMIT)) {
     HIP_CHECK(hipStreamSynchronize(st));
     HIP_CHECK(hipMemset(g_ft_sync, 0, sizeof(FwdTopSync)));
     g_ft_seq = 0;

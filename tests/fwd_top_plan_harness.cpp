@@ -14,7 +14,7 @@ int env_int(const char *name, int dflt) {
 
 int main(int argc, char **argv) {
   /* mode: RAMD_IN_* (3 text); want: RAMD_FWD_* (1 for the text top); uniform_idx < 0: staggered rings; resident, table,
-   * tickets: what the residency probe found (FwdTopSeats) */
+   * tickets: what the residency probe found (coop_rule.h: SeatRule) */
   std::map<std::string, long long> a = {
       {"input", 42}, {"hidden", 1024}, {"output", 42}, {"streams", 256}, {"row0", 0}, {"nrows", -1}, {"mode", 3},
       {"advance", 1}, {"noise", 0}, {"fwd_only", 0}, {"want", 1}, {"rows_built", 0}, {"one_net", 0}, {"uniform_idx", 0},
@@ -40,7 +40,7 @@ int main(int argc, char **argv) {
   c.ld = sh.input_size, c.global_count = c.nrows;
   c.advance = (int)a["advance"], c.noise = a["noise"] ? 0.1f : 0.0f, c.want = (int)a["want"];
   c.rows_built = (int)a["rows_built"], c.one_net = (int)a["one_net"];
-  const FwdTopSeats seats = {(int)a["resident"], (int)a["table"], (int)a["tickets"]};
+  const SeatRule seats = {(int)a["resident"], (int)a["table"], (int)a["tickets"], 0, nullptr};
   const FwdPlan p = ramd_plan_forward(&sh, &b, &c);
   printf("shape_ok=%d\ntakes=%d\n", (int)fwd_top_shape_ok(&sh, &b, &c, p), (int)fwd_top_takes(&sh, &b, &c, p, seats));
   return 0;

@@ -5,7 +5,7 @@ The table is derived by hand from what the launch is: 256 workgroups, one per CU
 32-stream row tile on one XCD, workgroup j of them also stream j's top layer.  So hidden 1024 (32 column tiles = 32
 streams), whole row tiles at one ring position, at most eight (one per XCD), text input, no noise, no bottom layer, the
 shape k_text_top2 takes (o_size a multiple of 4 up to 64), the residency probe passed with its seat table, and the
-process not on tickets.
+process not on tickets (recur_amd/csrc/coop_rule.h: SeatRule; tests/test_coop_rule.py asks that rule itself).
 
 And the build-time promise of the kernel: its hidden-1024 instantiation needs no scratch memory and no accumulation
 registers as spill space (sixteen waves a workgroup leave each wave 128 registers)."""

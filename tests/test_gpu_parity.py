@@ -1463,7 +1463,8 @@ def test_a_chain_that_gives_up_in_mid_run_is_redone_a_launch_per_step():
     """A co-tenant that takes CUs in mid-run makes a one-launch chain give up.  With RECUR_AMD_CHAIN_CHECK=1 (implied by
     RECUR_AMD_CHAIN_TEST_GIVEUP=n, n > 1, which pretends that the n-th launch gave up) every chain launch is checked:
     the launcher resets the abort word, switches the kernel off for the process and runs THAT call's chain again a
-    launch per step -- the results must be the oracle's, before and after (kernels_chain.hip: launch_chain_persist)."""
+    launch per step -- the results must be the oracle's, before and after (kernels_chain.hip: launch_chain_persist;
+    kernels_coop.hip: coop_mark_broken)."""
     import subprocess
     import sys as _sys
     script = GIVEUP_SCRIPT.replace("for i in range(4):", "for i in range(9):")
@@ -1479,7 +1480,7 @@ def test_the_chain_beside_another_process_on_the_same_gpu():
     """round 4's default took a chain workgroup's XCD and seat from its NUMBER, which anything
     else on the GPU -- another stream of the embedding application, another process, a second GStreamer element --
     invalidates by interleaving the dispatch: the launch gave up with abort code 2 and the host process was killed.  The
-    seat now comes from the CU a workgroup runs on (HW_REG_XCC_ID + HW_REG_HW_ID through the residency probe's table).
+    seat now comes from the CU a workgroup runs on (HW_REG_XCC_ID + HW_REG_HW_ID through the residency probe's table: coop_rule.h, k_coop.h).
     tools/gpu_cotenant_probe.py trains the north-star set while a SECOND PROCESS launches 256-workgroup kernels back to back
     (build/delta_direct_microbench: one workgroup per CU): 200 generations must go through without a give-up and a
     generation made beside the other process must match the oracle at 1e-4 -- and the same run with the workgroup-number
@@ -1511,7 +1512,7 @@ def test_the_chain_beside_another_process_on_the_same_gpu():
 def test_a_chain_that_gives_up_on_its_first_launch_falls_back_for_that_call():
     """The one-launch chain needs its 256 workgroups resident together; whether the device and queue grant that (no
     CU mask, no partition mode, no co-tenant holding CUs) is found out by a probe launch before the process's first
-    chain (kernels_chain.hip: chain_validate).  Where the probe fails the launch-per-step chain is used from the first
+    chain (kernels_coop.hip: coop_validate).  Where the probe fails the launch-per-step chain is used from the first
     call on.  RECUR_AMD_CHAIN_TEST_GIVEUP=1 takes that branch on a healthy device: the run must say so and its
     results must be the oracle's."""
     import subprocess
