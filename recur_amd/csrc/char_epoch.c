@@ -17,6 +17,7 @@
  */
 #include "char_host.h"
 #include "classify_rule.h"
+#include "text_pos_rule.h"
 
 /* ------------------------------------------------------------ cross entropy -- */
 
@@ -307,7 +308,7 @@ static void choose_route(Epoch *ep) {
   }
 }
 
-/* generation i of the epoch: stream j reads the text at i + j * spacing, wrapped (charmodel-predict.c:295-298) */
+/* generation i of the epoch: stream j reads the text where text_pos_rule.h says (charmodel-predict.c:295-298) */
 static void train_generation(Epoch *ep, int i, float momentum) {
   RnnCharModel *m = ep->model;
   RecurNN *net = m->net;
@@ -320,10 +321,9 @@ static void train_generation(Epoch *ep, int i, float momentum) {
     rnn_amd_set_char_step_fused(ep->set, i, m->batch_size);
     break;
   case ROUTE_NETS: {
-    const int last = ep->len - 1, spacing = last / m->n_training_nets;
     for (int j = 0; j < m->n_training_nets; j++) {
       RecurNN *stream = m->training_nets[j];
-      const int at = (i + j * spacing) % last;
+      const int at = text_pos(ep->len, m->n_training_nets, j, i); /* (i < len - 1: the epoch's loop) */
       rnn_bptt_advance(stream);
       host_loss(stream, ep->text[at], ep->text[at + 1], &ep->tally);
       rnn_bptt_calc_deltas(stream, j > 0, NULL); /* the first stream starts the sum, the others add */

@@ -1,5 +1,5 @@
 // fwd_top_plan.h -- whether a forward pass that stops for the text step's top launch (RAMD_FWD_FOR_TEXT_TOP) is taken,
-// top layer included, by the ONE launch k_fwd_top (kernels_forward.hip) instead of k_fwd_fused + k_text_top2: the rule,
+// top layer included, by the ONE launch k_fwd_top (k_fwd_top.h) instead of k_fwd_fused + k_text_top2: the rule,
 // apart from the launch.  Asked of the call's plan (ramd_plan_forward, whose answers stay what they are) before anything is
 // launched; where this says no, that plan and ramd_launch_text_top run as before.  No HIP call and no device pointer followed: the host compiler alone builds it,
 // and tests/test_fwd_top_plan.py asks it on a machine without a GPU.

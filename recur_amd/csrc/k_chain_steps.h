@@ -1,6 +1,6 @@
 // k_chain_steps.h -- the BPTT chain a launch per step: k_chain_main (32 x 32 tiles) and k_chain_wide (64 x 64 tiles, big
-// sets), included by kernels_chain.hip, which launches them.
-//
+// sets), included by kernels_chain.hip, which launches them.  Their K loop is k_ring.h's.
+#include "k_ring.h"
 // ------------------------------------------------------ BPTT chain step --
 //
 // One launch per BPTT step t (recur-nn.c:338-376 for every stream at once):
@@ -124,80 +124,50 @@ __global__ __launch_bounds__(512) void k_chain_main(const View *__restrict__ vp,
   const uint32_t lds0 = lds_byte_addr(smem);
   const uint32_t rowoff = (uint32_t)lm * (CK * 4u);
   if (loader) {
-#pragma unroll
-    for (int st = 0; st < nstages; st++) {
-      // stages st+1 .. st+C_STAGES-2 may stay in flight (8 DMAs per stage and loader wave)
-      const int ahead = min(C_STAGES - 2, nstages - 1 - st);
-      if (ahead >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-      else if (ahead == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier(); /* stage st has landed; stage st-1's buffer is free */
-      if (st + C_STAGES - 1 < nstages) issue(st + C_STAGES - 1);
-    }
+    RING_LOADER_LOOP(C_STAGES, nstages, issue)
   } else {
-    // Compute waves run one stage behind their own LDS reads: the fragments of stage
-    // st + 1 are requested right after its barrier and arrive while the 16 dependent
-    // MFMAs of stage st execute, so neither the ds_read latency nor the barrier sits
-    // between two MFMA blocks.
-    auto rd = [&](int st, f32x4 (&a)[4], f32x4 (&b)[4]) {
+    /* the K loop of a compute wave (k_ring.h): a stage's fragments are one quarter of its 32 chunks, on both operands */
+    struct Frag { f32x4 a[4], b[4]; };
+    auto rd = [&](int st, Frag &f) {
       const uint32_t abase = lds0 + (uint32_t)((st % C_STAGES) * C_STAGE_FLOATS) * 4u;
       const uint32_t bbase = abase + (uint32_t)(CM * CK) * 4u;
 #pragma unroll
       for (int gi = 0; gi < 4; gi++) {
         int c = 2 * (4 * wave + gi) + kh;               /* chunk = 4 consecutive k */
         uint32_t off = rowoff + (uint32_t)((c ^ (lm & 15)) * 16);
-        a[gi] = lds_read_b128(abase + off);
-        b[gi] = lds_read_b128(bbase + off);
+        f.a[gi] = lds_read_b128(abase + off);
+        f.b[gi] = lds_read_b128(bbase + off);
       }
     };
-    auto step = [&](int st, f32x4 (&a)[4], f32x4 (&b)[4], f32x4 (&an)[4], f32x4 (&bn)[4]) {
+    auto multiply = [&](const Frag &f) {
+#pragma unroll
+      for (int gi = 0; gi < 4; gi++) mfma_k4(acc, f.a[gi], f.b[gi].x, f.b[gi].y, f.b[gi].z, f.b[gi].w);
+    };
+    auto step = [&](int st, Frag &f, Frag &fn) {
       /* every read issued so far has arrived: this stage's fragments are usable, and the
        * loaders may overwrite its buffer after the next barrier */
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (st + 1 < nstages) {
         __builtin_amdgcn_s_barrier(); /* stage st + 1 has landed */
-        rd(st + 1, an, bn);
+        rd(st + 1, fn);
       }
       __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int gi = 0; gi < 4; gi++) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[gi].x, b[gi].x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[gi].y, b[gi].y, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[gi].z, b[gi].z, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[gi].w, b[gi].w, acc, 0, 0, 0);
-      }
+      multiply(f);
       __builtin_amdgcn_sched_barrier(0);
     };
     if constexpr (NS > 0) {
-      f32x4 a0[4], b0[4], a1[4], b1[4];
-      __builtin_amdgcn_s_barrier(); /* stage 0 has landed */
-      rd(0, a0, b0);
-#pragma unroll
-      for (int st = 0; st < NS; st += 2) {
-        step(st, a0, b0, a1, b1);
-        if (st + 1 < NS) step(st + 1, a1, b1, a0, b0);
-      }
-    } else {
-      /* Any number of stages: read, wait, multiply, stage by stage.  The read-ahead form above
-       * is only used fully unrolled: in a rolled loop the compiler may copy the ping-pong
-       * fragment registers right after the ds_read that fills them -- before the data has
-       * arrived -- since it cannot see that an inline-asm load completes later. */
-      f32x4 a[4], b[4];
+      RING_READ_AHEAD(NS, Frag, rd, step)
+    } else { /* any number of stages: read, wait, multiply, stage by stage (k_ring.h says why) */
+      Frag f;
       for (int st = 0; st < nstages; st++) {
         __builtin_amdgcn_s_barrier(); /* stage st has landed */
-        rd(st, a, b);
+        rd(st, f);
         asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]),
-                       "+v"(b[3])
+                     : "+v"(f.a[0]), "+v"(f.a[1]), "+v"(f.a[2]), "+v"(f.a[3]), "+v"(f.b[0]), "+v"(f.b[1]), "+v"(f.b[2]),
+                       "+v"(f.b[3])
                      :
                      : "memory");
-#pragma unroll
-        for (int gi = 0; gi < 4; gi++) {
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[gi].x, b[gi].x, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[gi].y, b[gi].y, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[gi].z, b[gi].z, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[gi].w, b[gi].w, acc, 0, 0, 0);
-        }
+        multiply(f);
       }
     }
   }
@@ -338,41 +308,28 @@ __global__ __launch_bounds__(512) void k_chain_wide(const View *__restrict__ vp,
 #pragma unroll
   for (int i = 0; i < 16; i++) acc[i] = 0.0f;
   const uint32_t arow = (uint32_t)((HALF ? 0 : wm * 32) + lm) * (WK * 4u), brow = (uint32_t)(MT + wn * 32 + lm) * (WK * 4u);
-  auto rd = [&](int st, f32x4 (&a)[NU], f32x4 (&b)[NU]) {
+  struct Frag { f32x4 a[NU], b[NU]; };
+  auto rd = [&](int st, Frag &f) {
     const uint32_t base = lds0 + (uint32_t)((st % W_STAGES) * W_STAGE_FLOATS) * 4u;
 #pragma unroll
     for (int u = 0; u < NU; u++) {
       const uint32_t off = (uint32_t)(((2 * (u + (HALF ? NU * wm : 0)) + kh) ^ (lm & 15)) * 16);
-      a[u] = lds_read_b128(base + arow + off);
-      b[u] = lds_read_b128(base + brow + off);
+      f.a[u] = lds_read_b128(base + arow + off);
+      f.b[u] = lds_read_b128(base + brow + off);
     }
   };
-  auto step = [&](int st, f32x4 (&a)[NU], f32x4 (&b)[NU], f32x4 (&an)[NU], f32x4 (&bn)[NU]) {
+  auto step = [&](int st, Frag &f, Frag &fn) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* this stage's fragments have arrived */
     if (st + 1 < NS) {
       __builtin_amdgcn_s_barrier(); /* stage st + 1 has landed */
-      rd(st + 1, an, bn);
+      rd(st + 1, fn);
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int u = 0; u < NU; u++) {
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].x, b[u].x, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].y, b[u].y, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].z, b[u].z, acc, 0, 0, 0);
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u].w, b[u].w, acc, 0, 0, 0);
-    }
+    for (int u = 0; u < NU; u++) mfma_k4(acc, f.a[u], f.b[u].x, f.b[u].y, f.b[u].z, f.b[u].w);
     __builtin_amdgcn_sched_barrier(0);
   };
-  {
-    f32x4 a0[NU], b0[NU], a1[NU], b1[NU];
-    __builtin_amdgcn_s_barrier(); /* stage 0 has landed */
-    rd(0, a0, b0);
-#pragma unroll
-    for (int st = 0; st < NS; st += 2) {
-      step(st, a0, b0, a1, b1);
-      if (st + 1 < NS) step(st + 1, a1, b1, a0, b0);
-    }
-  }
+  RING_READ_AHEAD(NS, Frag, rd, step)
   // the tile through LDS (the ring buffer stage NS would have used was read four barriers ago); HALF: the two K
   // halves' tiles, [2][32][64], as rows 0 .. 31 and 32 .. 63 of the same image
   float *red = wsm + (NS % W_STAGES) * W_STAGE_FLOATS; /* [64][64] */
@@ -389,10 +346,7 @@ __global__ __launch_bounds__(512) void k_chain_wide(const View *__restrict__ vp,
     float4 e4 = ld4(red + row * WN + c4);
     if (HALF) {
       const float4 f4 = ld4(red + (32 + row) * WN + c4);
-      e4.x += f4.x;
-      e4.y += f4.y;
-      e4.z += f4.z;
-      e4.w += f4.w;
+      add4(e4, f4);
     }
     const float e[4] = {e4.x, e4.y, e4.z, e4.w};
     float sq = 0.0f;

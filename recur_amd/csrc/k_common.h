@@ -8,7 +8,8 @@
 //   forward   Hpre[S x H] = X[S x I] . W_ih[I x H]              (recur-nn.c:18-48, 117)
 //   chain     E_i[S x I]  = E_h[S x H] . W_ih^T   per BPTT step (recur-nn.c:338-376)
 //   delta     dW[I x H]   = sum_t X_t^T . diag(c_t) . E_h,t      (recur-nn.c:344-356, 738)
-// kernels_forward.hip holds the first, kernels_chain.hip the second (its kernels in k_chain_steps.h and k_chain_persist.h),
+// kernels_forward.hip holds the first (its kernels in k_fwd_stages.h, k_fwd_wide.h, k_fwd_fused.h, k_fwd_top.h,
+// k_fwd_small.h and k_fwd_out.h), kernels_chain.hip the second (its kernels in k_chain_steps.h and k_chain_persist.h),
 // kernels_bptt.hip the third with
 // the rest of rnn_bptt_calc_deltas (its kernels by stage in k_bptt_top.h, k_bptt_extras.h, k_delta_direct.h,
 // k_delta_dma.h, k_bptt_small.h; the launchers in the .hip), kernels_loss.hip the callers' loss functions on the device, kernels_rows.hip
@@ -247,7 +248,7 @@ __device__ __forceinline__ int stale_plane(int n) { return (n & 1) ? n - 1 : n; 
 // The input row of one stream, by a workgroup of 256 threads: bias, the previous hidden values from `hid`, the real
 // inputs as `mode` says (recur-nn.c:104-112: kept, a dense row, or the one-hot of `hot`), the padding as it is (zero);
 // then the emergency soft clip of the whole row (maybe_scale_inputs, recur-nn.c:68-81).  The rule is stated here once,
-// for k_assemble (kernels_forward.hip) and the feed halves of kernels_rows.hip.  Every thread of the
+// for k_assemble (k_fwd_stages.h) and the feed halves of kernels_rows.hip.  Every thread of the
 // workgroup calls it (block_sum_256's barriers); red: 4 floats of LDS.
 __device__ __forceinline__ void assemble_input_row(const RamdShape &s, float *slot, const float *hid, int mode, int hot,
                                                    const float *dense_row, float *red) {
@@ -282,6 +283,10 @@ __device__ __forceinline__ float4 ld4(const float *p) {
   return *reinterpret_cast<const float4 *>(p);
 }
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
+/* a += t */
+__device__ __forceinline__ void add4(float4 &a, const float4 &t) {
+  a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
+}
 
 // recur-rng.h:22-31 (Jenkins small fast PRNG, 64 bit) and 179-200 (the sum of twelve
 // 16-bit fields), bit for bit: the noise a stream gets must be the one the reference
@@ -402,8 +407,21 @@ __device__ __forceinline__ f32x4 lds_read_b128(uint32_t addr) {
   return v;
 }
 
-/* [k][col] and [k + 1][col] of a 64-column K-major stage; _hi: k + 2, k + 3 (offsets in dwords) */
+/* [k][col] and [k + 1][col] of a 32-column K-major stage; _hi: k + 2, k + 3 (offsets in dwords).  The results are
+ * used as they come (sub-registers of the asm output): a copy the compiler is free to place
+ * before the s_waitcnt would read them too early */
 typedef float f32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 lds_read2_b32(uint32_t addr) {
+  f32x2 v;
+  asm volatile("ds_read2_b32 %0, %1 offset1:32" : "=v"(v) : "v"(addr));
+  return v;
+}
+__device__ __forceinline__ f32x2 lds_read2_b32_hi(uint32_t addr) {
+  f32x2 v;
+  asm volatile("ds_read2_b32 %0, %1 offset0:64 offset1:96" : "=v"(v) : "v"(addr));
+  return v;
+}
+/* the same of a 64-column stage */
 __device__ __forceinline__ f32x2 lds_read2_b32_w64(uint32_t addr) {
   f32x2 v;
   asm volatile("ds_read2_b32 %0, %1 offset1:64" : "=v"(v) : "v"(addr));
@@ -515,7 +533,7 @@ __device__ __forceinline__ float4 sum_planes(const float *src, size_t stride, in
     for (int z = 0; z < B; z++) t[z] = ld4(src + (size_t)(z0 + z < ks ? z0 + z : z0) * stride);
 #pragma unroll
     for (int z = 0; z < B; z++)
-      if (z0 + z < ks) { sum.x += t[z].x; sum.y += t[z].y; sum.z += t[z].z; sum.w += t[z].w; }
+      if (z0 + z < ks) { sum.x += t[z].x; sum.y += t[z].y; sum.z += t[z].z; sum.w += t[z].w; } /* (not add4: k_delta_finalize's order) */
   }
   return sum;
 }
@@ -656,7 +674,7 @@ __device__ __forceinline__ void chain_ho_delta(const View &v, const HoWork &hw, 
     float4 sum = *reinterpret_cast<const float4 *>(lds + 4 * (rr * 16 + q));
     for (int w = 1; w < 8; w++) {
       const float4 t = *reinterpret_cast<const float4 *>(lds + 4 * ((w * HO_HR + rr) * 16 + q));
-      sum.x += t.x; sum.y += t.y; sum.z += t.z; sum.w += t.w;
+      add4(sum, t);
     }
     *reinterpret_cast<float4 *>(hw.dst + fin_off) = sum;
     if (ap.w) {

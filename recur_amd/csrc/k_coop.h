@@ -1,6 +1,6 @@
 // k_coop.h -- the device part of the one-per-CU launches' protocol ("Launches whose workgroups wait for one
 // another"; the pure part: coop_rule.h, the process state: kernels_coop.hip), for the kernels whose 256 workgroups wait
-// for one another through flags in an XCD's L2: k_chain_persist (k_chain_persist.h) and k_fwd_top (kernels_forward.hip).
+// for one another through flags in an XCD's L2: k_chain_persist (k_chain_persist.h) and k_fwd_top (k_fwd_top.h).
 // Where a workgroup is (XCD, CU) and which seat that gives it; the bounded poll; the give-up pair.
 #pragma once
 #include "k_common.h"

@@ -4,6 +4,7 @@
 #pragma once
 #include "k_common.h"
 #include "k_gemm.h"
+#include "k_ring.h"
 
 // ------------------------------------------------ weight-delta GEMM by LDS-DMA --
 //
@@ -147,9 +148,7 @@ __global__ __launch_bounds__(512) void k_delta_dma(View v, int row0, int nrows, 
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
       } else {
-        if (ahead >= 2) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-        else if (ahead == 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        ring_wait_ahead(ahead);
       }
       __builtin_amdgcn_s_barrier(); /* stage st has landed; stage st-1's buffer is free */
       if (st + DD_STAGES - 1 < nst) issue(st + DD_STAGES - 1);

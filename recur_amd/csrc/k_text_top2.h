@@ -1,5 +1,5 @@
 // k_text_top2.h -- the text step's top layer for one stream by one workgroup of sixteen waves, round 6 form: the device
-// body that k_text_top2 (kernels_loss.hip) and the forward + top launch k_fwd_top (kernels_forward.hip) both run, so that
+// body that k_text_top2 (kernels_loss.hip) and the forward + top launch k_fwd_top (k_fwd_top.h) both run, so that
 // the two give the same bits.  Every function here sets its own fp contract mode (off: the reference's operations one by
 // one), whatever its including file has in force.
 //

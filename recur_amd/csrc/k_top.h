@@ -221,7 +221,7 @@ struct WaveSumDpp { /* wave_sum_all: DPP within a row, then (r0 + r1) + (r2 + r3
 // activation and write the hidden row here (what k_fwd_finalize does, recur-nn.c:123-148).  fwd_ks < 0: k_fwd_fused left
 // one plane of sums and, for the h_size padding columns, -fwd_ks per-tile partial sums in plane 1.
 /* one of the forward launch's sums.  PAST_L1: by a load that does not look in this CU's L1 -- another workgroup of the
- * SAME launch wrote the value (k_fwd_top, kernels_forward.hip); the value is the same either way */
+ * SAME launch wrote the value (k_fwd_top, k_fwd_top.h); the value is the same either way */
 template <bool PAST_L1> __device__ __forceinline__ float top_fwd_sum(const float *p) {
   if constexpr (PAST_L1)
     return __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<const unsigned *>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));

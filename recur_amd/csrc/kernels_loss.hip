@@ -376,7 +376,7 @@ __global__ __launch_bounds__(1024) void k_text_top(View v, int row0, int nrows, 
 }
 
 // ---- the text step's top launch, round 6 form (k_text_top2): W_ho once per workgroup, from registers both times --
-// (its body is k_text_top2.h's: the forward + top launch of kernels_forward.hip runs the same one)
+// (its body is k_text_top2.h's: the forward + top launch, k_fwd_top.h, runs the same one)
 __global__ __launch_bounds__(1024) void k_text_top2(View v, int row0, int nrows, int fwd_ks) {
   extern __shared__ float tsh[];
   const int j = blockIdx.x, r = row0 + j; /* the stream: within the call, state row */

@@ -1,4 +1,4 @@
-"""The text step's forward pass and top layer as ONE launch (k_fwd_top, recur_amd/csrc/kernels_forward.hip) against the
+"""The text step's forward pass and top layer as ONE launch (k_fwd_top, recur_amd/csrc/k_fwd_top.h) against the
 two launches it replaces (k_fwd_fused + k_text_top2): bit identity, no tolerance.  Both forms run the same device bodies
 (fwd_fused_tile, text_top2_rest), so every array and every statistic has to be equal bit for bit.
 
