@@ -1122,6 +1122,10 @@ double rnn_amd_kernel_time_ms(int which, long *launches, int reset);
 /* How many text steps of this process took the forward pass and the top layer as ONE launch (the north star's shape;
  * RECUR_AMD_FWD_TOP=0 for the two launches): for tests that compare the two forms. */
 long rnn_amd_fwd_top_launches(void);
+/* How many launches of the one-launch BPTT chain in this process started each half-step's multiply while the previous
+ * half-step's row stores drained (hidden 1024, 32-stream row tiles; RECUR_AMD_CHAIN_EARLY=0 for the form without): for tests
+ * that compare the two forms, which compute the same bits. */
+long rnn_amd_chain_early_launches(void);
 
 #ifdef __cplusplus
 }

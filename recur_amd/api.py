@@ -308,6 +308,7 @@ AMD_API = {
     "rnn_amd_kernel_time_enable": (None, [C.c_int]),
     "rnn_amd_kernel_time_ms": (C.c_double, [C.c_int, C.POINTER(C.c_long), C.c_int]),
     "rnn_amd_fwd_top_launches": (C.c_long, []),
+    "rnn_amd_chain_early_launches": (C.c_long, []),
 }
 RNN_AMD_WEIGHTS, RNN_AMD_MOMENTUMS, RNN_AMD_DELTAS, RNN_AMD_STREAM, RNN_AMD_ALL_STREAMS = 1, 2, 4, 8, 16
 RNN_AMD_EVERYTHING = 31

@@ -43,6 +43,9 @@ struct ChainSegment {
   bool one, pad; /* 16-stream row tiles; rows of the launch that are not the call's: multiplied along, never stored */
   int nvalid, vlo;
   int workers, idle_only; /* who shares a request for the top layer's delta (HoWork) */
+  int early;              /* K blocks of each burst issued under the row stores' drain (k_chain_persist_early, PC_EARLY of k_tiles.h);
+                           * 0: k_chain_persist.  The launcher has the last word: a launch that carries the tail for DENSE inputs
+                           * (known at the launch, not here) keeps k_chain_persist<.., XD>, which has no early form */
 };
 
 /* row tiles per launch: 8 XCDs x (32 seats / column tiles) */
@@ -56,6 +59,13 @@ static inline bool chain_persist_one(int seats, bool one_ok, int nrows) {
   return nrows / 16 <= seats && (nrows % 32 != 0 || one_ok);
 }
 static inline int chain_persist_rows(int seats, bool one) { return seats * (one ? 16 : 32); }
+
+/* K blocks (8 MFMAs each) of every half-step's burst that the multiplying waves issue while the finish's row stores drain
+ * (k_chain_persist.h, EARLY): hidden 1024 with 32-stream row tiles, where profiles/NOTES_r20.md measured it; 16-stream tiles
+ * have no drain beside a burst, and hidden 512 / 256 stay as they were.  RECUR_AMD_CHAIN_EARLY=0: k_chain_persist as before. */
+static inline int chain_early_blocks(int hidden_size, bool one, bool pad) {
+  return hidden_size == 1024 && !one && !pad && env_int("RECUR_AMD_CHAIN_EARLY", 1) ? PC_EARLY : 0;
+}
 
 /* the one-launch chain takes `nrows` rows of this shape (whether it is available is the launcher's to know) */
 static inline bool chain_persist_takes(const RamdShape *sh, const RamdBuffers *b, int nrows) {
@@ -164,5 +174,6 @@ static inline bool chain_segment(const ChainPlan &p, int r, ChainSegment *s) {
   const int busy = (s->nrows / (s->one ? 16 : 32)) * p.nt;
   s->idle_only = 256 - busy >= 128;
   s->workers = s->idle_only ? 256 - busy : 256;
+  s->early = chain_early_blocks(32 * p.nt, s->one, s->pad);
   return true;
 }

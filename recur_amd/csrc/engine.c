@@ -63,6 +63,7 @@ void rnn_amd_synchronize(void) {
 }
 void rnn_amd_kernel_time_enable(int enable) { ramd_timing_enable(enable); }
 long rnn_amd_fwd_top_launches(void) { return ramd_fwd_top_launches(); }
+long rnn_amd_chain_early_launches(void) { return ramd_chain_early_launches(); }
 double rnn_amd_kernel_time_ms(int which, long *launches, int reset) {
   return ramd_timing_ms(which, launches, reset);
 }

@@ -21,6 +21,11 @@ constexpr int W_STAGE_FLOATS = (WM + WN) * WK; /* 32 KB */
 constexpr int PC_SUB = 16;
 constexpr int PC_RED_FLOATS = 4 * PC_SUB * 32;
 constexpr int pc_lds_bytes(int K) { return (2 * PC_SUB * K + 2 * PC_RED_FLOATS) * 4 + 64; }
+/* the K blocks (8 MFMAs each) that its early form issues under the row stores' drain (k_chain_persist.h, EARLY, beside the two
+ * constants tuned to it): chain_plan.h hands the number to the launcher, which has that one instantiation */
+#ifndef PC_EARLY
+#define PC_EARLY 1
+#endif
 constexpr int FF_MAXIN = 64;    /* k_fwd_fused: dense input columns at most */
 constexpr int T2_NB = 17;       /* k_text_top2 (k_text_top2.h): float4 of W_ho per lane, i.e. a wave's rows in one batch of 4 x T2_NB */
 /* ... and the LDS its body needs, in floats: [H] hidden row, [16 waves][O] column sums, [O] outputs, [O] output error */

@@ -94,7 +94,20 @@ template <int ACT, int K, bool ONE, bool PAD, bool XD> static void launch_persis
               c.s.row0, c.s.nrows, c.D, c.seq, g_chain_sync, ramd_abort_word_dev(), c.s.nvalid, c.s.vlo, c.hw, c.xc, c.seats.mode,
               tseq, c.seats.seats);
 }
+/* the form that starts each burst under the row stores' drain (chain_plan.h: chain_early_blocks), and how often it ran */
+static long g_early_launches = 0;
+extern "C" long ramd_chain_early_launches(void) { return g_early_launches; }
+template <int ACT> static void launch_persist_early(const PersistLaunch &c) {
+  const unsigned tseq = c.seats.mode ? 0u : ++g_ticket_launches;
+  raise_lds_limit<k_chain_persist_early<ACT, PC_EARLY>>(pc_lds_bytes(1024));
+  RAMD_LAUNCH((k_chain_persist_early<ACT, PC_EARLY>), dim3(256), dim3(512), pc_lds_bytes(1024), c.st, c.d_view, c.uniform_idx,
+              c.s.row0, c.s.nrows, c.D, c.seq, g_chain_sync, ramd_abort_word_dev(), c.s.nvalid, c.s.vlo, c.hw, c.xc, c.seats.mode,
+              tseq, c.seats.seats);
+  g_early_launches++;
+}
 template <int ACT, int K, bool XD> static void launch_persist_tiles(const PersistLaunch &c) {
+  if constexpr (K == 1024 && !XD) /* (the text step's tail only: the dense tail keeps its one kernel) */
+    if (c.s.early) return launch_persist_early<ACT>(c);
   if (c.s.pad) launch_persist<ACT, K, true, true, XD>(c);
   else if (c.s.one) launch_persist<ACT, K, true, false, XD>(c);
   else launch_persist<ACT, K, false, false, XD>(c);

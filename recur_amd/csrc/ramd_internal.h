@@ -483,6 +483,7 @@ void ramd_launch_fused_updates(ramd_stream_t st, const RamdShape *sh, const Ramd
 unsigned ramd_chain_abort_word(void);
 unsigned *ramd_abort_word_dev(void);
 long ramd_fwd_top_launches(void); /* kernels_forward.hip: launches of the forward + top kernel so far */
+long ramd_chain_early_launches(void); /* kernels_chain.hip: launches of k_chain_persist_early so far */
 /* the library has created a second stream with work that may run beside the BPTT chain: the chain then stops
  * deriving its workgroups' XCDs from their numbers (kernels_chain.hip) */
 void ramd_note_side_stream(void);
